@@ -6,13 +6,17 @@ solved from the built-in cold start to KKT error <= tol, parameters already resi
 left in HBM, then the single result gather (tf, status, iters) to rank 0.
 Workload at N=1: BASELINE.json configs[2] -- the 4096-NLP Isp x dry-mass sweep of the model the reference
 declares, i.e. WITH its MV move penalty angledoubledot.DCOST = 1e-5 (Launch_Optimiser.py:99; --no-dcost times the
-unpenalised NLP as the headline instead; the other variant is always reported beside it as a secondary line).
+unpenalised NLP as the headline instead; with --full the other variant is reported beside it as a secondary line).
 With N ranks (weak scaling) every rank solves that same sweep, so the N=1 and N=8 lines time the same per-GPU work;
 --batch-per-gpu 32768 with --gpus 8 is config 4 itself (rank r = its contiguous shard of the 262 144-problem box).
 
-Prints ONE JSON line (rank 0).  `roofline.achieved` = algorithmic HBM bytes of the solve kernel
-(SURVEY.md 8d: B_alg = B_io + I*B_iter per NLP, I = iterations actually taken) / its HIP-event time;
-`cpu_baseline` = the plain-C oracle on the host cores for a bounded sample of the same workload.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`) with the configuration; --dump-outputs DIR writes what the last timed step computed.
+--full adds everything that takes runs of its own: `roofline.achieved` = algorithmic HBM bytes of the solve kernel
+(B_alg = B_io + I*B_iter per NLP, I = iterations actually taken, split by grid level with untimed
+solves of the coarser grids) / its HIP-event time; the secondary lines (continuation, the other DCOST variant, two
+streams, the other BASELINE configurations); `cpu_baseline` = the plain-C oracle on the host cores for a bounded
+sample of the same workload.
 """
 from __future__ import annotations
 
@@ -85,6 +89,33 @@ def source_sha16() -> str:
     return h.hexdigest()[:16]
 
 
+DUMP_TRAJ_BYTES = 48 << 20     # trajectories written by --dump-outputs; the per-NLP scalars come on top (64 MB in all)
+
+
+def dump_outputs(d: str, out: dict, gathered=None) -> None:
+    """The arrays the timed path hands its caller after its last step, as d/<name>.npy in float64: tf, status, iters
+    (per NLP), traj (10, nt, NLPs) and, with several ranks, the gathered (tf, status, iters) of every rank.  If the
+    trajectories of the whole batch exceed DUMP_TRAJ_BYTES, traj holds a fixed seeded sample of the NLPs (a power-of-two
+    count, ascending indices in traj_nlp_index.npy)."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    arrs = {k: out[k].cpu().numpy().astype(np.float64) for k in ("tf", "status", "iters")}
+    traj = out["traj"]
+    B = traj.shape[2]
+    n = B
+    while n > 1 and n * traj.shape[0] * traj.shape[1] * 8 > DUMP_TRAJ_BYTES:
+        n //= 2
+    if n < B:
+        idx = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+        arrs["traj_nlp_index"] = idx.astype(np.float64)
+        traj = traj.index_select(2, torch.from_numpy(idx).to(traj.device))
+    arrs["traj"] = traj.cpu().numpy()
+    if gathered is not None:
+        arrs["gathered_tf_status_iters"] = torch.stack(gathered).cpu().numpy()
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def usable_cores() -> int:
     """Host cores this process may actually use: affinity mask capped by the cgroup CPU quota."""
     n = len(os.sched_getaffinity(0))
@@ -138,7 +169,12 @@ def main():
     ap.add_argument("--no-pipelined", action="store_true", help="skip the secondary two-stream (overlapped batches) measurement")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the secondary lines for BASELINE configs 1, 4 (one shard) and 5")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for a CPU rehearsal of the gather)")
+    ap.add_argument("--full", action="store_true", help="also measure the roofline object and the secondary lines (continuation, the other DCOST "
+                    "variant, two streams, other configs, CPU baselines; the --no-* options above skip some of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import lunar_module_ascent_trajectory_optimiser_amd as A
@@ -238,11 +274,37 @@ def main():
         t = torch.tensor([conv_local, conv_all_steps], dtype=torch.float64, device=cdev)
         dist.all_reduce(t)
         conv_total, conv_all_steps = int(t[0].item()), int(t[1].item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, gathered)
     if rank == 0:
+        lv = nested_levels(NT)
+        line = {
+            "metric": "solved ascent NLPs/sec (N=200 collocation nodes)",
+            "value": conv_all_steps / elapsed,
+            "unit": "NLPs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {
+                "workload": ("BASELINE.json configs[2]: 4096-NLP Isp x dry-mass sweep (64x64, Isp 300-320 s, dry mass 2345-2545 kg)"
+                             if B == 4096 else f"{B}-NLP sweep per GPU") + ", N=200 nodes, backward Euler (reference NODES=2), "
+                            + (f"DCOST applied (the script's MV move penalty {args.dcost:g}, Launch_Optimiser.py:99, as an l1 term: the model the reference declares)"
+                               if mp else "DCOST not applied (the unpenalised NLP; the script's MV move penalty, Launch_Optimiser.py:99, switched off)"),
+                "move_penalty": bool(mp), "dcost": args.dcost if mp else 0.0,
+                "batch_per_gpu": B, "global_batch": B * world, "n_nodes": NT, "tol": args.tol,
+                "start": f"cold (built-in straight-line guess, mu0=0.1) on a {lv[-1]}-node grid, prolonged grid by grid ({' -> '.join(str(n) for n in lv[::-1])} nodes) "
+                         "(nested iteration, part of the solver and of the timed step)",
+                "parallelism": f"problem-sharded x{world}, gather only",
+                "iterations_min_mean_max": [int(iters.min()), float(iters.mean()), int(iters.max())],
+                "converged": conv_total, "of": B * world, "converged_over_all_timed_steps": conv_all_steps,
+                "kernel_source_sha16": source_sha16(),
+            },
+        }
+    if rank == 0 and args.full:
         k_ms = float(np.mean(kernel_ms))
         # iterations per grid level: `iters` counts all levels of the nested iteration; untimed solves of the coarser
         # grids alone (the same first legs, deterministic, at the coarse legs' tolerance) give the split
-        lv = nested_levels(NT)
         cum = [iters.astype(np.int64)]
         for n in lv[1:]:
             sub = A.solve_batch_torch(P_t, n, tol=max(args.tol, 1e-3), want_traj=False, sync=True, move_penalty=mp)
@@ -279,45 +341,22 @@ def main():
                     "traffic": traffic_of(key) if key else None, "kernel_ms": ms, "algorithmic_bytes_per_launch": b_,
                     "fp64_frac": f_ / (ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
                     "iterations_mean_by_grid": {str(n_): it_ / len(res.iters) for n_, it_ in levels_}}
-        line = {
-            "metric": "solved ascent NLPs/sec (N=200 collocation nodes)",
-            "value": conv_all_steps / elapsed,
-            "unit": "NLPs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {
-                "workload": ("BASELINE.json configs[2]: 4096-NLP Isp x dry-mass sweep (64x64, Isp 300-320 s, dry mass 2345-2545 kg)"
-                             if B == 4096 else f"{B}-NLP sweep per GPU") + ", N=200 nodes, backward Euler (reference NODES=2), "
-                            + (f"DCOST applied (the script's MV move penalty {args.dcost:g}, Launch_Optimiser.py:99, as an l1 term: the model the reference declares)"
-                               if mp else "DCOST not applied (the unpenalised NLP; the script's MV move penalty, Launch_Optimiser.py:99, switched off)"),
-                "move_penalty": bool(mp), "dcost": args.dcost if mp else 0.0,
-                "batch_per_gpu": B, "global_batch": B * world, "n_nodes": NT, "tol": args.tol,
-                "start": f"cold (built-in straight-line guess, mu0=0.1) on a {lv[-1]}-node grid, prolonged grid by grid ({' -> '.join(str(n) for n in lv[::-1])} nodes) "
-                         "(nested iteration, part of the solver and of the timed step)",
-                "parallelism": f"problem-sharded x{world}, gather only",
-                "iterations_min_mean_max": [int(iters.min()), float(iters.mean()), int(iters.max())],
-                "iterations_mean_by_grid": {str(n): float(it.mean()) for n, it in zip(lv, per_level)},
-                "converged": conv_total, "of": B * world, "converged_over_all_timed_steps": conv_all_steps,
-                "kernel_source_sha16": source_sha16(),
-            },
-            "roofline": {
-                "bound": "hbm", "binding": "fp64_issue", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                "kernel": (("p_solve (persistent kernel: one wavefront owns four NLPs for a whole grid level; one launch per grid level, "
-                            f"{len(lv)} levels) + p_init / p_transfer / p_finish") if A.default_path(B, NT, move_penalty=mp) == "persist" else
-                           "k_solve (fused, one lane per NLP), one launch per grid level" if A.default_path(B, NT, move_penalty=mp) == "fused" else
-                           A.default_path(B, NT, move_penalty=mp)),
-                "kernel_ms": k_ms, "algorithmic_bytes_per_launch": b_alg,
-                "fp64_achieved_tflops": f_alg / (k_ms * 1e-3) / 1e12,
-                "fp64_frac": f_alg / (k_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
-                "algorithmic_bytes_note": "SURVEY 8d's 21 doubles per node read + written per iteration; the penalised NLP carries 26 (lambda_u and the slack pair with its multipliers), not counted",
-                "note": ("kernel_ms = device time of one whole solve (HIP events around all launches of the step; p_solve is 97 % of it: "
-                         "profiles/); achieved = SURVEY 8d algorithmic bytes of the solve (iterations x nodes of every grid level x 2 x 21 "
-                         "doubles + i/o) / that time. The kernel is FP64-issue bound, not HBM bound: one wavefront per SIMD issues one "
-                         "instruction per 4 cycles, and the serial sweeps keep 10 of 16 lanes per NLP busy: see DESIGN.md section 5"),
-            },
+        line["config"]["iterations_mean_by_grid"] = {str(n): float(it.mean()) for n, it in zip(lv, per_level)}
+        line["roofline"] = {
+            "bound": "hbm", "binding": "fp64_issue", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "kernel": (("p_solve (persistent kernel: one wavefront owns four NLPs for a whole grid level; one launch per grid level, "
+                        f"{len(lv)} levels) + p_init / p_transfer / p_finish") if A.default_path(B, NT, move_penalty=mp) == "persist" else
+                       "k_solve (fused, one lane per NLP), one launch per grid level" if A.default_path(B, NT, move_penalty=mp) == "fused" else
+                       A.default_path(B, NT, move_penalty=mp)),
+            "kernel_ms": k_ms, "algorithmic_bytes_per_launch": b_alg,
+            "fp64_achieved_tflops": f_alg / (k_ms * 1e-3) / 1e12,
+            "fp64_frac": f_alg / (k_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
+            "algorithmic_bytes_note": "SURVEY 8d's 21 doubles per node read + written per iteration; the penalised NLP carries 26 (lambda_u and the slack pair with its multipliers), not counted",
+            "note": ("kernel_ms = device time of one whole solve (HIP events around all launches of the step; p_solve is 97 % of it: "
+                     "profiles/); achieved = SURVEY 8d algorithmic bytes of the solve (iterations x nodes of every grid level x 2 x 21 "
+                     "doubles + i/o) / that time. The kernel is FP64-issue bound, not HBM bound: one wavefront per SIMD issues one "
+                     "instruction per 4 cycles, and the serial sweeps keep 10 of 16 lanes per NLP busy: see DESIGN.md section 5"),
         }
         if world == 1 and not args.no_continuation:
             # Secondary, differently-defined number (never `value`): the same sweep under a continuation policy --
@@ -476,6 +515,7 @@ def main():
             tf_gpu = out["tf"].cpu().numpy()[idx[order]]
             cb["max_rel_tf_diff_vs_gpu"] = float(np.max(np.abs(tf_cpu - tf_gpu) / tf_cpu))
             line["cpu_baseline"] = cb
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if dist:
         dist.barrier()
