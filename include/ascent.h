@@ -176,8 +176,8 @@ int ascent_kkt_step(const ascent_params *p, int64_t batch, const ascent_opts *o,
                     int32_t *inertia_out, int device_id);
 
 /* The same two parity surfaces through a chosen solver path.  ascent_eval_nodes / ascent_kkt_step above take the path
- * ascent_solve_batch would take for that batch (batch-size rule, ASCENT_PIPELINE / ASCENT_FACTOR environment
- * overrides); these run one round of exactly the kernels of the named path at the given iterate:
+ * ascent_solve_batch would take for that batch (the same routing decision, environment overrides included; see
+ * ascent_default_path); these run one round of exactly the kernels of the named path at the given iterate:
  *   ASCENT_PATH_FUSED       k_eval_nodes / the passes of k_solve (scheme 0, formulation 0 only)
  *   ASCENT_PATH_SPLIT_LANE  q_trial_eval -> q_decide_factor -> q_forward -> q_local -> q_adjoint
  *   ASCENT_PATH_SPLIT_WIDE  q_trial_eval -> q_factor_wide -> q_forward_wide -> q_local -> q_adjoint_wide
@@ -191,8 +191,10 @@ enum ascent_path { ASCENT_PATH_AUTO = 0, ASCENT_PATH_FUSED = 1, ASCENT_PATH_SPLI
                                               h_solve (scheme 2, Hermite-Simpson, without the move penalty): ascent_kkt_step_path returns its
                                               Newton step; ascent_eval_nodes_path (schemes 0 / 1) the node rows it stages in LDS for the
                                               factorisation sweep, copied out before the sweep would read them */ };
-/* Which kernels ascent_solve_batch runs for a batch of this size with these options (and the environment overrides):
- * an ascent_path value, never ASCENT_PATH_AUTO.  No device work. */
+/* Which kernels ascent_solve_batch runs for a batch of this size with these options (and the environment overrides
+ * ASCENT_PIPELINE, ASCENT_FACTOR, ASCENT_SMALL_BATCH, ASCENT_DENSE_NEWTON, read on every call): an ascent_path value, never
+ * ASCENT_PATH_AUTO -- the decision the solve itself makes, not a second copy of it.  No device work.  (A path that cannot
+ * carry the options -- ASCENT_PIPELINE=split with the move penalty, say -- is reported as it is; the solve then refuses.) */
 int ascent_default_path(int64_t batch, const ascent_opts *o);
 /* Diagnostic (no device work): the persistent kernel's device workspace for a solve of `batch` NLPs with these options.
  * Returns the number of grid levels of the nested iteration (>= 1) or a negative code; out4[0] = bytes allocated,

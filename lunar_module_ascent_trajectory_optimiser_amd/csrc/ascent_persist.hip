@@ -1462,13 +1462,6 @@ static PGeo geo_of(int K, int form = 0, int mp = 0, int term = 0, int wide = 0, 
   g.form = form; g.mp = mp ? 1 : 0; g.term = term == 2 ? 2 : 0; g.wide = wide ? 1 : 0;
   return g;
 }
-// Batches that cannot give every SIMD a wavefront of four NLPs (MI355X: 256 CUs x 4 SIMDs) run one NLP per wavefront
-// (every variant of the kernel has both forms).
-static int use_wide(long batch, int scheme, int form, int mp, int term) {
-  (void)scheme; (void)form; (void)mp; (void)term;
-  if (const char *e = getenv("ASCENT_PERSIST_WIDE")) return e[0] == '1';
-  return batch <= 1024;
-}
 
 // One grid level's workspace, rounded up to a multiple of 256 bytes: the two regions of the nested iteration are laid out
 // back to back with exactly these sizes (persist_region1_offset below is the one place that says where the second one starts).
@@ -1538,13 +1531,10 @@ static void launch_solve(int scheme, int form, int mp, long batch, hipStream_t s
 // All grid levels of the nested iteration (levels[0] = the requested grid, finest first; the coarsest is solved first, cold or
 // from the caller's guess): p_init, then per level p_solve and p_transfer to the next finer grid, p_finish at the end.  Two
 // workspace regions alternate between the levels.  mp: with the l1 move penalty (schemes 0 / 1, formulation 0).
-int persist_run_nested(const ascent_params *dp, long batch, int scheme, int form, int mp, int term, const int *levels, int nlev, double *ws, const double *dguess, int warm,
+int persist_run_nested(const ascent_params *dp, long batch, int scheme, int form, int mp, int term, int wide, const int *levels, int nlev, double *ws, const double *dguess, int warm,
                        int max_iter, double tol, double tol_coarse, double mu0, double mu_first, double mu_next, double *dtraj,
                        double *dtf, int *dstatus, int *diters, double *dblob, hipStream_t stream, char *err, size_t errlen) {
-  if (term == 2 && form != 0) { snprintf(err, errlen, "the persistent kernel carries terminal 2 for formulation 0 only"); return ASCENT_E_ARG; }
-  if (scheme == 2 && (form != 0 || mp)) { snprintf(err, errlen, "the persistent Hermite-Simpson kernel has formulation 0 without the move penalty only"); return ASCENT_E_ARG; }
   double *region[2] = {ws, (double *)((char *)ws + persist_region1_offset(levels, batch, mp))};
-  const int wide = use_wide(batch, scheme, form, mp, term);
   PGeo g = geo_of(levels[nlev - 1] - 1, form, mp, term, wide, scheme);
   double *w = region[(nlev - 1) & 1];
   hipLaunchKernelGGL(p_init, dim3((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, w, dguess,
@@ -1568,11 +1558,9 @@ int persist_run_nested(const ascent_params *dp, long batch, int scheme, int form
 // One round of p_solve at a caller-supplied iterate (parity surface ascent_kkt_step_path): the iterate as it is, mu and
 // delta_w per problem from the caller; p_probe_out hands back the Newton step.  (mp: the slack pairs, which the blob does
 // not carry, are set around the iterate's own movement as every warm start sets them.)
-int persist_probe(const ascent_params *dp, long batch, int scheme, int form, int mp, int term, int K, double *ws, const double *diterate, const double *dmu, const double *ddw,
+int persist_probe(const ascent_params *dp, long batch, int scheme, int form, int mp, int term, int wide, int K, double *ws, const double *diterate, const double *dmu, const double *ddw,
                   double *dstep, int *dinertia, hipStream_t stream, char *err, size_t errlen) {
-  if (term == 2 && form != 0) { snprintf(err, errlen, "the persistent kernel carries terminal 2 for formulation 0 only"); return ASCENT_E_ARG; }
-  if (scheme == 2 && (form != 0 || mp)) { snprintf(err, errlen, "the persistent Hermite-Simpson kernel has formulation 0 without the move penalty only"); return ASCENT_E_ARG; }
-  const PGeo g = geo_of(K, form, mp, term, use_wide(batch, scheme, form, mp, term), scheme);
+  const PGeo g = geo_of(K, form, mp, term, wide, scheme);
   const dim3 ng((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)batch);
   hipLaunchKernelGGL(p_init, ng, dim3(WAVE), 0, stream, dp, batch, g, ws, diterate, 2, 0.1, dmu, ddw, 1);
   launch_solve(scheme, form, mp, batch, stream, dp, g, ws, 1000, -1.0);
@@ -1584,9 +1572,9 @@ int persist_probe(const ascent_params *dp, long batch, int scheme, int form, int
 // The node rows of the same kernel (parity surface ascent_eval_nodes_path): one round of p_solve up to the point where the
 // blocks of every chunk stand in LDS; they are copied out instead of being swept.  dzero: a device array of `batch` zeros
 // (mu and delta_w do not enter the rows).
-int persist_probe_rows(const ascent_params *dp, long batch, int scheme, int form, int K, double *ws, const double *diterate, const double *dzero,
+int persist_probe_rows(const ascent_params *dp, long batch, int scheme, int form, int wide, int K, double *ws, const double *diterate, const double *dzero,
                        double *ddefects, double *djac, double *dhess, hipStream_t stream, char *err, size_t errlen) {
-  const PGeo g = geo_of(K, form, 0, 0, use_wide(batch, scheme, form, 0, 0));
+  const PGeo g = geo_of(K, form, 0, 0, wide);
   const dim3 ng((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)batch);
   hipLaunchKernelGGL(p_init, ng, dim3(WAVE), 0, stream, dp, batch, g, ws, diterate, 2, 0.1, dzero, dzero, 2);
   launch_solve(scheme, form, 0, batch, stream, dp, g, ws, 1000, -1.0);

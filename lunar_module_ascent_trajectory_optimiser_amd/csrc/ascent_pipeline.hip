@@ -1,6 +1,6 @@
 // Split pipeline of the batched ascent NLP solver for small and medium batches (gfx950).
 //
-// The fused kernel (ascent_solver.hip) gives every NLP one lane and sweeps the 199 collocation steps
+// The fused kernel (ascent_fused.hip) gives every NLP one lane and sweeps the 199 collocation steps
 // serially for everything; at batch 4096 that occupies 64 of the chip's 1024 SIMDs.  Only the three
 // recurrences of a Newton step are inherently serial in time: the Riccati factorisation, the forward
 // substitution and the adjoint substitution.  Everything else -- the trial point x + alpha*dx, the
@@ -1599,7 +1599,7 @@ size_t pipeline_ws_bytes(int K, long batch) {
 
 int pipeline_run(const ascent_params *dp, long batch, int K, int scheme, int form, double *ws, const double *dguess, int warm,
                  int max_iter, double tol, double mu0, double *dtraj, double *dtf, int *dstatus, int *diters,
-                 double *dblob, hipStream_t stream, PipelineStats *stats, char *err, size_t errlen) {
+                 double *dblob, bool wide, hipStream_t stream, PipelineStats *stats, char *err, size_t errlen) {
   Geo g{K, (K + CHUNK - 1) / CHUNK, form, 0};
   const unsigned tiles = (unsigned)((batch + WAVE - 1) / WAVE);
   int *counters = (int *)((char *)ws + (size_t)tiles * g.tile_doubles() * sizeof(double));
@@ -1622,9 +1622,7 @@ int pipeline_run(const ascent_params *dp, long batch, int K, int scheme, int for
   // `burst` rounds back to back and reads the counters of the last one only then -- the device never waits
   // for the host inside a burst.  A lane needs at most max_iter+1 accepted trial points plus a bounded number
   // of rejected trials and refactorisations per iteration, so the loop terminates.
-  // the 16-lanes-per-NLP factorisation pays while the chip has idle SIMDs (see q_factor_wide)
-  bool wide = batch <= 4096;     // one wavefront per SIMD; beyond that the one-lane sweeps win (scripts/batch_sweep.py)
-  if (const char *e = getenv("ASCENT_FACTOR")) wide = e[0] == 'w';
+  // wide: the 16-lanes-per-NLP factorisation (q_factor_wide), which pays while the chip has idle SIMDs
   int burst = 4;
   if (const char *e = getenv("ASCENT_ROUNDS_PER_SYNC")) { const int v = atoi(e); if (v >= 1 && v <= 64) burst = v; }
   for (long round = 0;;) {

@@ -14,10 +14,10 @@ struct PipelineStats {
 size_t pipeline_ws_bytes(int K, long batch);
 
 // Solve; all pointers are device pointers.  Synchronises `stream` once per interior-point iteration
-// (it reads three counters to steer the lanes' state machines).  Returns ASCENT_OK or ASCENT_E_HIP.
+// (it reads three counters to steer the lanes' state machines).  `wide` picks the 16-lane sweeps.  Returns ASCENT_OK or ASCENT_E_HIP.
 int pipeline_run(const ascent_params *dp, long batch, int K, int scheme, int form, double *ws, const double *dguess, int warm,
                  int max_iter, double tol, double mu0, double *dtraj, double *dtf, int *dstatus, int *diters,
-                 double *dblob, hipStream_t stream, PipelineStats *stats, char *err, size_t errlen);
+                 double *dblob, bool wide, hipStream_t stream, PipelineStats *stats, char *err, size_t errlen);
 
 // One round of the pipeline's kernels at a caller-supplied iterate (the parity surface behind ascent_kkt_step /
 // ascent_eval_nodes): mu and delta_w per problem; `wide` picks the 16-lane sweeps.  With step_too == false only the

@@ -2,23 +2,13 @@
 // /root/reference/Launch_Optimiser.py, hand-written for MI355X (gfx950).  Replaces the
 // m.solve() call at Launch_Optimiser.py:177 (GEKKO -> APMonitor -> IPOPT/MUMPS).
 //
-// Kernel structure (one lane = one NLP, one 64-lane wavefront = one workgroup = one "tile" of 64 NLPs):
-//   k_solve       the whole interior-point loop; per iteration
-//                   pass B   evaluate defects/Jacobian/Hessian blocks of every collocation step and
-//                            factorise the bordered block-tridiagonal KKT system backwards in time
-//                   pass F   forward substitution: primal step, fraction-to-boundary, merit slope
-//                   pass A   adjoint substitution: multiplier step, bound-multiplier steps
-//                   pass T   merit function at trial points (backtracking line search)
-//                   pass UE  accept the step and evaluate the KKT error of the new iterate (fused)
-//   k_eval_nodes  per-(step, problem) defects + Jacobian + Hessian blocks (parity surface)
-//   k_kkt_step    one Newton step at a caller-supplied iterate (parity surface)
-//
-// Workspace layout in HBM: [tile][step k][field][64 lanes] doubles.  A pass streams the step
-// records of its tile in time order (forwards or backwards); every access of a wavefront is one
-// contiguous 512-byte row whose address is a wave-uniform base plus the lane, so loads use scalar
-// base registers.  Each pass is written as  prefetch(next step) / compute(current step) / store,  so
-// the HBM latency of step k-1 is hidden behind the arithmetic of step k (there is one wavefront per
-// SIMD at these register counts, so there is no other wavefront to switch to).
+// This file is the C ABI (include/ascent.h): argument checks, workspaces, staging of host pointers, the nested
+// iteration over grid levels, and route(), which picks the kernel family of a call.  The families sit behind their
+// own host interfaces:
+//   persistent p_solve / h_solve    ascent_persist.hpp (ascent_persist.hip, ascent_hs.hip)
+//   dense blocks d_* / pc_*         ascent_dense.hpp (ascent_dense.hip, ascent_blocktri.hip)
+//   split pipeline q_*              ascent_pipeline.hpp (ascent_pipeline.hip)
+//   fused k_solve                   ascent_fused.hpp (ascent_fused.hip)
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -35,797 +25,11 @@
 #include "ascent_dense.hpp"
 #include "ascent_blocktri.hpp"
 #include "ascent_persist.hpp"
+#include "ascent_fused.hpp"
 
 using namespace ascent;
 
 namespace {
-
-// rows of one step record
-constexpr int R_Z = 0, R_U = 7, R_L = 8, R_ZB = 15;          // iterate: z[7] u lambda[7] zb[6]
-constexpr int R_DZ = 21, R_DU = 28, R_DL = 29, R_DZB = 36;   // step:    same order
-constexpr int R_G = 42, R_E = 50, R_H = 54, R_F = 64, R_C = 71, R_KA = 78, R_K0 = 85, R_ID = 88;
-constexpr int R_STAGE = 94;
-
-__host__ __device__ inline size_t tile_doubles(int K) { return (size_t)K * R_STAGE * WAVE; }
-
-struct W {  // one lane's view of its tile
-  gdbl *tile;  // wave-uniform base of this wavefront's tile
-  int K;
-  double h;
-  Der d;
-};
-using Tile = TileT<R_STAGE>;
-
-// ---------------------------------------------------------------------------------------------
-// pass UE: (optionally) accept the step  it += alpha*step  and evaluate the KKT error pieces of the
-// resulting iterate, backwards in time.  `s` holds the already-updated scalars.
-// ---------------------------------------------------------------------------------------------
-struct InUE {
-  double zp[7], dzp[7], l[7], dl[7], zb[6], dzb[6], u, du;
-};
-template <bool UPDATE>
-ASC_DEV void loadUE(const Tile &t_, int k, InUE &in) {
-  const gdbl *sp = t_.st(k);
-  ldn<7>(t_, sp, R_L, in.l);
-  ldn<6>(t_, sp, R_ZB, in.zb);
-  in.u = ROW(sp, R_U);
-  if (UPDATE) {
-    ldn<7>(t_, sp, R_DL, in.dl);
-    ldn<6>(t_, sp, R_DZB, in.dzb);
-    in.du = ROW(sp, R_DU);
-  }
-  if (k > 0) {
-    const gdbl *spp = t_.st(k - 1);
-    ldn<7>(t_, spp, R_Z, in.zp);
-    if (UPDATE) ldn<7>(t_, spp, R_DZ, in.dzp);
-  } else {
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) { in.zp[i] = 0.0; in.dzp[i] = 0.0; }
-  }
-}
-
-template <bool UPDATE>
-ASC_PASS ErrParts pass_update_error(const W &w, const Scal &s, double alpha, double adu, double mu) {
-  const Der &d = w.d;
-  const Tile t_(w.tile);
-  const int K = uniform(w.K);
-  const double hT = w.h * d.T, dt = hT * s.th;
-  double rd = 0.0, cinf = 0.0, pmin = 1e300, pmax = -1e300, l1 = 0.0, zsum = 0.0, rth = 1.0;
-  double z[7], ln[7];
-  {
-    gdbl *sp = t_.st(K - 1);
-    ldn<7>(t_, sp, R_Z, z);
-    if (UPDATE) {
-      double dz[7];
-      ldn<7>(t_, sp, R_DZ, dz);
-      ASC_UNROLL
-      for (int i = 0; i < 7; i++) z[i] += alpha * dz[i];
-      stn<7>(t_, sp, R_Z, z);
-    }
-  }
-  ASC_UNROLL
-  for (int i = 0; i < 7; i++) ln[i] = 0.0;
-  const double mlo = mu * 1e-10, mhi = mu * 1e10;
-  auto body = [&](InUE &cur, int k) __attribute__((always_inline)) {
-    gdbl *sp = t_.st(k);
-    if (UPDATE) {
-      ASC_UNROLL
-      for (int i = 0; i < 7; i++) { cur.zp[i] += alpha * cur.dzp[i]; cur.l[i] += alpha * cur.dl[i]; }
-      cur.u += alpha * cur.du;
-      const double dist[6] = {z[IA], d.aub - z[IA], z[IM], 1.0 - z[IM], cur.u + 1.0, 1.0 - cur.u};
-      ASC_UNROLL
-      for (int b = 0; b < 6; b++) {   // keep z within [mu/(k d), k mu/d], k = 1e10
-        const double id = rcp(dist[b]);
-        cur.zb[b] = fmin(fmax(cur.zb[b] + adu * cur.dzb[b], mlo * id), mhi * id);
-      }
-      if (k > 0) stn<7>(t_, t_.st(k - 1), R_Z, cur.zp);
-      stn<7>(t_, sp, R_L, cur.l);
-      stn<6>(t_, sp, R_ZB, cur.zb);
-      ROW(sp, R_U) = cur.u;
-    }
-    double G[8], F[7], fl[7], r[7], ax, ay;
-    accel<1>(d, z[IX], z[IY], z[IA], z[IM], 0.0, 0.0, ax, ay, G, nullptr);
-    rhs_f(d, z, cur.u, ax, ay, F);
-    fzt_lambda(G, cur.l, fl);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) {
-      r[i] = cur.l[i] - dt * fl[i] - ln[i];
-      rth -= hT * F[i] * cur.l[i];
-      l1 += fabs(cur.l[i]);
-      cinf = fmax(cinf, fabs(z[i] - cur.zp[i] - dt * F[i]));
-    }
-    r[IA] += cur.zb[1] - cur.zb[0];
-    r[IM] += cur.zb[3] - cur.zb[2];
-    if (k == K - 1) {
-      const Terminal t = terminal_eval(d, z);
-      r[IX] += s.nu3 * t.e3g[0] + s.nu1 * t.g1g[0];
-      r[IY] += s.nu3 * t.e3g[1] + s.nu1 * t.g1g[1];
-      r[IVX] += s.nu3 * t.e3g[2] + s.nu2 * t.g2g[0];
-      r[IVY] += s.nu3 * t.e3g[3] + s.nu2 * t.g2g[1];
-      cinf = fmax(cinf, fmax(fabs(t.e3), fmax(fabs(t.g1 - s.s1), fabs(t.g2 - s.s2))));
-    }
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) rd = fmax(rd, fabs(r[i]));
-    rd = fmax(rd, fabs(-dt * d.alpha * cur.l[IW] - cur.zb[4] + cur.zb[5]));
-    const double lo[3] = {z[IA], z[IM], cur.u + 1.0}, up[3] = {d.aub - z[IA], 1.0 - z[IM], 1.0 - cur.u};
-    ASC_UNROLL
-    for (int b = 0; b < 3; b++) {
-      const double p1 = lo[b] * cur.zb[2 * b], p2 = up[b] * cur.zb[2 * b + 1];
-      pmin = fmin(pmin, fmin(p1, p2));
-      pmax = fmax(pmax, fmax(p1, p2));
-      zsum += cur.zb[2 * b] + cur.zb[2 * b + 1];
-    }
-    cpy<7>(ln, cur.l);
-    cpy<7>(z, cur.zp);
-  };
-#define LD_(k_, buf_) loadUE<UPDATE>(t_, k_, buf_)
-  ASC_SWEEP_BACKWARD(InUE, LD_, body)
-#undef LD_
-  rd = fmax(rd, fabs(rth - s.zlt + s.zut));
-  rd = fmax(rd, fmax(fabs(-s.nu1 - s.zs1), fabs(-s.nu2 - s.zs2)));
-  const double pr[4] = {(s.th - d.tlb) * s.zlt, (d.tub - s.th) * s.zut, s.s1 * s.zs1, s.s2 * s.zs2};
-  ASC_UNROLL
-  for (int j = 0; j < 4; j++) { pmin = fmin(pmin, pr[j]); pmax = fmax(pmax, pr[j]); }
-  l1 += fabs(s.nu3) + fabs(s.nu1) + fabs(s.nu2);
-  zsum += s.zlt + s.zut + s.zs1 + s.zs2;
-  ErrParts e;
-  e.rd = rd; e.cinf = cinf; e.pmin = pmin; e.pmax = pmax;
-  e.sd = fmax(100.0, (l1 + zsum) / (double)(13 * K + 7)) * 0.01;
-  return e;
-}
-
-// ---------------------------------------------------------------------------------------------
-// pass B: evaluate + backward factorisation.  Returns 0, or 1 when the inertia is wrong.
-// ---------------------------------------------------------------------------------------------
-struct BorderOut {
-  double dth, dnu3, c1, sig1, sig2, rs1, rs2;
-};
-struct InB {
-  double zp[7], l[7], zb[6], u;
-};
-ASC_DEV void loadB(const Tile &t_, int k, InB &in) {
-  const gdbl *sp = t_.st(k);
-  ldn<7>(t_, sp, R_L, in.l);
-  ldn<6>(t_, sp, R_ZB, in.zb);
-  in.u = ROW(sp, R_U);
-  if (k > 0) {
-    ldn<7>(t_, t_.st(k - 1), R_Z, in.zp);
-  } else {
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) in.zp[i] = 0.0;
-  }
-}
-
-ASC_PASS int pass_backward(const W &w, const Scal &s, double mu, double dw, BorderOut &out) {
-  const Der &d = w.d;
-  const Tile t_(w.tile);
-  const int K = uniform(w.K);
-  const double hT = w.h * d.T, dt = hT * s.th, be = dt * d.alpha;
-  double P[28], p0[7], p1[7], p2[7];
-  ASC_UNROLL
-  for (int i = 0; i < 28; i++) P[i] = 0.0;
-  ASC_UNROLL
-  for (int i = 0; i < 7; i++) { p0[i] = p1[i] = p2[i] = 0.0; }
-  double S10 = 0.0, S11 = 0.0, S12 = 0.0, S20 = 0.0, S22 = 0.0, rth = 1.0;
-  double z[7], ln[7];
-  ldn<7>(t_, t_.st(K - 1), R_Z, z);
-  ASC_UNROLL
-  for (int i = 0; i < 7; i++) ln[i] = 0.0;
-  const Terminal tm = terminal_eval(d, z);
-  const double is1 = rcp(s.s1), is2 = rcp(s.s2);
-  const double sig1 = s.zs1 * is1 + dw, sig2 = s.zs2 * is2 + dw;
-  const double rs1 = -mu * is1 - s.nu1, rs2 = -mu * is2 - s.nu2;
-  const double cg1 = tm.g1 - s.s1, cg2 = tm.g2 - s.s2;
-  double c1 = fabs(tm.e3) + fabs(cg1) + fabs(cg2);
-  int bad = 0;
-  auto body = [&](InB &cur, int k) __attribute__((always_inline)) {
-    gdbl *sp = t_.st(k);
-    double G[8], E[4], H[10], F[7], fl[7], ax, ay;
-    accel<2>(d, z[IX], z[IY], z[IA], z[IM], -dt * cur.l[IVX], -dt * cur.l[IVY], ax, ay, G, H);
-    rhs_f(d, z, cur.u, ax, ay, F);
-    implicit_block(G, dt, E);
-    fzt_lambda(G, cur.l, fl);
-    double rz[7], gt[7], cc[7];
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) {
-      rz[i] = cur.l[i] - dt * fl[i] - ln[i];
-      gt[i] = -hT * fl[i];
-      cc[i] = z[i] - cur.zp[i] - dt * F[i];
-      c1 += fabs(cc[i]);
-      rth -= hT * F[i] * cur.l[i];
-    }
-    // reciprocal distances to the bounds of angle, mass, u (reused by passes F and A)
-    const double a = z[IA], m = z[IM], u = cur.u;
-    const double id[6] = {rcp(a), rcp(d.aub - a), rcp(m), rcp(1.0 - m), rcp(u + 1.0), rcp(1.0 - u)};
-    stn<6>(t_, sp, R_ID, id);
-    rz[IA] += mu * (id[1] - id[0]);
-    rz[IM] += mu * (id[3] - id[2]);
-    const double ru = -be * cur.l[IW] + mu * (id[5] - id[4]);
-    const double gu = -hT * d.alpha * cur.l[IW];
-    const double R = cur.zb[4] * id[4] + cur.zb[5] * id[5] + dw;
-    const double qa = cur.zb[0] * id[0] + cur.zb[1] * id[1], qm = cur.zb[2] * id[2] + cur.zb[3] * id[3];
-    // N = Q_k + P_{k+1}, built in place in P
-    P[sid(IX, IX)] += H[0]; P[sid(IX, IY)] += H[1]; P[sid(IX, IA)] += H[2]; P[sid(IX, IM)] += H[3];
-    P[sid(IY, IY)] += H[4]; P[sid(IY, IA)] += H[5]; P[sid(IY, IM)] += H[6];
-    P[sid(IA, IA)] += H[7] + qa; P[sid(IA, IM)] += H[8]; P[sid(IM, IM)] += H[9] + qm;
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) P[sid(i, i)] += dw;
-    if (k == K - 1) {
-      terminal_hessian(P, tm, s.nu3, s.nu1, s.nu2, sig1, sig2);
-      const double w1 = s.nu1 + sig1 * cg1 + rs1, w2 = s.nu2 + sig2 * cg2 + rs2;
-      rz[IX] += s.nu3 * tm.e3g[0] + w1 * tm.g1g[0];
-      rz[IY] += s.nu3 * tm.e3g[1] + w1 * tm.g1g[1];
-      rz[IVX] += s.nu3 * tm.e3g[2] + w2 * tm.g2g[0];
-      rz[IVY] += s.nu3 * tm.e3g[3] + w2 * tm.g2g[1];
-    }
-    stn<8>(t_, sp, R_G, G);
-    stn<4>(t_, sp, R_E, E);
-    stn<10>(t_, sp, R_H, H);
-    stn<7>(t_, sp, R_F, F);
-    stn<7>(t_, sp, R_C, cc);
-    // M = A^-T N A^-1 (in place), pivot, gain, P_k
-    congruence(P, G, E, dt);
-    const double D = R + be * be * P[sid(IW, IW)];
-    if (!(D > 0.0)) bad = 1;
-    const double iD = rcp(D);
-    double mw[7], kap[7];
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) { mw[i] = be * P[sid(i, IW)]; kap[i] = mw[i] * iD; }
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) {
-      ASC_UNROLL
-      for (int j = i; j < 7; j++) P[sid(i, j)] -= mw[i] * kap[j];
-    }
-    stn<7>(t_, sp, R_KA, kap);
-    // three right-hand sides (0: residual, 1: -B_theta, 2: -B_nu3)
-    double n[7], nt[7], q0[7], q1[7], rc1[7], Prc[7], k00, k01, k02;
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) n[i] = -rz[i] + p0[i];
-    solveAT(G, E, dt, n, nt);
-    k00 = (be * nt[IW] - ru) * iD;
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) { q0[i] = nt[i] - mw[i] * k00; n[i] = -cc[i]; }
-    symv(P, n, Prc);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) p0[i] = q0[i] - Prc[i];
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) n[i] = -gt[i] + p1[i];
-    solveAT(G, E, dt, n, nt);
-    k01 = (be * nt[IW] - gu) * iD;
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) { q1[i] = nt[i] - mw[i] * k01; rc1[i] = hT * F[i]; }
-    symv(P, rc1, Prc);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) p1[i] = q1[i] - Prc[i];
-    cpy<7>(n, p2);
-    if (k == K - 1) { n[IX] -= tm.e3g[0]; n[IY] -= tm.e3g[1]; n[IVX] -= tm.e3g[2]; n[IVY] -= tm.e3g[3]; }
-    solveAT(G, E, dt, n, nt);
-    k02 = be * nt[IW] * iD;
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) p2[i] = nt[i] - mw[i] * k02;   // q2 = p2 (no defect part)
-    ROW(sp, R_K0) = k00; ROW(sp, R_K0 + 1) = k01; ROW(sp, R_K0 + 2) = k02;
-    // Schur-complement entries S_ij = rho_i' K0^-1 rho_j accumulated step by step
-    double a10 = D * k01 * k00, a11 = D * k01 * k01, a12 = D * k01 * k02, a20 = D * k02 * k00;
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) {
-      a10 += 0.5 * (rc1[i] * (q0[i] + p0[i]) - cc[i] * (q1[i] + p1[i]));
-      a11 += rc1[i] * (q1[i] + p1[i]);
-      a12 += rc1[i] * p2[i];
-      a20 -= cc[i] * p2[i];
-    }
-    S10 += a10; S11 += a11; S12 += a12; S20 += a20; S22 += D * k02 * k02;
-    cpy<7>(ln, cur.l);
-    cpy<7>(z, cur.zp);
-  };
-#define LD_(k_, buf_) loadB(t_, k_, buf_)
-  ASC_SWEEP_BACKWARD(InB, LD_, body)
-#undef LD_
-  if (bad) return 1;
-  const double itl = rcp(s.th - d.tlb), itu = rcp(d.tub - s.th);
-  rth += mu * (itu - itl);
-  const double sth = s.zlt * itl + s.zut * itu + dw;
-  const double a11 = sth - S11, a12 = -S12, a22 = -S22;
-  const double b1 = -rth + S10, b2 = -tm.e3 + S20;
-  const double det = a11 * a22 - a12 * a12;
-  if (!(det < 0.0)) return 1;
-  const double idet = 1.0 / det;
-  out.dth = (b1 * a22 - a12 * b2) * idet;
-  out.dnu3 = (a11 * b2 - a12 * b1) * idet;
-  out.c1 = c1; out.sig1 = sig1; out.sig2 = sig2; out.rs1 = rs1; out.rs2 = rs2;
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// pass F: forward substitution (primal step), primal fraction-to-boundary, barrier slope and the
-// barrier sum at the current iterate
-// ---------------------------------------------------------------------------------------------
-struct InF {
-  double G[8], E[4], cc[7], F[7], ka[7], k0[3], id[6], a, m, u;
-};
-ASC_DEV void loadF(const Tile &t_, int k, InF &in) {
-  const gdbl *sp = t_.st(k);
-  ldn<8>(t_, sp, R_G, in.G);
-  ldn<4>(t_, sp, R_E, in.E);
-  ldn<7>(t_, sp, R_C, in.cc);
-  ldn<7>(t_, sp, R_F, in.F);
-  ldn<7>(t_, sp, R_KA, in.ka);
-  ldn<3>(t_, sp, R_K0, in.k0);
-  ldn<6>(t_, sp, R_ID, in.id);
-  in.a = ROW(sp, R_Z + IA);
-  in.m = ROW(sp, R_Z + IM);
-  in.u = ROW(sp, R_U);
-}
-
-ASC_PASS void pass_forward(const W &w, const Scal &s, double mu, double tau, double dth, double dnu3,
-                           double &apr, double &gd, double &slog, double *dzK) {
-  const Der &d = w.d;
-  const Tile t_(w.tile);
-  const int K = uniform(w.K);
-  const double hT = w.h * d.T, dt = hT * s.th, be = dt * d.alpha;
-  double dzp[7];
-  ASC_UNROLL
-  for (int i = 0; i < 7; i++) dzp[i] = 0.0;
-  double rmax = 0.0, gsum = 0.0, lsum = 0.0;   // max of -dx/dist over all bounds; barrier slope / mu; sum of logs
-  auto body = [&](InF &cur, int k) __attribute__((always_inline)) {
-    gdbl *sp = t_.st(k);
-    double xi[7], dz[7];
-    double du = cur.k0[0] + cur.k0[1] * dth + cur.k0[2] * dnu3;
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) {
-      xi[i] = dzp[i] - cur.cc[i] + hT * cur.F[i] * dth;
-      du -= cur.ka[i] * xi[i];
-    }
-    xi[IW] += be * du;
-    solveA(cur.G, cur.E, dt, xi, dz);
-    stn<7>(t_, sp, R_DZ, dz);
-    ROW(sp, R_DU) = du;
-    cpy<7>(dzp, dz);
-    const double *id = cur.id;
-    ASC_FTBR(rmax, id[0], dz[IA]); ASC_FTBR(rmax, id[1], -dz[IA]);
-    ASC_FTBR(rmax, id[2], dz[IM]); ASC_FTBR(rmax, id[3], -dz[IM]);
-    ASC_FTBR(rmax, id[4], du); ASC_FTBR(rmax, id[5], -du);
-    gsum += dz[IA] * (id[1] - id[0]) + dz[IM] * (id[3] - id[2]) + du * (id[5] - id[4]);
-    const double a = cur.a, m = cur.m, u = cur.u;
-    lsum += log((a * (d.aub - a)) * (m * (1.0 - m)) * ((u + 1.0) * (1.0 - u)));
-  };
-#define LD_(k_, buf_) loadF(t_, k_, buf_)
-  ASC_SWEEP_FORWARD(InF, LD_, body)
-#undef LD_
-  if (rmax * apr > tau) apr = tau / rmax;
-  gd += mu * gsum;
-  slog += lsum;
-  cpy<7>(dzK, dzp);
-}
-
-// ---------------------------------------------------------------------------------------------
-// pass A: adjoint substitution (multiplier step), bound-multiplier steps, dual fraction-to-boundary,
-// and c'(lambda + dlambda) for the curvature estimate
-// ---------------------------------------------------------------------------------------------
-struct InA {
-  double G[8], E[4], H[10], dz[7], l[7], zb[6], cc[7], id[6], du;
-};
-ASC_DEV void loadA(const Tile &t_, int k, InA &in) {
-  const gdbl *sp = t_.st(k);
-  ldn<8>(t_, sp, R_G, in.G);
-  ldn<4>(t_, sp, R_E, in.E);
-  ldn<10>(t_, sp, R_H, in.H);
-  ldn<7>(t_, sp, R_DZ, in.dz);
-  ldn<7>(t_, sp, R_L, in.l);
-  ldn<6>(t_, sp, R_ZB, in.zb);
-  ldn<7>(t_, sp, R_C, in.cc);
-  ldn<6>(t_, sp, R_ID, in.id);
-  in.du = ROW(sp, R_DU);
-}
-
-ASC_PASS void pass_adjoint(const W &w, const Scal &s, double mu, double dw, double tau, double dth,
-                           double dnu3, double sig1, double sig2, double rs1, double rs2, double &adu,
-                           double &cl) {
-  const Der &d = w.d;
-  const Tile t_(w.tile);
-  const int K = uniform(w.K);
-  const double hT = w.h * d.T, dt = hT * s.th;
-  double dln[7], ln[7];
-  ASC_UNROLL
-  for (int i = 0; i < 7; i++) { dln[i] = 0.0; ln[i] = 0.0; }
-  auto body = [&](InA &cur, int k) __attribute__((always_inline)) {
-    gdbl *sp = t_.st(k);
-    const double *H = cur.H, *dz = cur.dz, *id = cur.id;
-    const double du = cur.du;
-    const double qa = cur.zb[0] * id[0] + cur.zb[1] * id[1], qm = cur.zb[2] * id[2] + cur.zb[3] * id[3];
-    double fl[7], r[7], dl[7];
-    fzt_lambda(cur.G, cur.l, fl);
-    // r = -(rz + gt*dtheta) + dlambda_{k+1} - Q dz, with rz = l - dt*fl - l_{k+1} + barrier gradient
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++)
-      r[i] = -(cur.l[i] - dt * fl[i] - ln[i]) + hT * fl[i] * dth + dln[i] - dw * dz[i];
-    r[IA] -= mu * (id[1] - id[0]);
-    r[IM] -= mu * (id[3] - id[2]);
-    r[IX] -= H[0] * dz[IX] + H[1] * dz[IY] + H[2] * dz[IA] + H[3] * dz[IM];
-    r[IY] -= H[1] * dz[IX] + H[4] * dz[IY] + H[5] * dz[IA] + H[6] * dz[IM];
-    r[IA] -= H[2] * dz[IX] + H[5] * dz[IY] + (H[7] + qa) * dz[IA] + H[8] * dz[IM];
-    r[IM] -= H[3] * dz[IX] + H[6] * dz[IY] + H[8] * dz[IA] + (H[9] + qm) * dz[IM];
-    if (k == K - 1) {
-      double zK[7], QT[28], qd[7];
-      ldn<7>(t_, sp, R_Z, zK);
-      const Terminal tm = terminal_eval(d, zK);
-      ASC_UNROLL
-      for (int i = 0; i < 28; i++) QT[i] = 0.0;
-      terminal_hessian(QT, tm, s.nu3, s.nu1, s.nu2, sig1, sig2);
-      symv(QT, dz, qd);
-      ASC_UNROLL
-      for (int i = 0; i < 7; i++) r[i] -= qd[i];
-      const double w1 = s.nu1 + sig1 * (tm.g1 - s.s1) + rs1, w2 = s.nu2 + sig2 * (tm.g2 - s.s2) + rs2;
-      r[IX] -= s.nu3 * tm.e3g[0] + w1 * tm.g1g[0] + tm.e3g[0] * dnu3;
-      r[IY] -= s.nu3 * tm.e3g[1] + w1 * tm.g1g[1] + tm.e3g[1] * dnu3;
-      r[IVX] -= s.nu3 * tm.e3g[2] + w2 * tm.g2g[0] + tm.e3g[2] * dnu3;
-      r[IVY] -= s.nu3 * tm.e3g[3] + w2 * tm.g2g[1] + tm.e3g[3] * dnu3;
-    }
-    solveAT(cur.G, cur.E, dt, r, dl);
-    stn<7>(t_, sp, R_DL, dl);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) cl += cur.cc[i] * (cur.l[i] + dl[i]);
-    // bound multipliers: dz_L = mu/d - z_L - z_L/d*dx,  dz_U = mu/d - z_U + z_U/d*dx
-    const double dx[3] = {dz[IA], dz[IM], du};
-    double dzb[6];
-    ASC_UNROLL
-    for (int b = 0; b < 3; b++) {
-      const double zl = cur.zb[2 * b], zu = cur.zb[2 * b + 1];
-      dzb[2 * b] = id[2 * b] * (mu - zl * dx[b]) - zl;
-      dzb[2 * b + 1] = id[2 * b + 1] * (mu + zu * dx[b]) - zu;
-      ASC_FTB(adu, zl, dzb[2 * b]);
-      ASC_FTB(adu, zu, dzb[2 * b + 1]);
-    }
-    stn<6>(t_, sp, R_DZB, dzb);
-    cpy<7>(dln, dl);
-    cpy<7>(ln, cur.l);
-  };
-#define LD_(k_, buf_) loadA(t_, k_, buf_)
-  ASC_SWEEP_BACKWARD(InA, LD_, body)
-#undef LD_
-}
-
-// ---------------------------------------------------------------------------------------------
-// pass T: l1 merit function at the trial point iterate + alpha*step
-// ---------------------------------------------------------------------------------------------
-struct InT {
-  double z[7], dz[7], u, du;
-};
-ASC_DEV void loadT(const Tile &t_, int k, InT &in) {
-  const gdbl *sp = t_.st(k);
-  ldn<7>(t_, sp, R_Z, in.z);
-  ldn<7>(t_, sp, R_DZ, in.dz);
-  in.u = ROW(sp, R_U);
-  in.du = ROW(sp, R_DU);
-}
-
-ASC_PASS double pass_trial(const W &w, const Scal &s, const Scal &ds, double alpha, double mu, double nu_pen) {
-  const Der &d = w.d;
-  const Tile t_(w.tile);
-  const int K = uniform(w.K);
-  const double th = s.th + alpha * ds.th, s1 = s.s1 + alpha * ds.s1, s2 = s.s2 + alpha * ds.s2;
-  const double dt = w.h * d.T * th;
-  double sl = log(((th - d.tlb) * (d.tub - th)) * (s1 * s2));
-  double c1 = 0.0, zp[7], z[7];
-  ASC_UNROLL
-  for (int i = 0; i < 7; i++) { zp[i] = 0.0; z[i] = 0.0; }
-  auto body = [&](InT &cur, int k) __attribute__((always_inline)) {
-    (void)k;
-    double F[7], ax, ay;
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) z[i] = cur.z[i] + alpha * cur.dz[i];
-    const double u = cur.u + alpha * cur.du;
-    accel<0>(d, z[IX], z[IY], z[IA], z[IM], 0.0, 0.0, ax, ay, nullptr, nullptr);
-    rhs_f(d, z, u, ax, ay, F);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) { c1 += fabs(z[i] - zp[i] - dt * F[i]); zp[i] = z[i]; }
-    // a negative factor (trial point outside a bound) gives NaN or a wrong sign pair; the fraction-to-
-    // boundary rule keeps every factor positive, and a NaN merit value is rejected by the line search
-    const double pa = z[IA] * (d.aub - z[IA]), pm = z[IM] * (1.0 - z[IM]), pu = (u + 1.0) * (1.0 - u);
-    sl += (pa > 0.0 && pm > 0.0 && pu > 0.0) ? log(pa * pm * pu) : NAN;
-  };
-#define LD_(k_, buf_) loadT(t_, k_, buf_)
-  ASC_SWEEP_FORWARD(InT, LD_, body)
-#undef LD_
-  const Terminal tm = terminal_eval(d, z);
-  c1 += fabs(tm.e3) + fabs(tm.g1 - s1) + fabs(tm.g2 - s2);
-  return th - mu * sl + nu_pen * c1;
-}
-
-// ---------------------------------------------------------------------------------------------
-// initial point
-// ---------------------------------------------------------------------------------------------
-// cold start: straight-line states toward a tangential insertion point, u = 0
-ASC_DEV void cold_guess(const W &w, Scal &s) {
-  const Der &d = w.d;
-  const Tile t_(w.tile);
-  const int K = uniform(w.K);
-  const double tf0 = 0.9, dr = 0.166, aend = 0.5, vp = sqrt(d.vp2), dt = w.h * d.T * tf0;
-  const double sdr = sin(dr), cdr = cos(dr);
-  const double xf = -d.rhof * sdr, yf = d.rhof * cdr - d.rho0;
-  for (int k = 0; k < K; k++) {
-    const double fr = (double)(k + 1) / K;
-    gdbl *sp = t_.st(k);
-    const double z[7] = {fr * xf, fr * yf, -fr * vp * cdr, -fr * vp * sdr, fr * aend, aend / (K * dt),
-                         d.mrate * dt * (k + 1)};
-    stn<7>(t_, sp, R_Z, z);
-    ROW(sp, R_U) = 0.0;
-  }
-  s.th = tf0;
-}
-
-// interior point + multipliers. mode 0/1: primal only (multipliers reset); 2: keep multipliers
-ASC_DEV void init_point(const W &w, Scal &s, int mode) {
-  const Der &d = w.d;
-  const Tile t_(w.tile);
-  const int K = uniform(w.K);
-  for (int k = 0; k < K; k++) {
-    gdbl *sp = t_.st(k);
-    ROW(sp, R_Z + IA) = push_in(ROW(sp, R_Z + IA), 0.0, d.aub);
-    ROW(sp, R_Z + IM) = push_in(ROW(sp, R_Z + IM), 0.0, 1.0);
-    ROW(sp, R_U) = push_in(ROW(sp, R_U), -1.0, 1.0);
-    if (mode != 2) {
-      ASC_UNROLL
-      for (int b = 0; b < 6; b++) ROW(sp, R_ZB + b) = 1.0;
-      ASC_UNROLL
-      for (int i = 0; i < 7; i++) ROW(sp, R_L + i) = 0.0;
-    } else {
-      ASC_UNROLL
-      for (int b = 0; b < 6; b++) ROW(sp, R_ZB + b) = fmax(ROW(sp, R_ZB + b), 1e-12);
-    }
-  }
-  s.th = push_in(s.th, d.tlb, d.tub);
-  double zK[7];
-  ldn<7>(t_, t_.st(K - 1), R_Z, zK);
-  const Terminal tm = terminal_eval(d, zK);
-  if (mode != 2) {
-    s.s1 = fmax(tm.g1, 1e-2); s.s2 = fmax(tm.g2, 1e-2);
-    s.zlt = s.zut = s.zs1 = s.zs2 = 1.0;
-    s.nu3 = s.nu1 = s.nu2 = 0.0;
-  } else {
-    s.s1 = fmax(s.s1, 1e-10); s.s2 = fmax(s.s2, 1e-10);
-    s.zlt = fmax(s.zlt, 1e-12); s.zut = fmax(s.zut, 1e-12);
-    s.zs1 = fmax(s.zs1, 1e-12); s.zs2 = fmax(s.zs2, 1e-12);
-  }
-}
-
-// Newton step at the current iterate: passes B, F, A.  Returns 0 / 1 (wrong inertia).
-struct StepInfo { double apr, adu, gd, cl, c1, slog; };
-
-ASC_DEV int newton_step(const W &w, const Scal &s, double mu, double dw, Scal &ds, StepInfo &si) {
-  BorderOut bo;
-  if (pass_backward(w, s, mu, dw, bo)) return 1;
-  const Der &d = w.d;
-  const double tau = fmax(0.99, 1.0 - mu);
-  double apr = 1.0, adu = 1.0, gd = 0.0, cl = 0.0, slog = 0.0, dzK[7];
-  pass_forward(w, s, mu, tau, bo.dth, bo.dnu3, apr, gd, slog, dzK);
-  pass_adjoint(w, s, mu, dw, tau, bo.dth, bo.dnu3, bo.sig1, bo.sig2, bo.rs1, bo.rs2, adu, cl);
-  double zK[7];
-  const Tile t_(w.tile);
-  ldn<7>(t_, t_.st(w.K - 1), R_Z, zK);
-  const Terminal tm = terminal_eval(d, zK);
-  ds.th = bo.dth; ds.nu3 = bo.dnu3;
-  ds.s1 = (tm.g1 - s.s1) + tm.g1g[0] * dzK[IX] + tm.g1g[1] * dzK[IY];
-  ds.s2 = (tm.g2 - s.s2) + tm.g2g[0] * dzK[IVX] + tm.g2g[1] * dzK[IVY];
-  ds.nu1 = bo.sig1 * ds.s1 + bo.rs1;
-  ds.nu2 = bo.sig2 * ds.s2 + bo.rs2;
-  ds.zs1 = mu / s.s1 - s.zs1 - s.zs1 / s.s1 * ds.s1;
-  ds.zs2 = mu / s.s2 - s.zs2 - s.zs2 / s.s2 * ds.s2;
-  const double dl = s.th - d.tlb, dU = d.tub - s.th;
-  ds.zlt = mu / dl - s.zlt - s.zlt / dl * ds.th;
-  ds.zut = mu / dU - s.zut + s.zut / dU * ds.th;
-  ASC_FTB(apr, dl, ds.th); ASC_FTB(apr, dU, -ds.th);
-  ASC_FTB(apr, s.s1, ds.s1); ASC_FTB(apr, s.s2, ds.s2);
-  ASC_FTB(adu, s.zlt, ds.zlt); ASC_FTB(adu, s.zut, ds.zut);
-  ASC_FTB(adu, s.zs1, ds.zs1); ASC_FTB(adu, s.zs2, ds.zs2);
-  gd += ds.th * (1.0 - mu / dl + mu / dU) - mu * ds.s1 / s.s1 - mu * ds.s2 / s.s2;
-  cl += tm.e3 * (s.nu3 + ds.nu3) + (tm.g1 - s.s1) * (s.nu1 + ds.nu1) + (tm.g2 - s.s2) * (s.nu2 + ds.nu2);
-  slog += log((dl * dU) * (s.s1 * s.s2));
-  si.apr = apr; si.adu = adu; si.gd = gd; si.cl = cl; si.c1 = bo.c1; si.slog = slog;
-  return 0;
-}
-
-ASC_DEV W make_w(double *ws, int K, const ascent_params &prm) {
-  W w;
-  w.tile = (gdbl *)ws + (size_t)blockIdx.x * tile_doubles(K);
-  w.K = K;
-  w.h = 1.0 / K;
-  w.d = derive(prm);
-  return w;
-}
-
-// external blob rows ([row][batch], include/ascent.h) <-> step records
-ASC_DEV void blob_to_tile(const W &w, const double *blob, long batch, long p, int r_z, int r_u, int r_l,
-                          int r_zb, Scal &s) {
-  const Tile t_(w.tile);
-  const int K = uniform(w.K);
-  for (int k = 0; k < K; k++) {
-    gdbl *sp = t_.st(k);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) {
-      ROW(sp, r_z + i) = blob[(7L * k + i) * batch + p];
-      ROW(sp, r_l + i) = blob[(8L * K + 7L * k + i) * batch + p];
-    }
-    ROW(sp, r_u) = blob[(7L * K + k) * batch + p];
-    ASC_UNROLL
-    for (int b = 0; b < 6; b++) ROW(sp, r_zb + b) = blob[(15L * K + 6L * k + b) * batch + p];
-  }
-  const double *sc = blob + (21L * K) * batch + p;
-  s.th = sc[S_TH * batch]; s.zlt = sc[S_ZLT * batch]; s.zut = sc[S_ZUT * batch];
-  s.s1 = sc[S_S1 * batch]; s.s2 = sc[S_S2 * batch]; s.zs1 = sc[S_ZS1 * batch]; s.zs2 = sc[S_ZS2 * batch];
-  s.nu3 = sc[S_NU3 * batch]; s.nu1 = sc[S_NU1 * batch]; s.nu2 = sc[S_NU2 * batch];
-}
-
-ASC_DEV void tile_to_blob(const W &w, double *blob, long batch, long p, int r_z, int r_u, int r_l, int r_zb,
-                          const Scal &s) {
-  const Tile t_(w.tile);
-  const int K = uniform(w.K);
-  for (int k = 0; k < K; k++) {
-    const gdbl *sp = t_.st(k);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) {
-      blob[(7L * k + i) * batch + p] = ROW(sp, r_z + i);
-      blob[(8L * K + 7L * k + i) * batch + p] = ROW(sp, r_l + i);
-    }
-    blob[(7L * K + k) * batch + p] = ROW(sp, r_u);
-    ASC_UNROLL
-    for (int b = 0; b < 6; b++) blob[(15L * K + 6L * k + b) * batch + p] = ROW(sp, r_zb + b);
-  }
-  double *sc = blob + (21L * K) * batch + p;
-  sc[S_TH * batch] = s.th; sc[S_ZLT * batch] = s.zlt; sc[S_ZUT * batch] = s.zut;
-  sc[S_S1 * batch] = s.s1; sc[S_S2 * batch] = s.s2; sc[S_ZS1 * batch] = s.zs1; sc[S_ZS2 * batch] = s.zs2;
-  sc[S_NU3 * batch] = s.nu3; sc[S_NU1 * batch] = s.nu1; sc[S_NU2 * batch] = s.nu2;
-}
-
-// ---------------------------------------------------------------------------------------------
-// kernels
-// ---------------------------------------------------------------------------------------------
-#ifdef ASCENT_PROFILE   // diagnostic build only (scripts/pass_profile.py): shader cycles per pass
-__device__ unsigned long long g_prof[8];
-#define PROF_T0 long long t0_ = clock64();
-#define PROF_ADD(i) do { long long t1_ = clock64(); prof[i] += t1_ - t0_; t0_ = t1_; } while (0)
-#else
-#define PROF_T0
-#define PROF_ADD(i) do { } while (0)
-#endif
-
-__global__ __launch_bounds__(WAVE) void k_solve(const ascent_params *params, long batch, int lpt, int K, double *ws,
-                                                const double *guess, int warm, int max_iter, double tol,
-                                                double mu_init, double *traj, double *tf_out, int *status_out,
-                                                int *iters_out, double *blob_out) {
-  const long p = (long)blockIdx.x * lpt + threadIdx.x;
-  if ((int)threadIdx.x >= lpt || p >= batch) return;
-  const W w = make_w(ws, K, params[p]);
-  Scal s;
-  // a guess whose theta is not positive means "no guess for this problem" (nested iteration: the coarse solve failed)
-  const int asked_warm = warm;
-  if (warm && !(guess[(21L * K + S_TH) * batch + p] > 0.0)) warm = 0;
-  if (warm) {
-    blob_to_tile(w, guess, batch, p, R_Z, R_U, R_L, R_ZB, s);
-  } else {
-    cold_guess(w, s);
-  }
-  init_point(w, s, warm);
-  double mu = (asked_warm && !warm) ? 0.1 : mu_init, nu_pen = 1.0, dw_last = 0.0;
-  int status = ASCENT_MAX_ITER, iters = 0;
-#ifdef ASCENT_PROFILE
-  long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  PROF_T0
-  ErrParts e = pass_update_error<false>(w, s, 0.0, 0.0, mu);
-  PROF_ADD(0);
-  for (int iter = 0; iter < max_iter; iter++) {
-    if (e.err(0.0) <= tol) { status = ASCENT_CONVERGED; break; }
-    while (mu > tol * 0.1 && e.err(mu) <= 10.0 * mu) {
-      mu = fmax(tol * 0.1, fmin(0.2 * mu, mu * sqrt(mu)));
-      nu_pen = 1.0;
-    }
-    double dw = 0.0;
-    Scal ds;
-    StepInfo si;
-    bool fail = false;
-    while (newton_step(w, s, mu, dw, ds, si)) {
-      dw = next_delta_w(dw, dw_last);
-      if (dw > 1e10) { fail = true; break; }
-    }
-    if (fail) { status = ASCENT_REGULARISATION_FAILED; break; }
-    dw_last = dw;
-    PROF_ADD(1);
-    const double curv = -si.gd + si.cl;
-    if (si.c1 > 0.0) {
-      const double need = (si.gd + 0.5 * fmax(curv, 0.0)) / (0.9 * si.c1);
-      if (nu_pen < need) nu_pen = need + 1.0;
-    }
-    const double Dm = si.gd - nu_pen * si.c1;
-    const double phi0 = s.th - mu * si.slog + nu_pen * si.c1;
-    double alpha = si.apr;
-    bool ok = false;
-    for (int ls = 0; ls < 40; ls++) {
-      const double phit = pass_trial(w, s, ds, alpha, mu, nu_pen);
-      if (isfinite(phit) && phit <= phi0 + 1e-8 * alpha * Dm + 2.220446049250313e-15 * fabs(phi0)) { ok = true; break; }
-      alpha *= 0.5;
-    }
-    if (!ok) { status = ASCENT_LINESEARCH_FAILED; break; }
-    PROF_ADD(3);
-    s.th += alpha * ds.th; s.s1 += alpha * ds.s1; s.s2 += alpha * ds.s2;
-    s.nu3 += alpha * ds.nu3; s.nu1 += alpha * ds.nu1; s.nu2 += alpha * ds.nu2;
-    s.zlt = clipz(s.zlt + si.adu * ds.zlt, s.th - w.d.tlb, mu);
-    s.zut = clipz(s.zut + si.adu * ds.zut, w.d.tub - s.th, mu);
-    s.zs1 = clipz(s.zs1 + si.adu * ds.zs1, s.s1, mu);
-    s.zs2 = clipz(s.zs2 + si.adu * ds.zs2, s.s2, mu);
-    e = pass_update_error<true>(w, s, alpha, si.adu, mu);
-    iters = iter + 1;
-    PROF_ADD(4);
-  }
-  if (status == ASCENT_MAX_ITER && e.err(0.0) <= tol) status = ASCENT_CONVERGED;
-#ifdef ASCENT_PROFILE
-  if (threadIdx.x == 0)
-    for (int i = 0; i < 8; i++) atomicAdd(&g_prof[i], (unsigned long long)prof[i]);
-#endif
-  tf_out[p] = s.th;
-  status_out[p] = status;
-  iters_out[p] = iters;
-  if (blob_out) tile_to_blob(w, blob_out, batch, p, R_Z, R_U, R_L, R_ZB, s);
-  if (traj) {
-    const Tile t_(w.tile);
-    const int nt = K + 1;
-    for (int k = 0; k < nt; k++) {
-      double z[7], u = 0.0, ax, ay;
-      if (k) {
-        ldn<7>(t_, t_.st(k - 1), R_Z, z);
-        u = ROW(t_.st(k - 1), R_U);
-      } else {
-        ASC_UNROLL
-        for (int i = 0; i < 7; i++) z[i] = 0.0;
-      }
-      accel<0>(w.d, z[IX], z[IY], z[IA], z[IM], 0.0, 0.0, ax, ay, nullptr, nullptr);
-      const double v[10] = {z[IX], z[IY], z[IVX], z[IVY], ax, ay, z[IA], z[IW], u, z[IM]};
-      ASC_UNROLL
-      for (int f = 0; f < 10; f++) traj[((long)f * nt + k) * batch + p] = v[f];
-    }
-  }
-}
-
-// thread = (problem, step): defects, Jacobian and Hessian blocks of one collocation step
-__global__ __launch_bounds__(256) void k_eval_nodes(const ascent_params *params, long batch, int K,
-                                                    const double *it, double *defects, double *jac,
-                                                    double *hess) {
-  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int k = blockIdx.y;
-  if (p >= batch) return;
-  const Der d = derive(params[p]);
-  const double th = it[(21L * K + S_TH) * batch + p];
-  const double dt = (1.0 / K) * d.T * th;
-  double z[7], zp[7], G[8], H[10], F[7], ax, ay;
-  ASC_UNROLL
-  for (int i = 0; i < 7; i++) {
-    z[i] = it[(7L * k + i) * batch + p];
-    zp[i] = k ? it[(7L * (k - 1) + i) * batch + p] : 0.0;
-  }
-  const double u = it[(7L * K + k) * batch + p];
-  const double lvx = it[(8L * K + 7L * k + IVX) * batch + p], lvy = it[(8L * K + 7L * k + IVY) * batch + p];
-  accel<2>(d, z[IX], z[IY], z[IA], z[IM], -dt * lvx, -dt * lvy, ax, ay, G, H);
-  rhs_f(d, z, u, ax, ay, F);
-  ASC_UNROLL
-  for (int i = 0; i < 7; i++) defects[(7L * k + i) * batch + p] = z[i] - zp[i] - dt * F[i];
-  ASC_UNROLL
-  for (int i = 0; i < 8; i++) jac[(8L * k + i) * batch + p] = G[i];
-  ASC_UNROLL
-  for (int i = 0; i < 10; i++) hess[(10L * k + i) * batch + p] = H[i];
-}
-
-__global__ __launch_bounds__(WAVE) void k_kkt_step(const ascent_params *params, long batch, int lpt, int K, double *ws,
-                                                   const double *it, const double *mu, const double *dw,
-                                                   double *step, int *inertia) {
-  const long p = (long)blockIdx.x * lpt + threadIdx.x;
-  if ((int)threadIdx.x >= lpt || p >= batch) return;
-  const W w = make_w(ws, K, params[p]);
-  Scal s, ds;
-  blob_to_tile(w, it, batch, p, R_Z, R_U, R_L, R_ZB, s);
-  StepInfo si;
-  const int rc = newton_step(w, s, mu[p], dw[p], ds, si);
-  inertia[p] = rc;
-  if (rc == 0) tile_to_blob(w, step, batch, p, R_DZ, R_DU, R_DL, R_DZB, ds);
-}
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -928,55 +132,89 @@ __global__ __launch_bounds__(WAVE) void k_terminal_params(const ascent_params *i
   out[p] = q;
 }
 
-bool use_dense_path(const ascent_opts *o, int64_t batch) {
-  if (o->solver_path == ASCENT_PATH_DENSE) return true;
-  const char *e = getenv("ASCENT_PIPELINE");
-  // Hermite-Simpson: the persistent kernel of ascent_hs.hip, or -- with the move penalty, or when an override names any other family -- dense blocks
-  if (o->scheme == 2 && (o->move_penalty || o->formulation != 0 || (e && strcmp(e, "persist")) || getenv("ASCENT_FACTOR"))) return true;
-  // (the move penalty and terminal 2 exist in the persistent kernel and in the dense-block path: an override that names any other family means the dense one)
-  if ((o->move_penalty || o->terminal == 2) && o->formulation == 0 && ((e && strcmp(e, "persist")) || getenv("ASCENT_FACTOR"))) return true;
-  if (e) return !strcmp(e, "dense") && o->formulation == 0;
-  // A handful of NLPs cannot fill the hand-tuned kernels (one wavefront per NLP, serial over the nodes: 2.0 ms at N=200,
-  // 4.8 ms at N=600, 17 ms at N=2000 for one NLP; 2.1 / 6.0 / 21.5 ms for eight); the dense-block path with its Newton systems
-  // solved by cyclic reduction over the nodes spreads ONE NLP over hundreds of wavefronts and costs ~1 us per node and NLP on
-  // top of a start-up that grows with log N: 3.5 ms (N=200), 4.4 ms (N=600), 8.5 ms (N=2000) for a single NLP; 4.5 / 8.6 /
-  // 23 ms for eight (scripts/small_batch_paths.py, round 3).  Taken on grids of >= 400 intervals while batch <= min(6, intervals/300).
-  // ASCENT_SMALL_BATCH=off keeps the hand-tuned path.
-  const char *sb = getenv("ASCENT_SMALL_BATCH");
-  if (sb && !strcmp(sb, "off")) return false;
-  if (o->formulation != 0 || getenv("ASCENT_FACTOR")) return false;
-  // (terminal 2 has no cyclic-reduction variant -- see the note at `pcr` in ascent_solve_batch --, and the dense Riccati recursion of one
-  //  wavefront loses to the persistent kernels at every size: one NLP at N=2000 Hermite-Simpson 131 ms against 50)
-  if (o->terminal == 2) return false;
-  const int64_t K = (int64_t)o->n_nodes - 1;
-  const int64_t lim = K < 400 ? 0 : (K / 300 < 6 ? K / 300 : 6);
-  return batch <= lim;
+// ---------------------------------------------------------------------------------------------
+// Routing: which kernel family runs a call, and in which form (DESIGN.md section 4 has the measurements behind every
+// threshold).  route() is the only reader of the routing overrides, on every call:
+//   ASCENT_PIPELINE=persist|split|fused|dense   a family by name
+//   ASCENT_FACTOR=wide|lane                     the split pipeline with its 16-lane / one-lane sweeps
+//   ASCENT_SMALL_BATCH=off                      no dense blocks for a handful of NLPs on a long grid
+//   ASCENT_DENSE_NEWTON=pcr|riccati             the dense path's Newton solver
+//   ASCENT_PERSIST_WIDE=1|0                     the persistent kernels with one / four NLPs per wavefront
+// ---------------------------------------------------------------------------------------------
+struct Route {
+  int path;       // enum ascent_path, never ASCENT_PATH_AUTO
+  bool pcr;       // ASCENT_PATH_DENSE: Newton systems by cyclic reduction over the nodes (else the serial Riccati recursion)
+  bool wide;      // ASCENT_PATH_PERSIST: one NLP per wavefront (else four)
+};
+
+// What a kernel family does not carry (beyond the option checks of check_common): nullptr, or the reason for refusing the call.
+const char *unsupported(int path, const ascent_opts *o) {
+  switch (path) {
+    case ASCENT_PATH_PERSIST:      // backward Euler (both formulations), the trapezoid, Hermite-Simpson without the move penalty
+      return o->scheme != 0 && o->formulation != 0 ? "the persistent kernels have formulation 1 with scheme 0 only"
+           : o->scheme == 2 && o->move_penalty ? "the persistent Hermite-Simpson kernel has no move penalty (the dense-block path has)"
+           : nullptr;
+    case ASCENT_PATH_DENSE:
+      return o->formulation != 0 ? "the dense-block path has formulation 0 only" : nullptr;
+    case ASCENT_PATH_FUSED:
+      if (o->scheme != 0 || o->formulation != 0) return "the fused path has scheme 0, formulation 0 only";
+      break;
+    default:      // the split pipeline
+      if (o->scheme == 2) return "scheme 2 exists in the persistent Hermite-Simpson kernel and in the dense-block path only";
+  }
+  if (o->move_penalty || o->terminal == 2)
+    return "move_penalty = 1 and terminal 2 exist in the persistent kernel and in the dense-block path only (ASCENT_PIPELINE / ASCENT_FACTOR name another family)";
+  return nullptr;
 }
 
-// The dense-block path solves its Newton systems either by the serial Riccati recursion of one wavefront per NLP or by
-// parallel cyclic reduction over the collocation nodes (one wavefront per node; ascent_blocktri.hip).  Measured
-// (profiles/r02_c_*): cyclic reduction wins while batch x nodes leaves SIMDs idle, i.e. for a handful of NLPs; the
-// crossover with the serial recursion lies around 100 NLPs.  ASCENT_DENSE_NEWTON=riccati|pcr overrides.
-bool use_pcr_newton(int64_t batch, bool move_penalty = false) {
-  const char *e = getenv("ASCENT_DENSE_NEWTON");
-  if (e && !strcmp(e, "pcr")) return true;
-  if (e && !strcmp(e, "riccati")) return false;
-  if (move_penalty) return batch <= 32;      // 16x16 node blocks: 10.9 vs 19.7 ms at 32 NLPs, 24.4 vs 19.8 at 64 (N=200); one NLP: 3.4 vs 14.2 ms, N=2000: 10.9 vs 166
-  return batch <= 64;      // scripts/small_batch_paths.py: 11.9 vs 11.9 ms at 64 NLPs (N=200), 163 vs 176 ms (N=2000); 5.8 vs 11.4 at 16
+static bool env_is(const char *e, const char *v) { return e && !strcmp(e, v); }
+
+// The path of ascent_solve_batch; the first rule that applies wins.
+static int auto_path(const ascent_opts *o, int64_t batch, const char *pipe, const char *factor, bool small_off) {
+  if (o->solver_path == ASCENT_PATH_DENSE) return ASCENT_PATH_DENSE;
+  // The move penalty, terminal 2 and Hermite-Simpson exist in the persistent kernels and in the dense-block path: an override
+  // that names any other family (ASCENT_FACTOR names the split pipeline) means the dense one.  So does Hermite-Simpson with
+  // the move penalty.
+  const bool other = (pipe && strcmp(pipe, "persist")) || factor;
+  if (o->scheme == 2 && (o->move_penalty || o->formulation != 0 || other)) return ASCENT_PATH_DENSE;
+  if ((o->move_penalty || o->terminal == 2) && o->formulation == 0 && other) return ASCENT_PATH_DENSE;
+  if (pipe) {
+    if (env_is(pipe, "dense") && o->formulation == 0) return ASCENT_PATH_DENSE;
+  } else if (!small_off && o->formulation == 0 && !factor && o->terminal != 2) {
+    // A handful of NLPs cannot fill the one-wavefront-per-NLP kernels; the dense-block path with cyclic reduction over the
+    // nodes spreads one NLP over hundreds of wavefronts: on grids of >= 400 intervals while batch <= min(6, intervals/300)
+    // (section 4d, scripts/small_batch_paths.py).  Not for terminal 2, which has no cyclic-reduction variant (see pcr below).
+    const int64_t K = (int64_t)o->n_nodes - 1;
+    const int64_t lim = K < 400 ? 0 : (K / 300 < 6 ? K / 300 : 6);
+    if (batch <= lim) return ASCENT_PATH_DENSE;
+  }
+  // the persistent kernels are ahead of the other families at every batch size (section 4a-wide, scripts/batch_sweep2.py)
+  if (o->scheme <= 2 && !unsupported(ASCENT_PATH_PERSIST, o) && (pipe ? env_is(pipe, "persist") : !factor)) return ASCENT_PATH_PERSIST;
+  // the split pipeline while the batch alone cannot fill the chip, the fused kernel above (section 4b, scripts/batch_sweep.py)
+  const bool split = o->scheme == 1 || o->formulation == 1 || env_is(pipe, "split") || (!env_is(pipe, "fused") && batch <= 24576);
+  if (!split) return ASCENT_PATH_FUSED;
+  // the 16-lanes-per-NLP sweeps pay while the chip has idle SIMDs (one wavefront per SIMD), the one-lane sweeps above
+  const bool wide = factor ? factor[0] == 'w' : batch <= 4096;
+  return wide ? ASCENT_PATH_SPLIT_WIDE : ASCENT_PATH_SPLIT_LANE;
 }
 
-// The persistent kernel (ascent_persist.hip: one wavefront owns four NLPs for the whole solve, node blocks handed from the
-// node-parallel phases to the serial sweeps through LDS) -- backward Euler (both formulations), the trapezoid, and Hermite-Simpson
-// without the move penalty (ascent_hs.hip).
-bool use_persist_path(const ascent_opts *o, int64_t batch) {
-  if (o->scheme > 2 || (o->formulation != 0 && o->scheme != 0) || (o->scheme == 2 && o->move_penalty)) return false;
-  const char *e = getenv("ASCENT_PIPELINE");
-  if (e) return !strcmp(e, "persist");
-  if (getenv("ASCENT_FACTOR")) return false;          // an explicit choice between the split pipeline's sweep kernels
-  // measured (scripts/batch_sweep2.py, N=200, three-grid nested iteration; persistent | split 16-lane | split one-lane |
-  // fused, k NLPs/s): 16: 4.6 | 3.5 | 2.3 | -; 1024: 246 | 182 | 128 | 49; 4096: 780 | 447 | 359 | 176; 8192: 770 | 483 |
-  // 514 | 302; 16 384: 848 | 502 | 649 | 555; 32 768: 905 | - | 783 | 797; 65 536: 923 | - | 759 | 881: ahead at every size
-  return true;
+// requested: ASCENT_PATH_AUTO (the path of ascent_solve_batch) or the explicit path of a parity surface.  probe: a parity
+// surface's call rather than a solve (an explicit ASCENT_DENSE_NEWTON then holds for terminal 2 as well).
+Route route(const ascent_opts *o, int64_t batch, int requested, bool probe) {
+  const char *pipe = getenv("ASCENT_PIPELINE"), *factor = getenv("ASCENT_FACTOR"), *small = getenv("ASCENT_SMALL_BATCH");
+  const char *newton = getenv("ASCENT_DENSE_NEWTON"), *pwide = getenv("ASCENT_PERSIST_WIDE");
+  const int path = requested != ASCENT_PATH_AUTO ? requested : auto_path(o, batch, pipe, factor, env_is(small, "off"));
+  Route r{path, false, false};
+  // Cyclic reduction wins while batch x nodes leaves SIMDs idle (section 4d).  Never in a solve with terminal 2: its
+  // curvature test sees no inertia and picks regularisations that stall on the nearly dependent terminal conditions.
+  if (path == ASCENT_PATH_DENSE && (o->terminal != 2 || (probe && newton))) {
+    if (env_is(newton, "pcr")) r.pcr = true;
+    else if (env_is(newton, "riccati")) r.pcr = false;
+    else r.pcr = batch <= (o->move_penalty ? 32 : 64);      // (16x16 node blocks with the move penalty)
+  }
+  // one NLP per wavefront while four per wavefront cannot give every SIMD a wavefront (section 4a-wide)
+  if (path == ASCENT_PATH_PERSIST) r.wide = pwide ? pwide[0] == '1' : batch <= 1024;
+  return r;
 }
 
 struct DeviceWs {
@@ -1029,31 +267,6 @@ static int claim_slot0(int dev) {                   // (under g_mu[dev])
   return 0;
 }
 
-// Which solver runs a batch: the split pipeline (ascent_pipeline.hip: node-parallel evaluation + thin
-// serial sweeps, best while the batch alone cannot fill the chip) or the fused one-lane-per-NLP kernel
-// (least HBM traffic and no host round trips, best for large batches).  ASCENT_PIPELINE=split|fused
-// overrides the batch-size rule.
-bool use_split_pipeline(int64_t batch) {
-  const char *e = getenv("ASCENT_PIPELINE");
-  if (e && !strcmp(e, "split")) return true;
-  if (e && !strcmp(e, "fused")) return false;
-  return batch <= 24576;   // measured crossover on MI355X, N=200 (scripts/batch_sweep.py)
-}
-
-// NLPs per wavefront (tile). 64 fills every lane; smaller values spread a small batch over more
-// wavefronts (and so more SIMDs) at the price of idle lanes.  Chosen per launch by lanes_per_tile().
-int lanes_per_tile(int64_t batch) {
-  const char *e = getenv("ASCENT_LANES_PER_WAVE");
-  if (e) { const int v = atoi(e); if (v == 64 || v == 32 || v == 16 || v == 8) return v; }
-  (void)batch;
-  return WAVE;
-}
-
-size_t ws_bytes(int K, int64_t batch, int lpt) {
-  const size_t tiles = (size_t)((batch + lpt - 1) / lpt);
-  return tiles * tile_doubles(K) * sizeof(double);
-}
-
 int ensure_ws(DeviceWs &w, size_t bytes) {
   if (!w.ev0) {
     HIPCHK(hipEventCreate(&w.ev0));
@@ -1083,6 +296,13 @@ int grow(T *&ptr, size_t &have, size_t need) {
   return 0;
 }
 
+int check_device(int device_id) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { snprintf(g_err, sizeof g_err, "no HIP device available"); return ASCENT_E_NODEVICE; }
+  if (device_id < 0 || device_id >= n || device_id >= MAX_DEV) { snprintf(g_err, sizeof g_err, "device %d of %d", device_id, n); return ASCENT_E_NODEVICE; }
+  return 0;
+}
+
 int check_common(const ascent_params *p, int64_t batch, const ascent_opts *o, int device_id) {
   if (!p || !o || batch <= 0) { snprintf(g_err, sizeof g_err, "null params/opts or batch <= 0"); return ASCENT_E_ARG; }
   if (o->n_nodes < 3 || o->n_nodes > 65536) { snprintf(g_err, sizeof g_err, "n_nodes out of range (3 .. 65536)"); return ASCENT_E_ARG; }
@@ -1096,10 +316,24 @@ int check_common(const ascent_params *p, int64_t batch, const ascent_opts *o, in
   if ((o->scheme == 2 || o->solver_path == ASCENT_PATH_DENSE) && o->formulation != 0) { snprintf(g_err, sizeof g_err, "the dense-block path (scheme 2 / ASCENT_PATH_DENSE) has formulation 0 only"); return ASCENT_E_ARG; }
   if (o->move_penalty && o->formulation != 0 && (o->scheme != 0 || o->solver_path == ASCENT_PATH_DENSE)) { snprintf(g_err, sizeof g_err, "move_penalty = 1 with formulation 1: scheme 0, persistent kernel only"); return ASCENT_E_ARG; }
   if (o->move_penalty != 0 && o->move_penalty != 1) { snprintf(g_err, sizeof g_err, "move_penalty must be 0 or 1"); return ASCENT_E_ARG; }
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { snprintf(g_err, sizeof g_err, "no HIP device available"); return ASCENT_E_NODEVICE; }
-  if (device_id < 0 || device_id >= n || device_id >= MAX_DEV) { snprintf(g_err, sizeof g_err, "device %d of %d", device_id, n); return ASCENT_E_NODEVICE; }
+  return check_device(device_id);
+}
+
+// move_penalty = 1 on host-resident parameter sets: every weight must be positive
+int check_dcost(const ascent_params *p, int64_t batch) {
+  for (int64_t i = 0; i < batch; i++)
+    if (!(p[i].dcost > 0.0)) { snprintf(g_err, sizeof g_err, "move_penalty = 1 needs ascent_params.dcost > 0 (problem %lld has %g)", (long long)i, p[i].dcost); return ASCENT_E_ARG; }
   return 0;
+}
+
+// workspace of one grid level of K intervals on the routed family
+size_t ws_bytes(const Route &r, int K, int64_t batch, int mp) {
+  switch (r.path) {
+    case ASCENT_PATH_PERSIST: return persist_ws_bytes(K, (long)batch, mp);
+    case ASCENT_PATH_DENSE: return r.pcr ? dense_pcr_ws_bytes(K, (long)batch) : dense_ws_bytes(K, (long)batch);
+    case ASCENT_PATH_FUSED: return fused_ws_bytes(K, (long)batch);
+    default: return pipeline_ws_bytes(K, (long)batch);
+  }
 }
 
 template <typename T>
@@ -1179,30 +413,22 @@ int ascent_solve_batch(const ascent_params *p, int64_t batch, const ascent_opts 
   if (!tf_out || !status_out || !iters_out) { snprintf(g_err, sizeof g_err, "null output pointer"); return ASCENT_E_ARG; }
   if (o->warm_start < 0 || o->warm_start > 2 || (o->warm_start && !guess)) { snprintf(g_err, sizeof g_err, "warm_start needs a guess blob"); return ASCENT_E_ARG; }
   if (!(o->tol > 0) || o->max_iter < 0) { snprintf(g_err, sizeof g_err, "tol must be > 0, max_iter >= 0"); return ASCENT_E_ARG; }
-  if (o->move_penalty && !ptr_is_device) {      // (device-resident parameter sets are the caller's to check: the weight must be positive)
-    for (int64_t i = 0; i < batch; i++)
-      if (!(p[i].dcost > 0.0)) { snprintf(g_err, sizeof g_err, "move_penalty = 1 needs ascent_params.dcost > 0 (problem %lld has %g)", (long long)i, p[i].dcost); return ASCENT_E_ARG; }
-  }
+  // (device-resident parameter sets are the caller's to check: the weight must be positive)
+  if (o->move_penalty && !ptr_is_device && (rc = check_dcost(p, batch))) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   hipStream_t stream = (hipStream_t)stream_;
   const int K = o->n_nodes - 1, nt = o->n_nodes;
   const size_t rows = 21 * (size_t)K + NSC;
-  const int lpt = lanes_per_tile(batch);
-  const bool dense = use_dense_path(o, batch);
-  // (terminal 2: the Riccati form.  Its two conditions are nearly dependent near the periapsis -- multipliers of -3 and -3000 -- and the
-  //  cyclic-reduction variant's curvature test, which sees no inertia, then picks regularisations that stall: 45-99 iterations on a
-  //  sweep against 31-48, max_iter on the nominal Hermite-Simpson problem; measured in round 3, the PCR kernels do carry the block)
-  const bool pcr = dense && o->terminal != 2 && use_pcr_newton(batch, o->move_penalty != 0);
-  const bool persist = !dense && use_persist_path(o, batch);
-  const bool split = o->scheme == 1 || o->formulation == 1 || use_split_pipeline(batch);
-  if ((o->move_penalty || o->terminal == 2) && !persist && !dense) { snprintf(g_err, sizeof g_err, "move_penalty / terminal 2 exist in the persistent kernel and the dense-block path only (ASCENT_PIPELINE / ASCENT_FACTOR name another family)"); return ASCENT_E_ARG; }
+  const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
+  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
+  const bool persist = r.path == ASCENT_PATH_PERSIST;
   int levels[8];
   const int nlev = nested_levels(o, levels);
   const int slot = slot_for(device_id, stream);
   DeviceWs &w = g_wss[device_id][slot];
   g_ws_last[device_id] = slot;
-  rc = ensure_ws(w, persist ? persist_ws_bytes_nested(levels, nlev, (long)batch, (int)o->move_penalty) : dense ? (pcr ? dense_pcr_ws_bytes(K, (long)batch) : dense_ws_bytes(K, (long)batch)) : split ? pipeline_ws_bytes(K, (long)batch) : ws_bytes(K, batch, lpt));
+  rc = ensure_ws(w, persist ? persist_ws_bytes_nested(levels, nlev, (long)batch, (int)o->move_penalty) : ws_bytes(r, K, batch, (int)o->move_penalty));
   if (rc) return rc;
   const double mu0 = o->mu_init > 0 ? o->mu_init : (o->warm_start ? 1e-4 : 0.1);
 
@@ -1236,7 +462,6 @@ int ascent_solve_batch(const ascent_params *p, int64_t batch, const ascent_opts 
     HIPCHK(hipGetLastError());
     dp = w.t_p;
   }
-  const unsigned grid = (unsigned)((batch + lpt - 1) / lpt);
   if (nlev > 1 && !persist) {
     size_t n3 = w.int_n, n3b = w.int_n, n3c = w.int_n, ntf = w.int_n;
     rc = grow(w.sol, w.sol_n, (21 * (size_t)(levels[1] - 1) + NSC) * batch);
@@ -1252,7 +477,7 @@ int ascent_solve_batch(const ascent_params *p, int64_t batch, const ascent_opts 
   double mu_first = o->move_penalty ? NESTED_MU_FIRST_MP : NESTED_MU_FIRST, mu_next = o->move_penalty ? nested_mu_next_mp(o->tol) : nested_mu_next(o->tol);
   if (const char *e = getenv("ASCENT_NESTED_MU")) sscanf(e, "%lf,%lf", &mu_first, &mu_next);      // experiments only ("first,next")
   if (persist) {      // all levels inside the kernel's own layout
-    rc = persist_run_nested(dp, (long)batch, (int)o->scheme, (int)o->formulation, (int)o->move_penalty, o->terminal == 2 ? 2 : 0, levels, nlev, w.ws, dguess, (int)o->warm_start, (int)o->max_iter, o->tol,
+    rc = persist_run_nested(dp, (long)batch, (int)o->scheme, (int)o->formulation, (int)o->move_penalty, o->terminal == 2 ? 2 : 0, r.wide, levels, nlev, w.ws, dguess, (int)o->warm_start, (int)o->max_iter, o->tol,
                             fmax(o->tol, NESTED_COARSE_TOL), mu0, mu_first, mu_next, dtraj, dtf, dstatus, diters,
                             dblob, stream, g_err, sizeof g_err);
     if (rc) return rc;
@@ -1266,19 +491,15 @@ int ascent_solve_batch(const ascent_params *p, int64_t batch, const ascent_opts 
     const double tol_l = fin ? o->tol : fmax(o->tol, NESTED_COARSE_TOL);
     double *traj_l = fin ? dtraj : nullptr, *tf_l = fin ? dtf : w.tfc, *blob_l = fin ? dblob : w.sol;
     int *st_l = fin ? dstatus : w.st_c, *it_l = fin ? diters : w.it_c;
-    if (dense) {
+    if (r.path == ASCENT_PATH_DENSE)
       rc = dense_run(dp, (long)batch, Kl, (int)o->scheme, o->terminal == 2 ? 2 : 0, w.ws, g_l, warm_l, (int)o->max_iter, tol_l, mu_l, traj_l, tf_l, st_l,
-                     it_l, blob_l, stream, g_err, sizeof g_err, pcr ? 1 : 0, (int)o->move_penalty);
-      if (rc) return rc;
-    } else if (split) {
+                     it_l, blob_l, stream, g_err, sizeof g_err, r.pcr ? 1 : 0, (int)o->move_penalty);
+    else if (r.path == ASCENT_PATH_FUSED)
+      rc = fused_run(dp, (long)batch, Kl, w.ws, g_l, warm_l, (int)o->max_iter, tol_l, mu_l, traj_l, tf_l, st_l, it_l, blob_l, stream, g_err, sizeof g_err);
+    else
       rc = pipeline_run(dp, (long)batch, Kl, (int)o->scheme, (int)o->formulation, w.ws, g_l, warm_l, (int)o->max_iter, tol_l, mu_l,
-                        traj_l, tf_l, st_l, it_l, blob_l, stream, nullptr, g_err, sizeof g_err);
-      if (rc) return rc;
-    } else {
-      hipLaunchKernelGGL(k_solve, dim3(grid), dim3(WAVE), 0, stream, dp, (long)batch, lpt, Kl, w.ws, g_l, warm_l,
-                         (int)o->max_iter, tol_l, mu_l, traj_l, tf_l, st_l, it_l, blob_l);
-      HIPCHK(hipGetLastError());
-    }
+                        traj_l, tf_l, st_l, it_l, blob_l, r.path == ASCENT_PATH_SPLIT_WIDE, stream, nullptr, g_err, sizeof g_err);
+    if (rc) return rc;
     if (!fin) {
       const int Kf = levels[l - 1] - 1;
       hipLaunchKernelGGL(k_prolong, dim3((unsigned)((batch + WAVE - 1) / WAVE), (unsigned)Kf), dim3(WAVE), 0, stream, w.sol,
@@ -1303,20 +524,6 @@ int ascent_solve_batch(const ascent_params *p, int64_t batch, const ascent_opts 
   return ASCENT_OK;
 }
 
-// which kernels a parity-surface call runs: an explicit path, or (AUTO) the one ascent_solve_batch would take
-static int resolve_path(int path, const ascent_opts *o, int64_t batch, bool steps = false) {
-  if (path == ASCENT_PATH_AUTO) {
-    if (use_dense_path(o, batch)) return ASCENT_PATH_DENSE;
-    if (steps && use_persist_path(o, batch)) return ASCENT_PATH_PERSIST;      // (the persistent kernel keeps its node rows in LDS)
-    const bool split = o->scheme == 1 || o->formulation == 1 || use_split_pipeline(batch);
-    if (!split) return ASCENT_PATH_FUSED;
-    bool wide = batch <= 4096;
-    if (const char *e = getenv("ASCENT_FACTOR")) wide = e[0] == 'w';
-    return wide ? ASCENT_PATH_SPLIT_WIDE : ASCENT_PATH_SPLIT_LANE;
-  }
-  return path;
-}
-
 int ascent_workspace_layout(int64_t batch, const ascent_opts *o, int64_t *out4) {
   if (!o || !out4 || batch <= 0 || o->n_nodes < 3) return ASCENT_E_ARG;
   int levels[8];
@@ -1330,7 +537,7 @@ int ascent_workspace_layout(int64_t batch, const ascent_opts *o, int64_t *out4) 
 
 int ascent_default_path(int64_t batch, const ascent_opts *o) {
   if (!o || batch <= 0) return ASCENT_E_ARG;
-  return resolve_path(ASCENT_PATH_AUTO, o, batch, true);
+  return route(o, batch, ASCENT_PATH_AUTO, false).path;
 }
 
 int ascent_eval_nodes_path(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,
@@ -1340,11 +547,12 @@ int ascent_eval_nodes_path(const ascent_params *p, int64_t batch, const ascent_o
   if (o->move_penalty) { snprintf(g_err, sizeof g_err, "the parity surfaces take the unpenalised NLP only (move_penalty = 1 is an option of ascent_solve_batch)"); return ASCENT_E_ARG; }
   if (!iterate || !defects || !jac_blocks || !hess_blocks) { snprintf(g_err, sizeof g_err, "null pointer"); return ASCENT_E_ARG; }
   if (path < ASCENT_PATH_AUTO || path > ASCENT_PATH_PERSIST) { snprintf(g_err, sizeof g_err, "unknown path %d", path); return ASCENT_E_ARG; }
-  path = resolve_path(path, o, batch, true);
-  if (path == ASCENT_PATH_PERSIST && (o->scheme > 2 || (o->scheme >= 1 && o->formulation != 0) || (o->scheme == 2 && o->move_penalty))) { snprintf(g_err, sizeof g_err, "the persistent kernels have schemes 0, 1 and 2 (formulation 1 with scheme 0 only; scheme 2 without the move penalty)"); return ASCENT_E_ARG; }
-  if (path == ASCENT_PATH_DENSE) { snprintf(g_err, sizeof g_err, "the dense-block path exposes its node evaluation through ascent_dense_records"); return ASCENT_E_ARG; }
+  const Route r = route(o, batch, path, true);
+  if (r.path == ASCENT_PATH_DENSE) { snprintf(g_err, sizeof g_err, "the dense-block path exposes its node evaluation through ascent_dense_records"); return ASCENT_E_ARG; }
   if (o->scheme == 2) { snprintf(g_err, sizeof g_err, "the node evaluation of scheme 2 is exposed through ascent_dense_records"); return ASCENT_E_ARG; }
-  if (path == ASCENT_PATH_FUSED && (o->scheme != 0 || o->formulation != 0)) { snprintf(g_err, sizeof g_err, "the fused path has scheme 0, formulation 0 only"); return ASCENT_E_ARG; }
+  ascent_opts rows_o = *o;
+  rows_o.terminal = 0;      // (the node rows do not see the terminal condition)
+  if (const char *why = unsupported(r.path, &rows_o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   { const int rc0 = claim_slot0(device_id); if (rc0) return rc0; }
@@ -1356,27 +564,21 @@ int ascent_eval_nodes_path(const ascent_params *p, int64_t batch, const ascent_o
   HIPCHK(bd.alloc((size_t)7 * K * batch)); HIPCHK(bj.alloc((size_t)8 * K * batch)); HIPCHK(bh.alloc((size_t)10 * K * batch));
   HIPCHK(hipMemcpy(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(bit.d, iterate, rows * batch * sizeof(double), hipMemcpyHostToDevice));
-  if (path == ASCENT_PATH_FUSED) {
-    hipLaunchKernelGGL(k_eval_nodes, dim3((unsigned)((batch + 255) / 256), K), dim3(256), 0, 0, bp.d, (long)batch, K,
-                       bit.d, bd.d, bj.d, bh.d);
-    HIPCHK(hipGetLastError());
-  } else if (path == ASCENT_PATH_PERSIST) {
-    rc = ensure_ws(g_ws_slot0(device_id), persist_ws_bytes(K, (long)batch, 0));
-    if (rc) return rc;
-    HIPCHK(bz.alloc(batch));
-    HIPCHK(hipMemset(bz.d, 0, batch * sizeof(double)));
-    rc = persist_probe_rows(bp.d, (long)batch, (int)o->scheme, (int)o->formulation, K, g_ws_slot0(device_id).ws, bit.d, bz.d, bd.d, bj.d, bh.d, 0,
-                            g_err, sizeof g_err);
-    if (rc) return rc;
-  } else {
-    rc = ensure_ws(g_ws_slot0(device_id), pipeline_ws_bytes(K, (long)batch));
+  if (r.path != ASCENT_PATH_FUSED) {      // (k_eval_nodes needs no workspace)
+    rc = ensure_ws(g_ws_slot0(device_id), ws_bytes(r, K, batch, 0));
     if (rc) return rc;
     HIPCHK(bz.alloc(batch));                       // mu, delta_w: not used by the node evaluation
     HIPCHK(hipMemset(bz.d, 0, batch * sizeof(double)));
-    rc = pipeline_probe(bp.d, (long)batch, K, (int)o->scheme, (int)o->formulation, g_ws_slot0(device_id).ws, bit.d, bz.d, bz.d,
-                        path == ASCENT_PATH_SPLIT_WIDE, false, nullptr, nullptr, bd.d, bj.d, bh.d, 0, g_err, sizeof g_err);
-    if (rc) return rc;
   }
+  if (r.path == ASCENT_PATH_FUSED)
+    rc = fused_eval_nodes(bp.d, (long)batch, K, bit.d, bd.d, bj.d, bh.d, 0, g_err, sizeof g_err);
+  else if (r.path == ASCENT_PATH_PERSIST)
+    rc = persist_probe_rows(bp.d, (long)batch, (int)o->scheme, (int)o->formulation, r.wide, K, g_ws_slot0(device_id).ws, bit.d, bz.d, bd.d, bj.d, bh.d, 0,
+                            g_err, sizeof g_err);
+  else
+    rc = pipeline_probe(bp.d, (long)batch, K, (int)o->scheme, (int)o->formulation, g_ws_slot0(device_id).ws, bit.d, bz.d, bz.d,
+                        r.path == ASCENT_PATH_SPLIT_WIDE, false, nullptr, nullptr, bd.d, bj.d, bh.d, 0, g_err, sizeof g_err);
+  if (rc) return rc;
   HIPCHK(hipMemcpy(defects, bd.d, (size_t)7 * K * batch * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(jac_blocks, bj.d, (size_t)8 * K * batch * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(hess_blocks, bh.d, (size_t)10 * K * batch * sizeof(double), hipMemcpyDeviceToHost));
@@ -1395,25 +597,15 @@ int ascent_kkt_step_path(const ascent_params *p, int64_t batch, const ascent_opt
   if (rc) return rc;
   if (!iterate || !mu || !delta_w || !step || !inertia_out) { snprintf(g_err, sizeof g_err, "null pointer"); return ASCENT_E_ARG; }
   if (path < ASCENT_PATH_AUTO || path > ASCENT_PATH_PERSIST) { snprintf(g_err, sizeof g_err, "unknown path %d", path); return ASCENT_E_ARG; }
-  path = resolve_path(path, o, batch, true);
-  if (o->move_penalty && path != ASCENT_PATH_PERSIST && path != ASCENT_PATH_DENSE) { snprintf(g_err, sizeof g_err, "move_penalty = 1 exists in the persistent kernel and in the dense-block path only"); return ASCENT_E_ARG; }
-  if (o->move_penalty)
-    for (int64_t i = 0; i < batch; i++)
-      if (!(p[i].dcost > 0.0)) { snprintf(g_err, sizeof g_err, "move_penalty = 1 needs ascent_params.dcost > 0 (problem %lld has %g)", (long long)i, p[i].dcost); return ASCENT_E_ARG; }
-  if (o->scheme == 2 && path != ASCENT_PATH_DENSE && path != ASCENT_PATH_PERSIST) { snprintf(g_err, sizeof g_err, "scheme 2 exists in the persistent Hermite-Simpson kernel and in the dense-block path only"); return ASCENT_E_ARG; }
-  if (path == ASCENT_PATH_PERSIST && (o->scheme > 2 || (o->scheme >= 1 && o->formulation != 0) || (o->scheme == 2 && o->move_penalty))) { snprintf(g_err, sizeof g_err, "the persistent kernels have schemes 0, 1 and 2 (formulation 1 with scheme 0 only; scheme 2 without the move penalty)"); return ASCENT_E_ARG; }
-  if (path == ASCENT_PATH_DENSE && o->formulation != 0) { snprintf(g_err, sizeof g_err, "the dense-block path has formulation 0 only"); return ASCENT_E_ARG; }
-  if (path == ASCENT_PATH_FUSED && (o->scheme != 0 || o->formulation != 0)) { snprintf(g_err, sizeof g_err, "the fused path has scheme 0, formulation 0 only"); return ASCENT_E_ARG; }
+  const Route r = route(o, batch, path, true);
+  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
+  if (o->move_penalty && (rc = check_dcost(p, batch))) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   { const int rc0 = claim_slot0(device_id); if (rc0) return rc0; }
   const int K = o->n_nodes - 1;
   const size_t rows = 21 * (size_t)K + NSC;
-  const int lpt = lanes_per_tile(batch);
-  const bool pcr_probe = path == ASCENT_PATH_DENSE && (o->terminal != 2 || getenv("ASCENT_DENSE_NEWTON")) && use_pcr_newton(batch, o->move_penalty != 0);
-  if (o->terminal == 2 && path != ASCENT_PATH_DENSE && path != ASCENT_PATH_PERSIST) { snprintf(g_err, sizeof g_err, "terminal 2 exists in the persistent kernel and in the dense-block path only"); return ASCENT_E_ARG; }
-  rc = ensure_ws(g_ws_slot0(device_id), path == ASCENT_PATH_DENSE ? (pcr_probe ? dense_pcr_ws_bytes(K, (long)batch) : dense_ws_bytes(K, (long)batch))
-                            : path == ASCENT_PATH_PERSIST ? persist_ws_bytes(K, (long)batch, (int)o->move_penalty) : path == ASCENT_PATH_FUSED ? ws_bytes(K, batch, lpt) : pipeline_ws_bytes(K, (long)batch));
+  rc = ensure_ws(g_ws_slot0(device_id), ws_bytes(r, K, batch, (int)o->move_penalty));
   if (rc) return rc;
   DevBuf<ascent_params> bp;
   DevBuf<double> bit, bmu, bdw, bst;
@@ -1429,22 +621,19 @@ int ascent_kkt_step_path(const ascent_params *p, int64_t batch, const ascent_opt
     hipLaunchKernelGGL(k_terminal_params, dim3((unsigned)((batch + WAVE - 1) / WAVE)), dim3(WAVE), 0, 0, bp.d, bp.d, (long)batch);
     HIPCHK(hipGetLastError());
   }
-  if (path == ASCENT_PATH_DENSE) {
-    rc = dense_probe(bp.d, (long)batch, K, (int)o->scheme, o->terminal == 2 ? 2 : 0, g_ws_slot0(device_id).ws, bit.d, bmu.d, bdw.d, true, bst.d, bin.d, nullptr,
-                     0, g_err, sizeof g_err, pcr_probe ? 1 : 0, (int)o->move_penalty);
-    if (rc) return rc;
-  } else if (path == ASCENT_PATH_PERSIST) {
-    rc = persist_probe(bp.d, (long)batch, (int)o->scheme, (int)o->formulation, (int)o->move_penalty, o->terminal == 2 ? 2 : 0, K, g_ws_slot0(device_id).ws, bit.d, bmu.d, bdw.d, bst.d, bin.d, 0, g_err, sizeof g_err);
-    if (rc) return rc;
-  } else if (path == ASCENT_PATH_FUSED) {
-    hipLaunchKernelGGL(k_kkt_step, dim3((unsigned)((batch + lpt - 1) / lpt)), dim3(WAVE), 0, 0, bp.d, (long)batch, lpt, K,
-                       g_ws_slot0(device_id).ws, bit.d, bmu.d, bdw.d, bst.d, bin.d);
-    HIPCHK(hipGetLastError());
-  } else {
-    rc = pipeline_probe(bp.d, (long)batch, K, (int)o->scheme, (int)o->formulation, g_ws_slot0(device_id).ws, bit.d, bmu.d, bdw.d,
-                        path == ASCENT_PATH_SPLIT_WIDE, true, bst.d, bin.d, nullptr, nullptr, nullptr, 0, g_err, sizeof g_err);
-    if (rc) return rc;
-  }
+  double *ws = g_ws_slot0(device_id).ws;
+  if (r.path == ASCENT_PATH_DENSE)
+    rc = dense_probe(bp.d, (long)batch, K, (int)o->scheme, o->terminal == 2 ? 2 : 0, ws, bit.d, bmu.d, bdw.d, true, bst.d, bin.d, nullptr,
+                     0, g_err, sizeof g_err, r.pcr ? 1 : 0, (int)o->move_penalty);
+  else if (r.path == ASCENT_PATH_PERSIST)
+    rc = persist_probe(bp.d, (long)batch, (int)o->scheme, (int)o->formulation, (int)o->move_penalty, o->terminal == 2 ? 2 : 0, r.wide, K, ws, bit.d, bmu.d, bdw.d,
+                       bst.d, bin.d, 0, g_err, sizeof g_err);
+  else if (r.path == ASCENT_PATH_FUSED)
+    rc = fused_probe(bp.d, (long)batch, K, ws, bit.d, bmu.d, bdw.d, bst.d, bin.d, 0, g_err, sizeof g_err);
+  else
+    rc = pipeline_probe(bp.d, (long)batch, K, (int)o->scheme, (int)o->formulation, ws, bit.d, bmu.d, bdw.d,
+                        r.path == ASCENT_PATH_SPLIT_WIDE, true, bst.d, bin.d, nullptr, nullptr, nullptr, 0, g_err, sizeof g_err);
+  if (rc) return rc;
   HIPCHK(hipMemcpy(step, bst.d, rows * batch * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(inertia_out, bin.d, batch * sizeof(int), hipMemcpyDeviceToHost));
   for (int64_t q = 0; q < batch; q++) inertia_out[q] = inertia_out[q] != 0;     // (the dense path reports a status code)
@@ -1457,7 +646,7 @@ int ascent_dense_records(const ascent_params *p, int64_t batch, const ascent_opt
   if (rc) return rc;
   if (o->move_penalty) { snprintf(g_err, sizeof g_err, "the parity surfaces take the unpenalised NLP only (move_penalty = 1 is an option of ascent_solve_batch)"); return ASCENT_E_ARG; }
   if (!iterate || !records) { snprintf(g_err, sizeof g_err, "null pointer"); return ASCENT_E_ARG; }
-  if (o->formulation != 0) { snprintf(g_err, sizeof g_err, "the dense-block path has formulation 0 only"); return ASCENT_E_ARG; }
+  if (const char *why = unsupported(ASCENT_PATH_DENSE, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   { const int rc0 = claim_slot0(device_id); if (rc0) return rc0; }
@@ -1487,9 +676,7 @@ int ascent_coast_batch(const ascent_params *p, int64_t batch, const double *fina
                        int ptr_is_device) {
   if (!p || batch <= 0 || !final_state || !coast_traj || !coast_tf || !apsides) { snprintf(g_err, sizeof g_err, "null pointer or batch <= 0"); return ASCENT_E_ARG; }
   if (coast_nodes < 1 || coast_nodes > 65535) { snprintf(g_err, sizeof g_err, "coast_nodes out of range (1 .. 65535)"); return ASCENT_E_ARG; }
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { snprintf(g_err, sizeof g_err, "no HIP device available"); return ASCENT_E_NODEVICE; }
-  if (device_id < 0 || device_id >= n || device_id >= MAX_DEV) { snprintf(g_err, sizeof g_err, "device %d of %d", device_id, n); return ASCENT_E_NODEVICE; }
+  if (const int rc0 = check_device(device_id)) return rc0;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   hipStream_t stream = (hipStream_t)stream_;
@@ -1527,9 +714,7 @@ int ascent_kkt_solve(int64_t batch, int32_t n, int32_t bs, int32_t nb, const dou
     return ASCENT_E_ARG;
   }
   if (!diag || !lower || !upper || !rhs || !sol || (nb && (!border || !border_diag))) { snprintf(g_err, sizeof g_err, "null pointer"); return ASCENT_E_ARG; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { snprintf(g_err, sizeof g_err, "no HIP device available"); return ASCENT_E_NODEVICE; }
-  if (device_id < 0 || device_id >= ndev || device_id >= MAX_DEV) { snprintf(g_err, sizeof g_err, "device %d of %d", device_id, ndev); return ASCENT_E_NODEVICE; }
+  if (const int rc0 = check_device(device_id)) return rc0;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   { const int rc0 = claim_slot0(device_id); if (rc0) return rc0; }

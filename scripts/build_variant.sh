@@ -12,7 +12,7 @@ for s in ${SRCS:-ascent_persist ascent_hs}; do
 done
 wait
 objs=""
-for s in ascent_solver ascent_pipeline ascent_dense ascent_blocktri ascent_persist ascent_hs; do
+for s in ascent_solver ascent_fused ascent_pipeline ascent_dense ascent_blocktri ascent_persist ascent_hs; do
   if [ -f dbglib/_obj_$name/$s.o ]; then objs="$objs dbglib/_obj_$name/$s.o"; else objs="$objs $C/_obj/$s.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o dbglib/libascent_$name.so $objs

@@ -133,6 +133,31 @@ def test_default_path_dispatch_rule(monkeypatch):
     assert A.default_path(4096, 201, scheme=2) == "dense"                  # (... nor Hermite-Simpson)
 
 
+def test_default_path_matches_route_table(lib, monkeypatch):
+    """ascent_default_path over batch sizes on both sides of every threshold it shows (6 NLPs, 400 intervals, 4096, 24576), all
+    option combinations and the routing overrides, against tests/golden/route_table.json (scripts/make_route_table.py, written by
+    the library before its routing moved into one function)."""
+    import itertools
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "route_table.json")) as f:
+        table = json.load(f)
+    f = lib.ascent_default_path
+    routing = sorted({k for env in table["env"] for k in env})
+    got = []
+    for env in table["env"]:
+        for k in routing:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        for b, nn, sc, fo, mp, te, sp in itertools.product(*table["axes"].values()):
+            o = _lib.AscentOptsC(n_nodes=nn, scheme=sc, max_iter=300, warm_start=0, tol=1e-9, mu_init=0.0, formulation=fo,
+                                 coarse_nodes=0, terminal=te, solver_path=sp, move_penalty=mp, reserved=0)
+            got.append(f(b, C.byref(o)))
+    assert len(got) == len(table["paths"])
+    bad = [i for i, (g, w) in enumerate(zip(got, table["paths"])) if g != w]
+    assert not bad, f"{len(bad)} routes differ from the table, first at entry {bad[0]}: {got[bad[0]]} instead of {table['paths'][bad[0]]}"
+
+
 def test_persistent_workspace_regions_fit_the_allocation(lib):
     """The two workspace regions of the persistent kernel's nested iteration (levels alternate between them) lie inside the
     allocation for every batch and grid combination -- the second region starts at a 256-byte boundary behind the first, and
