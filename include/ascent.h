@@ -227,6 +227,23 @@ int ascent_coast_batch(const ascent_params *p, int64_t batch, const double *fina
                        double *coast_traj, double *coast_tf, double *apsides, int device_id,
                        void *hip_stream_or_null, int ptr_is_device);
 
+/* Post-optimal sensitivity (envelope theorem) of the optimal objective to every ascent_params field, from a
+ * solution blob written by ascent_solve_batch with the same options.  grad_out [16][batch]: row i is d J* / d(field i of
+ * ascent_params, in declaration order), in units of the scaled objective per SI unit of that field, where J is the
+ * objective of the scaled NLP as solved: tf (= final time / T_scale), plus dcost * sum_k |u_k - u_{k-1}| with
+ * move_penalty = 1 (formulation 1: weight dcost * angle_ub / 2, u_{-1} = -1).  The value is the partial derivative of
+ * the Lagrangian at the blob,  dJ/dp + lambda' dc/dp + nu' d(terminal)/dp + zL' d lb/dp - zU' d ub/dp  (defects of the
+ * scheme, formulation 1's angle row, the terminal conditions of o->terminal, the angle_ub and tf bounds, and the penalty
+ * sum taken from the blob's controls): one read of the blob, no KKT solve.  It is the derivative of the optimum only at
+ * a converged solution: for problems whose status was not ASCENT_CONVERGED the rows are defined (computed at whatever
+ * the blob holds) but meaningless.  d(final time)/dp in seconds = T_scale * row, plus tf for the T_scale row.
+ * Options: refuses (ASCENT_E_ARG) exactly what ascent_solve_batch refuses for these options and this batch; the fields
+ * that only steer the iteration (max_iter, tol, mu_init, warm_start) are not read.  Host or device pointers
+ * (ptr_is_device); with device pointers and a stream the call only enqueues one kernel. */
+int ascent_param_sensitivity(const ascent_params *p, int64_t batch, const ascent_opts *o,
+                             const double *sol_blob, double *grad_out,
+                             int device_id, void *hip_stream_or_null, int ptr_is_device);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

@@ -142,6 +142,34 @@ ASC_DEV void accel(const Der &d, double x, double y, double a, double m, double 
   }
 }
 
+// Derivatives of the scaled accelerations with respect to the Der constants they read (post-optimal sensitivity,
+// ascent_sens.hip), order ACC_RHO0 .. ACC_MS: rho0 enters through eta = y + rho0 (d/d rho0 = d/dy), gam through the gravity
+// term, thr / M0 / ms through the thrust th(m) = thr / (M0 - ms*m).
+constexpr int ACC_RHO0 = 0, ACC_GAM = 1, ACC_THR = 2, ACC_M0 = 3, ACC_MS = 4, ACC_NDER = 5;
+ASC_DEV void accel_dder(const Der &d, double x, double y, double a, double m, double *dax, double *day) {
+  const double xi = x, et = y + d.rho0;
+  const double r2 = xi * xi + et * et;
+  const double ir = rsqrt(r2);
+  const double ex = xi * ir, ey = et * ir;
+  double s, c;
+  sincos_bounded(3.0 * a, s, c);
+  const double dx = ex * c - ey * s, dy = ey * c + ex * s;
+  const double imp = rcp(d.M0 - d.ms * m);
+  const double th = d.thr * imp;
+  const double ir3 = ir * ir * ir, g3 = d.gam * ir3;
+  const double fy = ex * ir, g3e = 3.0 * g3 * ex * ey;
+  dax[ACC_RHO0] = -th * dy * fy + g3e;
+  day[ACC_RHO0] = th * dx * fy - g3 * (1.0 - 3.0 * ey * ey);
+  dax[ACC_GAM] = -ir3 * xi;
+  day[ACC_GAM] = -ir3 * et;
+  dax[ACC_THR] = imp * dx;
+  day[ACC_THR] = imp * dy;
+  dax[ACC_M0] = -th * imp * dx;
+  day[ACC_M0] = -th * imp * dy;
+  dax[ACC_MS] = th * imp * m * dx;
+  day[ACC_MS] = th * imp * m * dy;
+}
+
 // Inertia correction (Waechter & Biegler 2006, Algorithm IC, with retuned constants): the primal regularisation
 // delta_w tried after a factorisation with the wrong inertia.  First correction of a solve 1e-2, later ones a
 // third of the last successful value; x10 while the inertia stays wrong.  (IPOPT's 1e-4 / x100-then-x8 needs

@@ -9,6 +9,7 @@
 //   dense blocks d_* / pc_*         ascent_dense.hpp (ascent_dense.hip, ascent_blocktri.hip)
 //   split pipeline q_*              ascent_pipeline.hpp (ascent_pipeline.hip)
 //   fused k_solve                   ascent_fused.hpp (ascent_fused.hip)
+// and the post-optimal sensitivity s_sens, ascent_sens.hpp (ascent_sens.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -26,6 +27,7 @@
 #include "ascent_blocktri.hpp"
 #include "ascent_persist.hpp"
 #include "ascent_fused.hpp"
+#include "ascent_sens.hpp"
 
 using namespace ascent;
 
@@ -697,6 +699,38 @@ int ascent_coast_batch(const ascent_params *p, int64_t batch, const double *fina
   HIPCHK(hipMemcpyAsync(coast_traj, bc.d, nco * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(coast_tf, bt.d, batch * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(apsides, ba.d, (size_t)2 * batch * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return ASCENT_OK;
+}
+
+int ascent_param_sensitivity(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                             double *grad_out, int device_id, void *stream_, int ptr_is_device) {
+  int rc = check_common(p, batch, o, device_id);
+  if (rc) return rc;
+  if (!sol_blob || !grad_out) { snprintf(g_err, sizeof g_err, "null solution blob or output pointer"); return ASCENT_E_ARG; }
+  // the options ascent_solve_batch refuses for this batch are refused here: the same route, the same check
+  const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
+  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
+  if (o->move_penalty && !ptr_is_device && (rc = check_dcost(p, batch))) return rc;
+  std::lock_guard<std::mutex> lock(g_mu[device_id]);
+  HIPCHK(hipSetDevice(device_id));
+  hipStream_t stream = (hipStream_t)stream_;
+  const int K = o->n_nodes - 1;
+  if (ptr_is_device) {
+    rc = sens_run(p, (long)batch, K, o->scheme, o->formulation, o->terminal, o->move_penalty, sol_blob, grad_out, stream, g_err, sizeof g_err);
+    if (rc) return rc;
+    if (!stream) HIPCHK(hipStreamSynchronize(stream));
+    return ASCENT_OK;
+  }
+  const size_t nb = (21 * (size_t)K + NSC) * batch, ng = (size_t)16 * batch;
+  DevBuf<ascent_params> bp;
+  DevBuf<double> bb, bg;
+  HIPCHK(bp.alloc(batch)); HIPCHK(bb.alloc(nb)); HIPCHK(bg.alloc(ng));
+  HIPCHK(hipMemcpyAsync(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(bb.d, sol_blob, nb * sizeof(double), hipMemcpyHostToDevice, stream));
+  rc = sens_run(bp.d, (long)batch, K, o->scheme, o->formulation, o->terminal, o->move_penalty, bb.d, bg.d, stream, g_err, sizeof g_err);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(grad_out, bg.d, ng * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   return ASCENT_OK;
 }

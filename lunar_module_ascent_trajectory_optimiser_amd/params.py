@@ -66,6 +66,19 @@ def sweep_isp_drymass(n_isp=64, n_dry=64, isp=(300.0, 320.0), dry=(2345.0, 2545.
     return out
 
 
+def isp_drymass_gradient(sens, params) -> tuple[np.ndarray, np.ndarray]:
+    """d t_f / d Isp (s/s) and d t_f / d(dry mass) (s/kg) of rows built as sweep_isp_drymass builds them (mdot = Ft/(Isp g0),
+    M0 = dry + fuel_mass), from the (batch, 16) sensitivity of solve_batch(sensitivity=True), by the chain rule:
+    d mdot / d Isp = -mdot / Isp, d M0 / d dry = 1."""
+    P = np.atleast_2d(np.asarray(params, dtype=np.float64))
+    S = np.atleast_2d(np.asarray(sens, dtype=np.float64))
+    if S.shape != P.shape or P.shape[1] != len(PARAM_FIELDS):
+        raise ValueError("sens and params must both have shape (batch, 16)")
+    mdot, Ft = P[:, PARAM_FIELDS.index("mdot")], P[:, PARAM_FIELDS.index("Ft")]
+    isp = Ft / (mdot * G0)
+    return -S[:, PARAM_FIELDS.index("mdot")] * mdot / isp, S[:, PARAM_FIELDS.index("M0")].copy()
+
+
 def sweep_config4(n_isp=64, n_dry=64, n_apo=8, n_acc=8, apo_km=(70.0, 105.0), acc=(3e-4, 1e-3),
                   base=None) -> np.ndarray:
     """BASELINE.json config 4: config-3 grid x target apoapsis x angular-acceleration cap

@@ -52,6 +52,7 @@ class BatchResult:
     iters: np.ndarray           # (batch,) int32
     blob: np.ndarray | None     # (21K+10, batch) primal-dual solution (warm-start material)
     kernel_ms: float            # device time of the solve kernel
+    sensitivity: np.ndarray | None = None   # (batch, 16) d(T_scale J*)/dp, s per SI unit (solve_batch(sensitivity=True))
 
     @property
     def converged(self) -> np.ndarray:
@@ -110,7 +111,7 @@ class BatchResult:
 def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, guess: np.ndarray | None = None,
                 warm_start: int | None = None, mu_init: float = 0.0, device: int = 0, want_traj: bool = True,
                 want_blob: bool = False, scheme=0, formulation=0, coarse_nodes: int = 0, terminal=0,
-                path: str = "auto", move_penalty: bool = False) -> BatchResult:
+                path: str = "auto", move_penalty: bool = False, sensitivity: bool = False) -> BatchResult:
     """Solve a batch of ascent NLPs on one GPU.  params: AscentParams | list | (batch,16) array.
     guess: (21K+10, batch) blob, with warm_start 1 (primal only) or 2 (primal-dual).
     scheme: 0 / "backward_euler" (the reference's NODES=2), 1 / "trapezoid" or 2 / "hermite_simpson" (both with the
@@ -124,7 +125,10 @@ def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, g
     scheme 2: dense-block path; default off: `dcost` is then ignored).
     formulation: 0 / "current" or 1 / "v1" (the PDF appendix script: the angle is the MV; see include/ascent.h).
     coarse_nodes: nested iteration for cold starts (0 automatic, -1 single grid, > 0 explicit coarse grid);
-    `iters` then counts the iterations of all grid levels."""
+    `iters` then counts the iterations of all grid levels.
+    sensitivity: also set `BatchResult.sensitivity`, (batch, 16) d(T_scale J*)/dp in seconds per SI unit of every parameter
+    field (param_sensitivity at the solution; the T_scale column is J* + T_scale dJ*/dT_scale); rows of problems that did not
+    converge are NaN.  Without the move penalty this is d t_f*/dp; with it, the penalised objective in seconds."""
     L = _lib.load()
     P = pack(params)
     B = P.shape[0]
@@ -137,14 +141,65 @@ def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, g
             warm_start = 1
     warm_start = warm_start or 0
     traj = np.empty((10, nt, B)) if want_traj else None
-    blob = np.empty((rows, B)) if want_blob else None
+    blob = np.empty((rows, B)) if (want_blob or sensitivity) else None
     tf = np.empty(B)
     status = np.empty(B, dtype=np.int32)
     iters = np.empty(B, dtype=np.int32)
     o = _opts(nt, max_iter, tol, warm_start, mu_init, scheme, formulation, coarse_nodes, terminal, path, move_penalty)
     _lib.check(L.ascent_solve_batch(_ptr(P), B, C.byref(o), _ptr(guess), _ptr(traj), _ptr(tf), _ptr(status),
                                     _ptr(iters), _ptr(blob), device, None, 0))
-    return BatchResult(P, nt, traj, tf, status, iters, blob, L.ascent_last_kernel_ms(device))
+    kms = L.ascent_last_kernel_ms(device)
+    sens = None
+    if sensitivity:
+        g = param_sensitivity(P, blob, nt, scheme=scheme, formulation=formulation, terminal=terminal,
+                              move_penalty=move_penalty, device=device)
+        sens = _seconds(P, blob, nt, g, formulation, move_penalty)
+        sens[status != 0] = np.nan
+    return BatchResult(P, nt, traj, tf, status, iters, blob if want_blob else None, kms, sens)
+
+
+def _penalty_weight(P, formulation):
+    """weight of sum_k |u_k - u_{k-1}| in the scaled objective and u_{-1} (include/ascent.h: ascent_opts.move_penalty)"""
+    form = FORMULATIONS.get(formulation, formulation)
+    return (P[:, 15] * P[:, 12] * 0.5, -1.0) if form == 1 else (P[:, 15], 0.0)
+
+
+def objective(params, sol_blob, nt: int, formulation=0, move_penalty: bool = False) -> np.ndarray:
+    """J* of every problem at its solution blob (rows, batch): the scaled objective as solved -- tf, plus the move penalty
+    dcost * sum_k |u_k - u_{k-1}| taken from the blob's controls when move_penalty is on."""
+    P = pack(params)
+    K = nt - 1
+    J = np.array(sol_blob[21 * K], dtype=np.float64)
+    if move_penalty:
+        w, u0 = _penalty_weight(P, formulation)
+        U = np.vstack([np.full((1, P.shape[0]), u0), sol_blob[7 * K:8 * K]])
+        J = J + w * np.abs(np.diff(U, axis=0)).sum(axis=0)
+    return J
+
+
+def _seconds(P, blob, nt, g, formulation, move_penalty):
+    """(batch, 16) d(T J*)/dp from dJ*/dp: T g, and J* + T g for the T_scale column."""
+    sens = P[:, 11:12] * g
+    sens[:, 11] += objective(P, blob, nt, formulation, move_penalty)
+    return sens
+
+
+def param_sensitivity(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0,
+                      move_penalty: bool = False, device: int = 0) -> np.ndarray:
+    """Post-optimal sensitivity (envelope theorem, include/ascent.h: ascent_param_sensitivity): (batch, 16) dJ*/dp of the
+    scaled objective J* to every ascent_params field (PARAM_FIELDS order, per SI unit), at the solution blob (21K+10, batch)
+    that solve_batch returned with the same options.  One read of the blob on the device, no extra solve.  Rows of problems
+    that did not converge are computed at whatever the blob holds and are meaningless."""
+    P = pack(params)
+    B = P.shape[0]
+    blob = np.ascontiguousarray(sol_blob, dtype=np.float64)
+    if blob.shape != (blob_rows(nt), B):
+        raise ValueError(f"sol_blob must have shape {(blob_rows(nt), B)}")
+    L = _lib.load()
+    g = np.empty((16, B))
+    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
+    _lib.check(L.ascent_param_sensitivity(_ptr(P), B, C.byref(o), _ptr(blob), _ptr(g), device, None, 0))
+    return np.ascontiguousarray(g.T)
 
 
 def eval_nodes(params, iterate: np.ndarray, nt: int = 200, device: int = 0, path="auto", scheme=0, formulation=0):
@@ -243,12 +298,15 @@ def kkt_solve(diag, lower, upper, rhs, border=None, border_diag=None, algo="pcr"
 def solve_batch_torch(params_t, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, guess_t=None,
                       warm_start: int = 0, mu_init: float = 0.0, want_traj: bool = True, want_blob: bool = False,
                       out: dict | None = None, sync: bool = False, coarse_nodes: int = 0, scheme=0,
-                      formulation=0, move_penalty: bool = False, terminal=0, path: str = "auto") -> dict:
+                      formulation=0, move_penalty: bool = False, terminal=0, path: str = "auto",
+                      sensitivity: bool = False) -> dict:
     """Device-resident variant: `params_t` is a torch float64 CUDA tensor (batch,16); all outputs are
     torch CUDA tensors (allocated here unless passed in `out`).  Enqueues on torch's current stream
     and returns without waiting unless sync=True.  torch is only the owner of device memory/streams.
     Options as solve_batch (scheme, formulation, terminal, path, move_penalty: the weights params_t[:, 15] must be
-    positive then -- checked here on the device, the library cannot look into device memory from the host)."""
+    positive then -- checked here on the device, the library cannot look into device memory from the host).
+    sensitivity: also out["sensitivity"], (batch, 16) d(T_scale J*)/dp as solve_batch(sensitivity=True) computes it (NaN rows
+    for problems that did not converge), enqueued on the same stream right after the solve: no host read."""
     import torch
     L = _lib.load()
     _lib.require_single_hip_runtime()
@@ -279,6 +337,9 @@ def solve_batch_torch(params_t, nt: int = 200, tol: float = 1e-9, max_iter: int 
     iters = buf("iters", (B,), torch.int32)
     traj = buf("traj", (10, nt, B), torch.float64) if want_traj else None
     blob = buf("blob", (rows, B), torch.float64) if want_blob else None
+    if sensitivity and blob is None:       # the solve's blob, needed by the sensitivity kernel only
+        blob = torch.empty((rows, B), dtype=torch.float64, device=dev)
+    sens = buf("sensitivity", (B, 16), torch.float64) if sensitivity else None
     o = _opts(nt, max_iter, tol, warm_start, mu_init, scheme, formulation, coarse_nodes, terminal, path, move_penalty)
     stream = torch.cuda.current_stream(dev).cuda_stream
     _lib.check(L.ascent_solve_batch(params_t.data_ptr(), B, C.byref(o),
@@ -286,9 +347,70 @@ def solve_batch_torch(params_t, nt: int = 200, tol: float = 1e-9, max_iter: int 
                                     traj.data_ptr() if traj is not None else None, tf.data_ptr(), status.data_ptr(),
                                     iters.data_ptr(), blob.data_ptr() if blob is not None else None,
                                     dev.index or 0, C.c_void_p(stream), 1))
+    if sensitivity:
+        g = torch.empty((16, B), dtype=torch.float64, device=dev)
+        _lib.check(L.ascent_param_sensitivity(params_t.data_ptr(), B, C.byref(o), blob.data_ptr(), g.data_ptr(),
+                                              dev.index or 0, C.c_void_p(stream), 1))
+        K = nt - 1
+        J = blob[21 * K].clone()
+        if move_penalty:
+            form = FORMULATIONS.get(formulation, formulation)
+            w = params_t[:, 15] * params_t[:, 12] * 0.5 if form == 1 else params_t[:, 15]
+            U = torch.cat([torch.full((1, B), -1.0 if form == 1 else 0.0, dtype=torch.float64, device=dev), blob[7 * K:8 * K]])
+            J = J + w * (U[1:] - U[:-1]).abs().sum(0)
+        s_ = g.t() * params_t[:, 11:12]
+        s_[:, 11] += J
+        sens.copy_(torch.where((status == 0)[:, None], s_, torch.full_like(s_, float("nan"))))
     if sync:
         torch.cuda.synchronize(dev)
     return out
+
+
+class _FinalTime:
+    """torch.autograd.Function of final_time (built on first use: torch is imported lazily)."""
+    fn = None
+
+    @classmethod
+    def get(cls):
+        if cls.fn is None:
+            import torch
+
+            class FinalTime(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, params_t, kw):
+                    out = solve_batch_torch(params_t.detach().contiguous(), sensitivity=True, want_traj=False,
+                                            want_blob=kw.get("move_penalty", False), **kw)
+                    T = params_t[:, 11].detach()
+                    if kw.get("move_penalty", False):
+                        nt = kw.get("nt", 200)
+                        K = nt - 1
+                        form = FORMULATIONS.get(kw.get("formulation", 0), kw.get("formulation", 0))
+                        w = params_t[:, 15] * params_t[:, 12] * 0.5 if form == 1 else params_t[:, 15]
+                        B = params_t.shape[0]
+                        U = torch.cat([torch.full((1, B), -1.0 if form == 1 else 0.0, dtype=torch.float64,
+                                                  device=params_t.device), out["blob"][7 * K:8 * K]])
+                        y = T * (out["tf"] + w.detach() * (U[1:] - U[:-1]).abs().sum(0))
+                    else:
+                        y = T * out["tf"]
+                    y = torch.where(out["status"] == 0, y, torch.full_like(y, float("nan")))
+                    ctx.save_for_backward(out["sensitivity"])
+                    return y
+
+                @staticmethod
+                def backward(ctx, grad_out):
+                    (sens,) = ctx.saved_tensors
+                    return grad_out[:, None] * sens, None
+
+            cls.fn = FinalTime
+        return cls.fn
+
+
+def final_time(params_t, **solve_kw):
+    """Differentiable optimal final time: (batch,) t_f* in seconds of the NLPs of `params_t` (a float64 CUDA tensor
+    (batch, 16), solved by solve_batch_torch with `solve_kw`); backward gives grad_out * d t_f*/dp from the post-optimal
+    sensitivity (no extra solve).  With move_penalty=True the value is the penalised objective T_scale J* in seconds and
+    the gradient is its own.  NLPs that did not converge give NaN values and NaN gradients."""
+    return _FinalTime.get().apply(params_t, dict(solve_kw))
 
 
 def default_path(batch: int, nt: int = 200, scheme=0, formulation=0, move_penalty: bool = False, terminal=0) -> str:

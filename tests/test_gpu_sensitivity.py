@@ -1,0 +1,251 @@
+"""Post-optimal sensitivity dJ*/dp (ascent_param_sensitivity) on the GPU: the kernel against the CPU reference of dL/dp at
+the same blob, against finite differences of GPU solves, over a whole sweep, and the surfaces built on it."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import sens_reference as sr
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = sr.FIELDS
+DCOST = 1e-4
+
+
+def _lib():
+    from lunar_module_ascent_trajectory_optimiser_amd import _lib
+    return _lib
+
+
+def _points(n=3):
+    """the nominal point and sweep corners (config 3), tf_ub = 1.2"""
+    from lunar_module_ascent_trajectory_optimiser_amd import AscentParams, sweep_isp_drymass
+    nom = AscentParams(tf_ub=1.2).as_row()
+    sw = sweep_isp_drymass()
+    P = np.vstack([nom, sw[0], sw[4095], sw[63], sw[4032]])[:n].copy()
+    P[:, 15] = DCOST
+    return P
+
+
+def _combos():
+    out = []
+    for scheme in (0, 1, 2):
+        for form in ((0, 1) if scheme == 0 else (0,)):
+            for term in ((0, 1) if form == 1 else (0, 1, 2)):
+                for mp in (0, 1):
+                    out.append((scheme, form, term, mp))
+    return out
+
+
+def _check_against_reference(P, nt, scheme, form, term, mp):
+    from lunar_module_ascent_trajectory_optimiser_amd import solve_batch, param_sensitivity
+    r = solve_batch(P, nt, want_blob=True, scheme=scheme, formulation=form, terminal=term, move_penalty=bool(mp))
+    g = param_sensitivity(P, r.blob, nt, scheme=scheme, formulation=form, terminal=term, move_penalty=bool(mp))
+    assert g.shape == (P.shape[0], 16) and np.isfinite(g).all()
+    for j in range(P.shape[0]):
+        gr, scale = sr.reference_gradient(P[j], nt, r.blob[:, j], scheme, form, term, bool(mp))
+        err = np.abs(P[j] * (g[j] - gr))
+        bound = 1e-8 * np.abs(P[j]) * scale + 1e-300
+        bad = [(FIELDS[i], g[j, i], gr[i], err[i], bound[i]) for i in range(16) if err[i] > bound[i]]
+        assert not bad, f"problem {j} ({scheme}, {form}, {term}, {mp}, nt={nt}): {bad}"
+
+
+@pytest.mark.parametrize("scheme,form,term,mp", _combos())
+def test_kernel_matches_reference_nt50(scheme, form, term, mp):
+    _check_against_reference(_points(3), 50, scheme, form, term, mp)
+
+
+@pytest.mark.parametrize("scheme", [0, 1, 2])
+def test_kernel_matches_reference_nt200(scheme):
+    _check_against_reference(_points(2), 200, scheme, 0, 0, 0)
+
+
+def test_kernel_matches_reference_hermite_simpson_nt2000():
+    _check_against_reference(_points(1), 2000, 2, 0, 0, 0)
+
+
+@pytest.mark.parametrize("scheme,term,mp", [(s, t, m) for s in (0, 2) for t in (0, 2) for m in (0, 1)])
+def test_against_finite_differences_of_gpu_solves(scheme, term, mp):
+    """Elasticities p_i d(T J*)/dp_i against central differences of warm-started GPU solves (relative step 1e-4, tol 1e-10):
+    solve noise ~1e-10 (scaled) / 1e-4 * T ~ 5e-4 s, truncation ~1e-8 relative -> 2e-3 s + 1e-5 |elasticity|."""
+    from lunar_module_ascent_trajectory_optimiser_amd import solve_batch
+    nt, delta = 100, 1e-4
+    P = _points(5)
+    kw = dict(scheme=scheme, terminal=term, move_penalty=bool(mp))
+    base = solve_batch(P, nt, tol=1e-10, want_blob=True, sensitivity=True, **kw)
+    assert (base.status == 0).all()
+    idx = [i for i in range(16) if P[0, i] != 0.0 and FIELDS[i] not in ("tf_lb",)]
+    rows, guess = [], []
+    for j in range(P.shape[0]):
+        for i in idx:
+            for s in (1.0, -1.0):
+                q = P[j].copy()
+                q[i] *= 1.0 + s * delta
+                rows.append(q)
+                guess.append(base.blob[:, j])
+    Q = np.array(rows)
+    pert = solve_batch(Q, nt, tol=1e-10, guess=np.ascontiguousarray(np.array(guess).T), warm_start=2, want_blob=True, **kw)
+    # a perturbed solve that stops short of tol 1e-10 (a line-search failure of one warm start in 165 was seen on the
+    # dense-block path with the penalty) has no finite difference; such pairs are left out, at most 5 % of them
+    assert (pert.status == 0).mean() >= 0.98
+    TJ = Q[:, 11] * sr_objective(Q, pert.blob, nt, mp)
+    n = checked = 0
+    for j in range(P.shape[0]):
+        for i in idx:
+            if pert.status[n] == 0 and pert.status[n + 1] == 0:
+                fd = (TJ[n] - TJ[n + 1]) / (2.0 * delta)
+                el = P[j, i] * base.sensitivity[j, i]
+                assert abs(el - fd) <= 2e-3 + 1e-5 * abs(el), (j, FIELDS[i], el, fd)
+                checked += 1
+            n += 2
+    assert checked >= 0.95 * len(idx) * P.shape[0]
+
+
+def sr_objective(P, blob, nt, mp, form=0):
+    return np.array([sr.objective(P[j], nt, blob[:, j], form, bool(mp)) for j in range(P.shape[0])])
+
+
+@pytest.fixture(scope="module", params=[0, 1], ids=["plain", "penalty"])
+def sweep(request):
+    from lunar_module_ascent_trajectory_optimiser_amd import solve_batch, sweep_isp_drymass
+    P = sweep_isp_drymass()
+    P[:, 15] = DCOST
+    r = solve_batch(P, 200, tol=1e-10, want_blob=True, sensitivity=True, move_penalty=bool(request.param))
+    return request.param, P, r
+
+
+def _gap_bound(P, blob, nt, mp):
+    """seconds: T_scale times an upper estimate of how far a solve's objective sits above the optimum of its NLP, the
+    complementarity gap left at the stopping barrier parameter (number of bound pairs x largest pair product; with the
+    penalty two more pairs per step, which the blob does not carry)"""
+    K = nt - 1
+    z = blob[:7 * K].reshape(K, 7, -1)
+    u = blob[7 * K:8 * K]
+    zb = blob[15 * K:21 * K].reshape(K, 6, -1)
+    sc = blob[21 * K:]
+    aub, tlb, tub = P[:, 12], P[:, 13], P[:, 14]
+    prods = np.concatenate([zb[:, 0] * z[:, 4], zb[:, 1] * (aub - z[:, 4]), zb[:, 2] * z[:, 6], zb[:, 3] * (1 - z[:, 6]),
+                            zb[:, 4] * (u + 1), zb[:, 5] * (1 - u),
+                            (sc[1] * (sc[0] - tlb))[None], (sc[2] * (tub - sc[0]))[None], (sc[5] * sc[3])[None],
+                            (sc[6] * sc[4])[None]])
+    npairs = prods.shape[0] + (2 * K if mp else 0)
+    return P[:, 11] * npairs * np.abs(prods).max(axis=0)
+
+
+def test_sweep_neighbours_integrate_the_gradient(sweep):
+    """t_f (T J* with the penalty) of neighbouring grid points differs by the trapezoid integral of the gradient along the
+    axis.  Trapezoid error ~ step^3/12 |t'''| < 1e-7 s here.  Each solve's objective sits above its NLP's optimum by up to
+    the complementarity gap left at the stopping barrier parameter (at tol 1e-9: ~1200 pairs x 1e-10 x 470 s ~ 5e-5 s, and
+    neighbours may stop at different barrier parameters), so the sweep is solved at tol 1e-10 and each pair is allowed
+    1e-5 s plus the two gaps (_gap_bound)."""
+    from lunar_module_ascent_trajectory_optimiser_amd import isp_drymass_gradient
+    mp, P, r = sweep
+    TJ = (P[:, 11] * sr_objective(P, r.blob, 200, mp)).reshape(64, 64)
+    gi, gd = isp_drymass_gradient(r.sensitivity, P)
+    gi, gd = gi.reshape(64, 64), gd.reshape(64, 64)
+    g0 = 9.80665
+    isp = (P[:, 3] / (P[:, 5] * g0)).reshape(64, 64)
+    dry = (P[:, 4] - P[:, 6]).reshape(64, 64)
+    e1 = np.abs(TJ[1:] - TJ[:-1] - 0.5 * (isp[1:] - isp[:-1]) * (gi[1:] + gi[:-1]))
+    e2 = np.abs(TJ[:, 1:] - TJ[:, :-1] - 0.5 * (dry[:, 1:] - dry[:, :-1]) * (gd[:, 1:] + gd[:, :-1]))
+    ok1, ok2 = np.isfinite(e1), np.isfinite(e2)
+    assert ok1.mean() > 0.95 and ok2.mean() > 0.95
+    gap = _gap_bound(P, r.blob, 200, mp).reshape(64, 64)
+    b1 = 1e-5 + gap[1:] + gap[:-1]
+    b2 = 1e-5 + gap[:, 1:] + gap[:, :-1]
+    # Measured: ~95 % of the pairs agree to < 1e-6 s; about 4.5 % of them (along one axis or the other, depending on the
+    # run) differ by 1e-5 .. 5e-5 s at tol 1e-9 and 1e-10 alike, so not solve noise -- not yet explained (a change of the
+    # discrete active set between neighbours is the suspect).  Checked: the bulk within the derived bound, every pair
+    # within 1e-4 s (2e-7 of t_f).
+    for e, b, ok in ((e1, b1, ok1), (e2, b2, ok2)):
+        assert np.mean(e[ok] <= b[ok]) >= 0.9, (e[ok].max(), (e[ok] > b[ok]).sum())
+        assert e[ok].max() <= 1e-4, e[ok].max()
+
+
+def test_time_scale_identity_and_exact_identities(sweep):
+    """Without the penalty and with the tf bounds inactive, T_scale only rescales tf: d(T J*)/dT = J* + T dJ*/dT = 0.
+    And the identities the parameters' homogeneity implies, to rounding, on the kernel's raw output."""
+    from lunar_module_ascent_trajectory_optimiser_amd import param_sensitivity
+    mp, P, r = sweep
+    ok = r.status == 0
+    assert ok.mean() > 0.95
+    g = param_sensitivity(P, r.blob, 200, move_penalty=bool(mp))
+    if not mp:
+        J = r.blob[21 * 199]
+        assert np.all(np.abs(r.sensitivity[ok, 11]) <= 1e-7 * P[ok, 11] * J[ok])
+    F = {f: i for i, f in enumerate(FIELDS)}
+    t1 = [P[:, F["Ft"]] * g[:, F["Ft"]], P[:, F["M0"]] * g[:, F["M0"]], P[:, F["mass_scalar"]] * g[:, F["mass_scalar"]]]
+    assert np.all(np.abs(sum(t1)) <= 1e-11 * sum(np.abs(t) for t in t1))
+    t2 = [P[:, F["mdot"]] * g[:, F["mdot"]], P[:, F["fuel_mass"]] * g[:, F["fuel_mass"]]]
+    assert np.all(np.abs(sum(t2)) <= 1e-13 * sum(np.abs(t) for t in t2))
+    a, b = P[:, F["G"]] * g[:, F["G"]], P[:, F["M"]] * g[:, F["M"]]
+    assert np.all(np.abs(a - b) <= 1e-13 * np.abs(a))
+
+
+def test_device_pointer_path_is_bit_identical_to_host_path():
+    import torch
+    from lunar_module_ascent_trajectory_optimiser_amd import solve_batch_torch, param_sensitivity, solve_batch
+    from lunar_module_ascent_trajectory_optimiser_amd.solver import _opts
+    P = _points(5)
+    r = solve_batch(P, 50, want_blob=True, sensitivity=True)
+    g_host = param_sensitivity(P, r.blob, 50)
+    L, lib = _lib().load(), _lib()
+    pt = torch.from_numpy(P).cuda()
+    bt = torch.from_numpy(np.ascontiguousarray(r.blob)).cuda()
+    gt = torch.empty((16, P.shape[0]), dtype=torch.float64, device="cuda")
+    o = _opts(50, 0, 1.0, 0, 0.0)
+    stream = torch.cuda.current_stream().cuda_stream
+    lib.check(L.ascent_param_sensitivity(pt.data_ptr(), P.shape[0], C.byref(o), bt.data_ptr(), gt.data_ptr(), 0,
+                                         C.c_void_p(stream), 1))
+    torch.cuda.synchronize()
+    assert np.array_equal(gt.cpu().numpy().T, g_host)
+    out = solve_batch_torch(pt, 50, want_blob=True, sensitivity=True, sync=True)
+    g_dev = param_sensitivity(P, out["blob"].cpu().numpy(), 50)
+    s_host = P[:, 11:12] * g_dev
+    s_host[:, 11] += out["blob"][21 * 49].cpu().numpy()
+    assert np.array_equal(out["sensitivity"].cpu().numpy(), s_host)
+
+
+def test_unconverged_rows_are_nan():
+    from lunar_module_ascent_trajectory_optimiser_amd import solve_batch
+    r = solve_batch(_points(3), 50, max_iter=2, coarse_nodes=-1, sensitivity=True)
+    assert (r.status != 0).all()
+    assert np.isnan(r.sensitivity).all()
+
+
+def test_argument_errors_return_e_arg():
+    from lunar_module_ascent_trajectory_optimiser_amd.solver import _opts
+    L = _lib().load()
+    P = _points(2)
+    blob = np.zeros((21 * 49 + 10, 2))
+    g = np.zeros((16, 2))
+    pp, bp, gp = (a.ctypes.data_as(C.c_void_p) for a in (P, blob, g))
+    ok = _opts(50, 0, 1.0, 0, 0.0)
+    assert L.ascent_param_sensitivity(pp, 2, C.byref(ok), bp, gp, 0, None, 0) == 0
+    assert L.ascent_param_sensitivity(pp, 2, C.byref(ok), None, gp, 0, None, 0) == -1
+    assert L.ascent_param_sensitivity(pp, 2, C.byref(ok), bp, None, 0, None, 0) == -1
+    assert L.ascent_param_sensitivity(None, 2, C.byref(ok), bp, gp, 0, None, 0) == -1
+    assert L.ascent_param_sensitivity(pp, 0, C.byref(ok), bp, gp, 0, None, 0) == -1
+    for bad in (_opts(2, 0, 1.0, 0, 0.0), _opts(50, 0, 1.0, 0, 0.0, scheme=2, formulation=1),
+                _opts(50, 0, 1.0, 0, 0.0, scheme=1, formulation=1), _opts(50, 0, 1.0, 0, 0.0, terminal=2, formulation=1),
+                _opts(50, 0, 1.0, 0, 0.0, scheme=3)):
+        assert L.ascent_param_sensitivity(pp, 2, C.byref(bad), bp, gp, 0, None, 0) == -1
+        assert L.ascent_strerror(-1)
+    P0 = P.copy()
+    P0[:, 15] = 0.0
+    mp = _opts(50, 0, 1.0, 0, 0.0, move_penalty=True)
+    assert L.ascent_param_sensitivity(P0.ctypes.data_as(C.c_void_p), 2, C.byref(mp), bp, gp, 0, None, 0) == -1
+
+
+def test_autograd_wrapper_gradient():
+    import torch
+    from lunar_module_ascent_trajectory_optimiser_amd import final_time, solve_batch
+    P = _points(5)
+    pt = torch.from_numpy(P).cuda().requires_grad_(True)
+    w = torch.linspace(0.5, 2.0, P.shape[0], dtype=torch.float64, device="cuda")
+    y = final_time(pt, nt=50)
+    (w * y).sum().backward()
+    r = solve_batch(P, 50, sensitivity=True)
+    assert np.allclose(y.detach().cpu().numpy(), r.final_time(), rtol=1e-12, atol=0)
+    assert np.allclose(pt.grad.cpu().numpy(), w.cpu().numpy()[:, None] * r.sensitivity, rtol=1e-12, atol=0)
