@@ -4,7 +4,8 @@
 This is this repository's own counterpart of the reference script: the same problem, declared with
 the same modelling calls, solved by libascent on an MI355X instead of GEKKO/APMonitor/IPOPT.  It prints
 the quantities the reference prints (/root/reference/Launch_Optimiser.py:178-194) and writes the same
-three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR]
+three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly]
+--fly also integrates the ODEs under the control just found (RK4 on the device) and prints where that flight ends.
 """
 import argparse
 import os
@@ -89,6 +90,20 @@ def report(m, v, v_ins):
     return tfv * T
 
 
+def fly(m, scheme):
+    """Flight verification of the solved case: the solution's control flown with RK4 on the device (fly_batch)."""
+    from lunar_module_ascent_trajectory_optimiser_amd import fly_batch
+    res = m.result
+    f = fly_batch(res.params, res.flight_blob(), res.nt, scheme=scheme, formulation=m._formulation)
+    print("flown with RK4, %d substeps per step: the control ends %.4g m and %.4g m/s from the NLP's last node"
+          % (f.substeps[0], f.miss_position[0], f.miss_velocity[0]))
+    print("flown burnout orbit (periapsis / apoapsis altitude): %.1f m / %.1f m" % (f.flown_periapsis_alt[0], f.flown_apoapsis_alt[0]))
+    print("the NLP's own burnout orbit:                         %.1f m / %.1f m" % (f.nlp_periapsis_alt[0], f.nlp_apoapsis_alt[0]))
+    print("largest local error of a collocation step: %.4g m, %.4g m/s (position: step %d)"
+          % (f.max_local_position_error[0], f.max_local_velocity_error[0], f.max_local_step[0]))
+    return f
+
+
 def plots(m, v, outdir):
     import matplotlib
     matplotlib.use("Agg")
@@ -122,6 +137,7 @@ if __name__ == "__main__":
     ap.add_argument("--outdir", default=".")
     ap.add_argument("--no-dcost", action="store_true", help="ignore the MV's DCOST = 1e-5 (Launch_Optimiser.py:99; applied as an l1 move penalty by default)")
     ap.add_argument("--scheme", type=int, default=0, help="0 backward Euler (the reference's NODES=2), 1 trapezoid, 2 Hermite-Simpson")
+    ap.add_argument("--fly", action="store_true", help="fly the solution's control with RK4 on the device and print what it reaches")
     a = ap.parse_args()
     model, variables, v_ins = build()
     if a.no_dcost:
@@ -130,5 +146,7 @@ if __name__ == "__main__":
         model.options.ASCENT_SCHEME = a.scheme
     model.solve(disp=True)
     report(model, variables, v_ins)
+    if a.fly:
+        fly(model, a.scheme)
     if not a.no_plots:
         plots(model, variables, a.outdir)

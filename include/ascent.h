@@ -244,6 +244,39 @@ int ascent_param_sensitivity(const ascent_params *p, int64_t batch, const ascent
                              const double *sol_blob, double *grad_out,
                              int device_id, void *hip_stream_or_null, int ptr_is_device);
 
+/* Flight verification: what a solution's control reaches when it is flown.  The solver returns the minimiser of the
+ * discretised problem; this integrates the model's ODEs (Launch_Optimiser.py:114-136, scaled as everywhere here) under the
+ * control of a solution blob written by ascent_solve_batch with the same options, with a fixed-step classical RK4 on the
+ * device, and reports the distance between the flown trajectory and the NLP's.
+ * Model: node 0 is the zero initial state; step k (node k-1 -> k, duration dt = tf * T_scale / K seconds) flies with the
+ * blob's u_k held constant, for every scheme; formulation 1: the angle is held at (angle_ub/2)(u_k + 1) over step k and
+ * angledot stays 0.  move_penalty and terminal do not change the ODEs.
+ * substeps: RK4 steps per collocation step, 1 .. ASCENT_FLIGHT_MAX_SUBSTEPS for every problem, or 0 = automatic: per problem
+ * m = clamp(ceil(dt / 0.5 s), 1, ASCENT_FLIGHT_MAX_SUBSTEPS), m = 1 if dt is not finite (the RK4 error of a whole ascent is
+ * then below 1e-4 m; DESIGN.md has the measurement).
+ * flown_traj_out_or_null [10*n_nodes][batch]: the flown trajectory in the layout and field order of traj_out (accelerations
+ *   evaluated at the flown state; the control row as ascent_solve_batch writes it for this blob).
+ * local_err_out_or_null [7K][batch], row 7(k-1)+f: eta_k = (the NLP's z_{k-1} flown over step k) - z_k, the local
+ *   discretisation error of every collocation step, scaled units; steps are independent of each other.
+ * summary_out [ASCENT_FLIGHT_ROWS][batch], SI units:
+ *   0 position miss |flown - NLP| at the last node (m)        1 velocity miss (m/s)
+ *   2 / 3 periapsis / apoapsis altitude above R0 of the flown burnout orbit (m)    4 / 5 the same for the NLP's last node
+ *         (two-body formulas of ascent_coast_batch; specific energy >= 0 gives apoapsis +inf)
+ *   6 max over steps of the local position error |eta_k(x, y)| (m)      7 of the local velocity error (m/s)
+ *   8 the step k (1-based) where row 6 is attained         9 the m used
+ * Options: refuses (ASCENT_E_ARG) exactly what ascent_solve_batch refuses for these options and this batch; max_iter, tol,
+ * mu_init, warm_start are not read.  For problems whose status was not ASCENT_CONVERGED the rows are defined (computed from
+ * whatever the blob holds, NaN allowed) but meaningless; the work per problem is bounded by 4 * K * ASCENT_FLIGHT_MAX_SUBSTEPS
+ * right-hand sides whatever the blob holds -- a bound, not a small one: a garbage t_f on a grid of tens of thousands of nodes
+ * keeps one lane busy for minutes, so callers with long grids should not pass blobs of unconverged problems as they are (set
+ * their t_f row to 0 or NaN: m = 1).  Host or device pointers (ptr_is_device); with device pointers and a stream the
+ * call only enqueues two kernels (no host read, no synchronisation). */
+#define ASCENT_FLIGHT_ROWS 10
+#define ASCENT_FLIGHT_MAX_SUBSTEPS 4096
+int ascent_fly_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                     int32_t substeps, double *flown_traj_out_or_null, double *local_err_out_or_null,
+                     double *summary_out, int device_id, void *hip_stream_or_null, int ptr_is_device);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

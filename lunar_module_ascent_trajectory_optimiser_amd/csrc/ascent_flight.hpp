@@ -1,0 +1,16 @@
+// Host interface of the flight-verification kernels (ascent_flight.hip), used by the C ABI in ascent_solver.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include "ascent.h"
+
+namespace ascent {
+
+// Fly every NLP's control with RK4 and compare with its solution blob (include/ascent.h: ascent_fly_batch).  Device pointers:
+// dp[batch], dblob [21K+10][batch], dtraj [10(K+1)][batch] or null, dlocal [7K][batch] or null, dsummary
+// [ASCENT_FLIGHT_ROWS][batch].  Options already checked by the caller (formulation 0 / 1, substeps 0 .. ASCENT_FLIGHT_MAX_SUBSTEPS).
+// Only enqueues two kernels on `stream` (f_fly, f_local; they write disjoint rows).  Returns ASCENT_OK / ASCENT_E_HIP.
+int flight_run(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
+               double *dlocal, double *dsummary, hipStream_t stream, char *err, size_t errlen);
+
+}  // namespace ascent

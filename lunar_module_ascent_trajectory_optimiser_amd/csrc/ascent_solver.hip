@@ -9,7 +9,8 @@
 //   dense blocks d_* / pc_*         ascent_dense.hpp (ascent_dense.hip, ascent_blocktri.hip)
 //   split pipeline q_*              ascent_pipeline.hpp (ascent_pipeline.hip)
 //   fused k_solve                   ascent_fused.hpp (ascent_fused.hip)
-// and the post-optimal sensitivity s_sens, ascent_sens.hpp (ascent_sens.hip).
+// the post-optimal sensitivity s_sens, ascent_sens.hpp (ascent_sens.hip), and the flight verification f_fly / f_local,
+// ascent_flight.hpp (ascent_flight.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -28,6 +29,7 @@
 #include "ascent_persist.hpp"
 #include "ascent_fused.hpp"
 #include "ascent_sens.hpp"
+#include "ascent_flight.hpp"
 
 using namespace ascent;
 
@@ -731,6 +733,44 @@ int ascent_param_sensitivity(const ascent_params *p, int64_t batch, const ascent
   rc = sens_run(bp.d, (long)batch, K, o->scheme, o->formulation, o->terminal, o->move_penalty, bb.d, bg.d, stream, g_err, sizeof g_err);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(grad_out, bg.d, ng * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return ASCENT_OK;
+}
+
+int ascent_fly_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                     double *flown_traj, double *local_err, double *summary, int device_id, void *stream_, int ptr_is_device) {
+  int rc = check_common(p, batch, o, device_id);
+  if (rc) return rc;
+  if (!sol_blob || !summary) { snprintf(g_err, sizeof g_err, "null solution blob or summary pointer"); return ASCENT_E_ARG; }
+  if (substeps < 0 || substeps > ASCENT_FLIGHT_MAX_SUBSTEPS) { snprintf(g_err, sizeof g_err, "substeps out of range (0 = automatic, 1 .. %d)", ASCENT_FLIGHT_MAX_SUBSTEPS); return ASCENT_E_ARG; }
+  // the options ascent_solve_batch refuses for this batch are refused here: the same route, the same check
+  const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
+  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
+  if (o->move_penalty && !ptr_is_device && (rc = check_dcost(p, batch))) return rc;
+  std::lock_guard<std::mutex> lock(g_mu[device_id]);
+  HIPCHK(hipSetDevice(device_id));
+  hipStream_t stream = (hipStream_t)stream_;
+  const int K = o->n_nodes - 1;
+  if (ptr_is_device) {
+    rc = flight_run(p, (long)batch, K, o->formulation, substeps, sol_blob, flown_traj, local_err, summary, stream, g_err, sizeof g_err);
+    if (rc) return rc;
+    if (!stream) HIPCHK(hipStreamSynchronize(stream));
+    return ASCENT_OK;
+  }
+  const size_t nb = (21 * (size_t)K + NSC) * batch, ntr = (size_t)ASCENT_TRAJ_FIELDS * o->n_nodes * batch, nl = (size_t)7 * K * batch,
+               ns = (size_t)ASCENT_FLIGHT_ROWS * batch;
+  DevBuf<ascent_params> bp;
+  DevBuf<double> bb, bt, bl, bs;
+  HIPCHK(bp.alloc(batch)); HIPCHK(bb.alloc(nb)); HIPCHK(bs.alloc(ns));
+  if (flown_traj) HIPCHK(bt.alloc(ntr));
+  if (local_err) HIPCHK(bl.alloc(nl));
+  HIPCHK(hipMemcpyAsync(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(bb.d, sol_blob, nb * sizeof(double), hipMemcpyHostToDevice, stream));
+  rc = flight_run(bp.d, (long)batch, K, o->formulation, substeps, bb.d, bt.d, bl.d, bs.d, stream, g_err, sizeof g_err);
+  if (rc) return rc;
+  if (flown_traj) HIPCHK(hipMemcpyAsync(flown_traj, bt.d, ntr * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (local_err) HIPCHK(hipMemcpyAsync(local_err, bl.d, nl * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(summary, bs.d, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   return ASCENT_OK;
 }

@@ -41,6 +41,22 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+FLIGHT_ROWS = ("miss_position", "miss_velocity", "flown_periapsis_alt", "flown_apoapsis_alt", "nlp_periapsis_alt",
+               "nlp_apoapsis_alt", "max_local_position_error", "max_local_velocity_error", "max_local_step", "substeps")
+
+
+@dataclasses.dataclass
+class FlightResult:
+    """What every solution's control reaches when it is flown (fly_batch; include/ascent.h: ascent_fly_batch).  Problem index first."""
+    traj: np.ndarray | None         # (batch, 10, nt) the flown trajectory, scaled, fields TRAJ_FIELDS
+    local_error: np.ndarray | None  # (batch, K, 7) eta_k = (the NLP's z_{k-1} flown over step k) - z_k, scaled
+    summary: np.ndarray             # (batch, 10) SI units, columns FLIGHT_ROWS
+
+
+for _i, _n in enumerate(FLIGHT_ROWS):   # the summary columns by name: .miss_position (m), .miss_velocity (m/s), ... -> (batch,)
+    setattr(FlightResult, _n, property(lambda self, _i=_i: self.summary[:, _i]))
+
+
 @dataclasses.dataclass
 class BatchResult:
     """Solutions of a batch. Arrays keep the library's layout: problem index last."""
@@ -53,6 +69,7 @@ class BatchResult:
     blob: np.ndarray | None     # (21K+10, batch) primal-dual solution (warm-start material)
     kernel_ms: float            # device time of the solve kernel
     sensitivity: np.ndarray | None = None   # (batch, 16) d(T_scale J*)/dp, s per SI unit (solve_batch(sensitivity=True))
+    flight: FlightResult | None = None      # the solutions' controls flown with RK4 (solve_batch(flight=True))
 
     @property
     def converged(self) -> np.ndarray:
@@ -83,10 +100,25 @@ class BatchResult:
         return dict(periapsis_alt=a * (1 - e) - R0, apoapsis_alt=a * (1 + e) - R0, semi_major_axis=a, eccentricity=e,
                     flight_path_angle=np.arcsin(np.clip((X * VX + Y * VY) / (r * np.sqrt(v2)), -1, 1)))
 
-    def coast(self, coast_nodes: int = 200, device: int = 0) -> dict:
+    def coast(self, coast_nodes: int = 200, device: int = 0, flown: bool = False) -> dict:
         """The second phase: coast from every problem's burnout state to the apoapsis of its orbit, propagated on the
-        device (Kepler-exact; see coast_batch).  With terminal="ellipse" the arc ends at r_apo above the surface."""
-        return coast_batch(self.params, np.ascontiguousarray(self.traj[:4, -1, :]), coast_nodes, device)
+        device (Kepler-exact; see coast_batch).  With terminal="ellipse" the arc ends at r_apo above the surface.
+        flown: start from the burnout state the control actually reaches (solve_batch(flight=True)) instead of the NLP's."""
+        if not flown:
+            return coast_batch(self.params, np.ascontiguousarray(self.traj[:4, -1, :]), coast_nodes, device)
+        if self.flight is None or self.flight.traj is None:
+            raise ValueError("coast(flown=True) needs the flown trajectory: solve_batch(..., flight=True)")
+        return coast_batch(self.params, np.ascontiguousarray(self.flight.traj[:, :4, -1].T), coast_nodes, device)
+
+    def flight_blob(self) -> np.ndarray:
+        """The part of a solution blob that fly_batch reads -- states, control and tf -- rebuilt from the trajectory (the rest
+        zero): (21K+10, batch).  For results that were returned without their blob."""
+        K, B = self.nt - 1, self.params.shape[0]
+        blob = np.zeros((blob_rows(self.nt), B))
+        blob[:7 * K] = self.traj[[0, 1, 2, 3, 6, 7, 9], 1:].transpose(1, 0, 2).reshape(7 * K, B)
+        blob[7 * K:8 * K] = self.traj[8, 1:]
+        blob[21 * K] = self.tf
+        return blob
 
     def outputs(self, i: int = 0) -> dict:
         """The quantities the reference prints/plots for problem i (Launch_Optimiser.py:178-202):
@@ -111,7 +143,7 @@ class BatchResult:
 def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, guess: np.ndarray | None = None,
                 warm_start: int | None = None, mu_init: float = 0.0, device: int = 0, want_traj: bool = True,
                 want_blob: bool = False, scheme=0, formulation=0, coarse_nodes: int = 0, terminal=0,
-                path: str = "auto", move_penalty: bool = False, sensitivity: bool = False) -> BatchResult:
+                path: str = "auto", move_penalty: bool = False, sensitivity: bool = False, flight: bool = False) -> BatchResult:
     """Solve a batch of ascent NLPs on one GPU.  params: AscentParams | list | (batch,16) array.
     guess: (21K+10, batch) blob, with warm_start 1 (primal only) or 2 (primal-dual).
     scheme: 0 / "backward_euler" (the reference's NODES=2), 1 / "trapezoid" or 2 / "hermite_simpson" (both with the
@@ -128,7 +160,10 @@ def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, g
     `iters` then counts the iterations of all grid levels.
     sensitivity: also set `BatchResult.sensitivity`, (batch, 16) d(T_scale J*)/dp in seconds per SI unit of every parameter
     field (param_sensitivity at the solution; the T_scale column is J* + T_scale dJ*/dT_scale); rows of problems that did not
-    converge are NaN.  Without the move penalty this is d t_f*/dp; with it, the penalised objective in seconds."""
+    converge are NaN.  Without the move penalty this is d t_f*/dp; with it, the penalised objective in seconds.
+    flight: also set `BatchResult.flight`, a FlightResult: every solution's control flown with RK4 on the device (fly_batch,
+    automatic substeps) -- the flown trajectory, the local error of every step and the miss at burnout; rows of problems that
+    did not converge are NaN."""
     L = _lib.load()
     P = pack(params)
     B = P.shape[0]
@@ -141,7 +176,7 @@ def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, g
             warm_start = 1
     warm_start = warm_start or 0
     traj = np.empty((10, nt, B)) if want_traj else None
-    blob = np.empty((rows, B)) if (want_blob or sensitivity) else None
+    blob = np.empty((rows, B)) if (want_blob or sensitivity or flight) else None
     tf = np.empty(B)
     status = np.empty(B, dtype=np.int32)
     iters = np.empty(B, dtype=np.int32)
@@ -155,7 +190,13 @@ def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, g
                               move_penalty=move_penalty, device=device)
         sens = _seconds(P, blob, nt, g, formulation, move_penalty)
         sens[status != 0] = np.nan
-    return BatchResult(P, nt, traj, tf, status, iters, blob if want_blob else None, kms, sens)
+    fl = None
+    if flight:
+        fl = fly_batch(P, blob, nt, scheme=scheme, formulation=formulation, terminal=terminal, move_penalty=move_penalty,
+                       device=device)
+        for a in (fl.traj, fl.local_error, fl.summary):
+            a[status != 0] = np.nan
+    return BatchResult(P, nt, traj, tf, status, iters, blob if want_blob else None, kms, sens, fl)
 
 
 def _penalty_weight(P, formulation):
@@ -200,6 +241,31 @@ def param_sensitivity(params, sol_blob: np.ndarray, nt: int, scheme=0, formulati
     o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
     _lib.check(L.ascent_param_sensitivity(_ptr(P), B, C.byref(o), _ptr(blob), _ptr(g), device, None, 0))
     return np.ascontiguousarray(g.T)
+
+
+def fly_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,
+              substeps: int = 0, device: int = 0, want_traj: bool = True, want_local: bool = True) -> FlightResult:
+    """Flight verification (include/ascent.h: ascent_fly_batch): integrate the model's ODEs on the device under the control of
+    the solution blob (21K+10, batch) that solve_batch returned with the same options -- u_k held over step k, classical RK4 with
+    `substeps` steps per collocation step (0: automatic, substeps of at most 0.5 s) -- and compare with the NLP's own
+    trajectory.  Returns a FlightResult: the flown trajectory, the local discretisation error of every step (each step flown
+    from the NLP's own z_{k-1}), and per problem the miss at the last node, the flown and the NLP's burnout orbit and the largest
+    local error (FLIGHT_ROWS).  Rows of problems that did not converge are computed from whatever the blob holds."""
+    P = pack(params)
+    B, K = P.shape[0], nt - 1
+    blob = np.ascontiguousarray(sol_blob, dtype=np.float64)
+    if blob.shape != (blob_rows(nt), B):
+        raise ValueError(f"sol_blob must have shape {(blob_rows(nt), B)}")
+    L = _lib.load()
+    traj = np.empty((10, nt, B)) if want_traj else None
+    local = np.empty((K, 7, B)) if want_local else None
+    summ = np.empty((len(FLIGHT_ROWS), B))
+    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
+    _lib.check(L.ascent_fly_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(traj), _ptr(local), _ptr(summ),
+                                  device, None, 0))
+    return FlightResult(None if traj is None else np.ascontiguousarray(traj.transpose(2, 0, 1)),
+                        None if local is None else np.ascontiguousarray(local.transpose(2, 0, 1)),
+                        np.ascontiguousarray(summ.T))
 
 
 def eval_nodes(params, iterate: np.ndarray, nt: int = 200, device: int = 0, path="auto", scheme=0, formulation=0):
@@ -299,14 +365,17 @@ def solve_batch_torch(params_t, nt: int = 200, tol: float = 1e-9, max_iter: int 
                       warm_start: int = 0, mu_init: float = 0.0, want_traj: bool = True, want_blob: bool = False,
                       out: dict | None = None, sync: bool = False, coarse_nodes: int = 0, scheme=0,
                       formulation=0, move_penalty: bool = False, terminal=0, path: str = "auto",
-                      sensitivity: bool = False) -> dict:
+                      sensitivity: bool = False, flight: bool = False) -> dict:
     """Device-resident variant: `params_t` is a torch float64 CUDA tensor (batch,16); all outputs are
     torch CUDA tensors (allocated here unless passed in `out`).  Enqueues on torch's current stream
     and returns without waiting unless sync=True.  torch is only the owner of device memory/streams.
     Options as solve_batch (scheme, formulation, terminal, path, move_penalty: the weights params_t[:, 15] must be
     positive then -- checked here on the device, the library cannot look into device memory from the host).
     sensitivity: also out["sensitivity"], (batch, 16) d(T_scale J*)/dp as solve_batch(sensitivity=True) computes it (NaN rows
-    for problems that did not converge), enqueued on the same stream right after the solve: no host read."""
+    for problems that did not converge), enqueued on the same stream right after the solve: no host read.
+    flight: also out["flight_summary"] (batch, 10), out["flight_traj"] (batch, 10, nt) and out["flight_local"] (batch, K, 7) as
+    solve_batch(flight=True) computes them (NaN rows for problems that did not converge), enqueued on the same stream after
+    the solve: no host read."""
     import torch
     L = _lib.load()
     _lib.require_single_hip_runtime()
@@ -337,9 +406,12 @@ def solve_batch_torch(params_t, nt: int = 200, tol: float = 1e-9, max_iter: int 
     iters = buf("iters", (B,), torch.int32)
     traj = buf("traj", (10, nt, B), torch.float64) if want_traj else None
     blob = buf("blob", (rows, B), torch.float64) if want_blob else None
-    if sensitivity and blob is None:       # the solve's blob, needed by the sensitivity kernel only
+    if (sensitivity or flight) and blob is None:       # the solve's blob, needed by the sensitivity / flight kernels only
         blob = torch.empty((rows, B), dtype=torch.float64, device=dev)
     sens = buf("sensitivity", (B, 16), torch.float64) if sensitivity else None
+    if flight:
+        fsum, ftraj = buf("flight_summary", (B, len(FLIGHT_ROWS)), torch.float64), buf("flight_traj", (B, 10, nt), torch.float64)
+        floc = buf("flight_local", (B, nt - 1, 7), torch.float64)
     o = _opts(nt, max_iter, tol, warm_start, mu_init, scheme, formulation, coarse_nodes, terminal, path, move_penalty)
     stream = torch.cuda.current_stream(dev).cuda_stream
     _lib.check(L.ascent_solve_batch(params_t.data_ptr(), B, C.byref(o),
@@ -361,6 +433,17 @@ def solve_batch_torch(params_t, nt: int = 200, tol: float = 1e-9, max_iter: int 
         s_ = g.t() * params_t[:, 11:12]
         s_[:, 11] += J
         sens.copy_(torch.where((status == 0)[:, None], s_, torch.full_like(s_, float("nan"))))
+    if flight:
+        K = nt - 1
+        rs = torch.empty((len(FLIGHT_ROWS), B), dtype=torch.float64, device=dev)
+        rt = torch.empty((10, nt, B), dtype=torch.float64, device=dev)
+        rl = torch.empty((K, 7, B), dtype=torch.float64, device=dev)
+        _lib.check(L.ascent_fly_batch(params_t.data_ptr(), B, C.byref(o), blob.data_ptr(), 0, rt.data_ptr(), rl.data_ptr(),
+                                      rs.data_ptr(), dev.index or 0, C.c_void_p(stream), 1))
+        ok, nan = status == 0, torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        fsum.copy_(torch.where(ok[:, None], rs.t(), nan))
+        ftraj.copy_(torch.where(ok[:, None, None], rt.permute(2, 0, 1), nan))
+        floc.copy_(torch.where(ok[:, None, None], rl.permute(2, 0, 1), nan))
     if sync:
         torch.cuda.synchronize(dev)
     return out
