@@ -4,8 +4,10 @@
 This is this repository's own counterpart of the reference script: the same problem, declared with
 the same modelling calls, solved by libascent on an MI355X instead of GEKKO/APMonitor/IPOPT.  It prints
 the quantities the reference prints (/root/reference/Launch_Optimiser.py:178-194) and writes the same
-three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly]
+three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim]
 --fly also integrates the ODEs under the control just found (RK4 on the device) and prints where that flight ends.
+--trim corrects (t_f, u) so that the flown control reaches the target orbit (trim_batch) and prints t_f and the flown apsides
+before and after.
 """
 import argparse
 import os
@@ -104,6 +106,22 @@ def fly(m, scheme):
     return f
 
 
+def trim(m, scheme):
+    """The solved case trimmed: t_f and the control corrected so that the flown trajectory meets the terminal conditions."""
+    from lunar_module_ascent_trajectory_optimiser_amd import fly_batch, trim_batch
+    res = m.result
+    blob, T = res.flight_blob(), res.params[0, 11]
+    kw = dict(scheme=scheme, formulation=m._formulation)
+    before = fly_batch(res.params, blob, res.nt, want_traj=False, want_local=False, **kw)
+    t = trim_batch(res.params, blob, res.nt, **kw)
+    print("trim: status %d after %d rounds, flown conditions %.3g -> %.3g (scaled), %d of %d controls free, max |du| %.4g"
+          % (t.status[0], t.rounds[0], t.residual_before[0], t.residual[0], t.free_controls[0], res.nt - 1, t.max_delta_u[0]))
+    print("final time                                  before %.4f s   after %.4f s" % (res.tf[0] * T, t.tf[0] * T))
+    print("flown periapsis / apoapsis altitude (m)     before %.1f / %.1f   after %.3f / %.3f"
+          % (before.flown_periapsis_alt[0], before.flown_apoapsis_alt[0], t.flown_periapsis_alt[0], t.flown_apoapsis_alt[0]))
+    return t
+
+
 def plots(m, v, outdir):
     import matplotlib
     matplotlib.use("Agg")
@@ -138,6 +156,7 @@ if __name__ == "__main__":
     ap.add_argument("--no-dcost", action="store_true", help="ignore the MV's DCOST = 1e-5 (Launch_Optimiser.py:99; applied as an l1 move penalty by default)")
     ap.add_argument("--scheme", type=int, default=0, help="0 backward Euler (the reference's NODES=2), 1 trapezoid, 2 Hermite-Simpson")
     ap.add_argument("--fly", action="store_true", help="fly the solution's control with RK4 on the device and print what it reaches")
+    ap.add_argument("--trim", action="store_true", help="trim t_f and the control so that the flown trajectory reaches its orbit; prints before / after")
     a = ap.parse_args()
     model, variables, v_ins = build()
     if a.no_dcost:
@@ -148,5 +167,7 @@ if __name__ == "__main__":
     report(model, variables, v_ins)
     if a.fly:
         fly(model, a.scheme)
+    if a.trim:
+        trim(model, a.scheme)
     if not a.no_plots:
         plots(model, variables, a.outdir)

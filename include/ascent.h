@@ -277,6 +277,53 @@ int ascent_fly_batch(const ascent_params *p, int64_t batch, const ascent_opts *o
                      int32_t substeps, double *flown_traj_out_or_null, double *local_err_out_or_null,
                      double *summary_out, int device_id, void *hip_stream_or_null, int ptr_is_device);
 
+/* Flight Jacobian: the exact derivative of the discrete RK4 flight that ascent_fly_batch computes -- the open-loop
+ * counterpart of ascent_param_sensitivity (which gives d t_f* / dp under re-optimisation): what a dispersed vehicle does under
+ * the nominal control.  The map is F(z_0, p, t_f, u_1..u_K) -> the flown state at the last node: RK4 with m substeps per
+ * collocation step, m as ascent_fly_batch picks it at the blob (substeps = 0) and then held fixed; formulation 1 resets the
+ * angle at the start of every step.  It is the derivative of the arithmetic itself (the tangent of every RK4 stage), so it
+ * agrees with finite differences of ascent_fly_batch to their truncation error.
+ * Rows q (9): 0..6 the flown z_K in scaled units (x y xdot ydot angle angledot mass); 7 / 8 the flown periapsis / apoapsis
+ *   altitude in metres (summary rows 2 / 3 of ascent_fly_batch); row 8 is NaN where the flown specific energy is >= 0.
+ * jac_out [9][24][batch], element (q, c, problem) at jac_out[(q*24 + c)*batch + problem]: columns 0..6 the initial state z_0
+ *   (zero in every blob; scaled units), 7..22 the 16 ascent_params fields in declaration order, per SI unit of the field with
+ *   the blob held fixed in scaled units, 23 the scaled t_f.  Fields the flight does not read give exact zeros: r_apo, tf_lb,
+ *   tf_ub, dcost, angle_ub in formulation 0, ang_acc_max in formulation 1.
+ * jac_u_out_or_null [9][K][batch]: entry (q, k-1) is d/d u_k.
+ * Options: refuses (ASCENT_E_ARG) exactly what ascent_fly_batch refuses, plus terminal = 2.  Garbage blobs: the work is
+ * bounded as in ascent_fly_batch (K / 16 chunks of at most 4 * ASCENT_FLIGHT_MAX_SUBSTEPS serial right-hand sides after the
+ * fly-out itself); NaN rows are allowed.  A problem gives the same bits alone as inside any batch.  Host or device pointers
+ * (ptr_is_device); with device pointers and a stream the call only enqueues two kernels (the library's workspace for these
+ * two entry points is allocated on the first call of that size). */
+int ascent_flight_jacobian(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                           int32_t substeps, double *jac_out, double *jac_u_out_or_null, int device_id,
+                           void *hip_stream_or_null, int ptr_is_device);
+
+/* Trim: a least-norm Newton correction of (t_f, u) that drives the FLOWN terminal conditions to zero, so that the control,
+ * flown by ascent_fly_batch, reaches the orbit the NLP asked for.  Conditions c(z): e3, g1, g2 of the terminal constraints
+ * (r.v = 0, radius, speed^2 with the target speed of o->terminal = 0 or 1), as equalities, at the flown last node, scaled units.
+ * One round, per problem: fly; stop and freeze if |c|_inf <= tol; A = grad c [J_tf | J_u] (3 x (K+1), from rows 0..6 of the
+ * flight Jacobian); weights W: t_f 1, u_k 1 where |u_k| < 0.999 and 0 otherwise (saturated controls stay where they are);
+ * delta = -W A' (A W A')^-1 c;  t_f += delta_0,  u <- clip(u + delta, -1, 1).  `rounds` rounds are enqueued (1 .. 32, 0 = 6);
+ * converged problems freeze themselves on the device, there is no host round trip.  tol <= 0: 1e-10.  With substeps = 0 every
+ * round picks m from its current t_f.  A non-finite condition or a pivot of the 3 x 3 normal matrix below 1e-300 freezes the
+ * problem with status 2: no fault, bounded work.
+ * trim_blob_out [21K+10][batch]: the input blob with the u rows and the t_f row replaced and the state rows replaced by the
+ *   flown states of the trimmed control (ascent_fly_batch on it reports zero local error).  The multipliers are copied
+ *   unchanged and are STALE: the trimmed point is not a KKT point of the NLP.
+ * summary_out [ASCENT_TRIM_ROWS][batch]:
+ *   0 status: 0 converged, 1 rounds exhausted, 2 frozen as non-finite or singular       1 rounds used (updates applied)
+ *   2 final |c|_inf        3 |c|_inf before the first round        4 delta t_f in seconds        5 max_k |u_k - u_k(input)|
+ *   6 number of free controls (|u_k| < 0.999) at the last round that looked at the problem
+ *   7 / 8 flown periapsis / apoapsis altitude after the trim, m (as ascent_fly_batch rows 2 / 3)
+ *   9 the largest violation of 0 <= angle <= angle_ub along the trimmed flight (scaled angle; 0 = none)
+ * Options, pointers and stream as ascent_flight_jacobian; with device pointers and a stream the call only enqueues (one copy,
+ * one memset, three kernels per round and two more). */
+#define ASCENT_TRIM_ROWS 10
+int ascent_trim_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                      int32_t rounds, double tol, double *trim_blob_out, double *summary_out, int device_id,
+                      void *hip_stream_or_null, int ptr_is_device);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

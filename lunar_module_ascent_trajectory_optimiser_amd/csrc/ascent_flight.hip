@@ -23,6 +23,7 @@
 #include "ascent.h"
 #include "ascent_device.hpp"
 #include "ascent_flight.hpp"
+#include "ascent_flight_dev.hpp"
 #include "ascent_sens.hpp"
 
 namespace ascent {
@@ -31,62 +32,6 @@ namespace {
 constexpr int FW = 64;                     // f_fly: threads per workgroup (one wavefront)
 constexpr int LB = 256;                    // f_local: threads per workgroup
 constexpr int LNW = LB / 64;
-
-// substeps per collocation step: the caller's, or (0) dt / 0.5 s rounded up, 1 .. ASCENT_FLIGHT_MAX_SUBSTEPS; whatever the
-// blob holds, the loops below are bounded by it
-ASC_DEV int flight_substeps(double dt, int substeps) {
-  if (substeps > 0) return substeps;
-  if (!(fabs(dt) <= 1.79769313486231570815e308)) return 1;      // NaN, +-inf
-  const double q = ceil(dt / 0.5);
-  return q >= (double)ASCENT_FLIGHT_MAX_SUBSTEPS ? ASCENT_FLIGHT_MAX_SUBSTEPS : q >= 1.0 ? (int)q : 1;
-}
-
-template <int FORM>
-ASC_DEV void flight_f(const Der &d, const double *z, double u, double *F) {
-  double ax, ay;
-  accel<0>(d, z[IX], z[IY], z[IA], z[IM], 0.0, 0.0, ax, ay, nullptr, nullptr);
-  rhs_f<FORM>(d, z, u, ax, ay, F);
-}
-
-// one collocation step: m classical RK4 steps of size hs under the held control u
-template <int FORM>
-ASC_DEV void fly_step(const Der &d, double *z, double u, double hs, int m) {
-  if (FORM == 1) { z[IA] = 0.5 * d.aub * (u + 1.0); z[IW] = 0.0; }
-  for (int j = 0; j < m; j++) {
-    double k1[7], k2[7], k3[7], k4[7], w[7];
-    flight_f<FORM>(d, z, u, k1);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) w[i] = z[i] + 0.5 * hs * k1[i];
-    flight_f<FORM>(d, w, u, k2);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) w[i] = z[i] + 0.5 * hs * k2[i];
-    flight_f<FORM>(d, w, u, k3);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) w[i] = z[i] + hs * k3[i];
-    flight_f<FORM>(d, w, u, k4);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) z[i] += hs * (1.0 / 6.0) * (k1[i] + 2.0 * (k2[i] + k3[i]) + k4[i]);
-  }
-}
-
-// periapsis / apoapsis altitude above R0 (m) of the two-body orbit through a scaled state: k_coast's formulas (semi-major axis
-// from the vis-viva equation, eccentricity vector); specific energy >= 0: periapsis from the semi-latus rectum, apoapsis +inf
-ASC_DEV void apsides_of(const ascent_params &prm, double x, double y, double vx, double vy, double &peri, double &apo) {
-  const double S = prm.r_peri, GM = prm.G * prm.M;
-  const double X = x * S, Y = y * S + prm.R0, VX = vx * S, VY = vy * S;
-  const double r = sqrt(X * X + Y * Y), v2 = VX * VX + VY * VY, rv = X * VX + Y * VY;
-  const double ex = (v2 / GM - 1.0 / r) * X - rv / GM * VX, ey = (v2 / GM - 1.0 / r) * Y - rv / GM * VY;
-  const double e = sqrt(ex * ex + ey * ey);
-  if (0.5 * v2 - GM / r >= 0.0) {
-    const double h = X * VY - Y * VX;
-    peri = h * h / (GM * (1.0 + e)) - prm.R0;
-    apo = INFINITY;
-  } else {
-    const double a = 1.0 / (2.0 / r - v2 / GM);
-    peri = a * (1.0 - e) - prm.R0;
-    apo = a * (1.0 + e) - prm.R0;
-  }
-}
 
 template <int FORM>
 __global__ __launch_bounds__(FW) void f_fly(const ascent_params *__restrict__ P, long batch, int K, int substeps,
@@ -221,14 +166,20 @@ __global__ __launch_bounds__(LB) void f_local(const ascent_params *__restrict__ 
 
 #define FCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #call, hipGetErrorString(e_)); return ASCENT_E_HIP; } } while (0)
 
-int flight_run(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
-               double *dlocal, double *dsummary, hipStream_t stream, char *err, size_t errlen) {
+int flight_fly_only(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
+                    double *dsummary, hipStream_t stream, char *err, size_t errlen) {
   const dim3 gfly((unsigned)((batch + FW - 1) / FW)), bfly(FW);
   if (formulation == 1)
     hipLaunchKernelGGL((f_fly<1>), gfly, bfly, 0, stream, dp, batch, K, substeps, dblob, dtraj, dsummary);
   else
     hipLaunchKernelGGL((f_fly<0>), gfly, bfly, 0, stream, dp, batch, K, substeps, dblob, dtraj, dsummary);
   FCHK(hipGetLastError());
+  return ASCENT_OK;
+}
+
+int flight_run(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
+               double *dlocal, double *dsummary, hipStream_t stream, char *err, size_t errlen) {
+  if (const int rc = flight_fly_only(dp, batch, K, formulation, substeps, dblob, dtraj, dsummary, stream, err, errlen)) return rc;
   const int pb = sens_problems_per_group(batch);      // the same split of a workgroup between NLPs and steps as s_sens
   const dim3 gloc((unsigned)((batch + pb - 1) / pb)), bloc(LB);
   if (formulation == 1)

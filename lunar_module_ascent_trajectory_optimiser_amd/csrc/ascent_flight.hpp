@@ -13,4 +13,9 @@ namespace ascent {
 int flight_run(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
                double *dlocal, double *dsummary, hipStream_t stream, char *err, size_t errlen);
 
+// The serial fly-out alone (f_fly; summary rows 0..5 and 9 only): the linearisation point of the flight Jacobian and every
+// round of the trim (ascent_trim.hip).
+int flight_fly_only(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
+                    double *dsummary, hipStream_t stream, char *err, size_t errlen);
+
 }  // namespace ascent

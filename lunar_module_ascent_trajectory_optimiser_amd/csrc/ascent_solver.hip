@@ -10,7 +10,8 @@
 //   split pipeline q_*              ascent_pipeline.hpp (ascent_pipeline.hip)
 //   fused k_solve                   ascent_fused.hpp (ascent_fused.hip)
 // the post-optimal sensitivity s_sens, ascent_sens.hpp (ascent_sens.hip), and the flight verification f_fly / f_local,
-// ascent_flight.hpp (ascent_flight.hip).
+// ascent_flight.hpp (ascent_flight.hip), and the flight Jacobian and trim j_jac / t_update / t_final, ascent_trim.hpp
+// (ascent_trim.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -30,6 +31,7 @@
 #include "ascent_fused.hpp"
 #include "ascent_sens.hpp"
 #include "ascent_flight.hpp"
+#include "ascent_trim.hpp"
 
 using namespace ascent;
 
@@ -307,7 +309,7 @@ int check_device(int device_id) {
   return 0;
 }
 
-int check_common(const ascent_params *p, int64_t batch, const ascent_opts *o, int device_id) {
+int check_options(const ascent_params *p, int64_t batch, const ascent_opts *o) {
   if (!p || !o || batch <= 0) { snprintf(g_err, sizeof g_err, "null params/opts or batch <= 0"); return ASCENT_E_ARG; }
   if (o->n_nodes < 3 || o->n_nodes > 65536) { snprintf(g_err, sizeof g_err, "n_nodes out of range (3 .. 65536)"); return ASCENT_E_ARG; }
   if (o->formulation != 0 && o->formulation != 1) { snprintf(g_err, sizeof g_err, "formulation %d not supported (0 = current script, 1 = v1 script)", o->formulation); return ASCENT_E_ARG; }
@@ -320,6 +322,10 @@ int check_common(const ascent_params *p, int64_t batch, const ascent_opts *o, in
   if ((o->scheme == 2 || o->solver_path == ASCENT_PATH_DENSE) && o->formulation != 0) { snprintf(g_err, sizeof g_err, "the dense-block path (scheme 2 / ASCENT_PATH_DENSE) has formulation 0 only"); return ASCENT_E_ARG; }
   if (o->move_penalty && o->formulation != 0 && (o->scheme != 0 || o->solver_path == ASCENT_PATH_DENSE)) { snprintf(g_err, sizeof g_err, "move_penalty = 1 with formulation 1: scheme 0, persistent kernel only"); return ASCENT_E_ARG; }
   if (o->move_penalty != 0 && o->move_penalty != 1) { snprintf(g_err, sizeof g_err, "move_penalty must be 0 or 1"); return ASCENT_E_ARG; }
+  return 0;
+}
+int check_common(const ascent_params *p, int64_t batch, const ascent_opts *o, int device_id) {
+  if (const int rc = check_options(p, batch, o)) return rc;
   return check_device(device_id);
 }
 
@@ -771,6 +777,126 @@ int ascent_fly_batch(const ascent_params *p, int64_t batch, const ascent_opts *o
   if (flown_traj) HIPCHK(hipMemcpyAsync(flown_traj, bt.d, ntr * sizeof(double), hipMemcpyDeviceToHost, stream));
   if (local_err) HIPCHK(hipMemcpyAsync(local_err, bl.d, nl * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipMemcpyAsync(summary, bs.d, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return ASCENT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Flight Jacobian and trim (ascent_trim.hip).  Their device workspace is one buffer per device, apart from the solver's: a
+// call on another stream than its predecessor waits for the predecessor's last kernel (an event) before it reuses the buffer;
+// growing it frees the old one, which waits for the device.
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct TrimDeviceWs { double *ws = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool used = false; };
+TrimDeviceWs g_trim_ws[MAX_DEV];
+
+int trim_ws_claim(int dev, size_t bytes, hipStream_t stream, double **out) {      // (under g_mu[dev])
+  TrimDeviceWs &w = g_trim_ws[dev];
+  if (!w.ev) HIPCHK(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+  if (w.bytes < bytes) {
+    if (w.ws) HIPCHK(hipFree(w.ws));
+    w.ws = nullptr; w.bytes = 0;
+    const hipError_t e = hipMalloc(&w.ws, bytes);
+    if (e != hipSuccess) { snprintf(g_err, sizeof g_err, "workspace hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e)); return ASCENT_E_NOMEM; }
+    w.bytes = bytes;
+  } else if (w.used) {
+    HIPCHK(hipStreamWaitEvent(stream, w.ev, 0));
+  }
+  *out = w.ws;
+  return 0;
+}
+int trim_ws_release(int dev, hipStream_t stream) {
+  TrimDeviceWs &w = g_trim_ws[dev];
+  HIPCHK(hipEventRecord(w.ev, stream));
+  w.used = true;
+  return 0;
+}
+
+// what ascent_fly_batch refuses, plus terminal = 2; every argument error before the device is looked at
+int check_flight_like(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                      int device_id, int ptr_is_device) {
+  int rc = check_options(p, batch, o);
+  if (rc) return rc;
+  if (!sol_blob) { snprintf(g_err, sizeof g_err, "null solution blob"); return ASCENT_E_ARG; }
+  if (substeps < 0 || substeps > ASCENT_FLIGHT_MAX_SUBSTEPS) { snprintf(g_err, sizeof g_err, "substeps out of range (0 = automatic, 1 .. %d)", ASCENT_FLIGHT_MAX_SUBSTEPS); return ASCENT_E_ARG; }
+  if (o->terminal == 2) { snprintf(g_err, sizeof g_err, "terminal 2 is not supported by the flight Jacobian and the trim (its two conditions are nearly dependent where burnout sits at an apsis)"); return ASCENT_E_ARG; }
+  const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
+  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
+  if (o->move_penalty && !ptr_is_device && (rc = check_dcost(p, batch))) return rc;
+  return 0;
+}
+}  // namespace
+
+int ascent_flight_jacobian(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                           double *jac_out, double *jac_u_out, int device_id, void *stream_, int ptr_is_device) {
+  int rc = check_flight_like(p, batch, o, sol_blob, substeps, device_id, ptr_is_device);
+  if (rc) return rc;
+  if (!jac_out) { snprintf(g_err, sizeof g_err, "null jac_out"); return ASCENT_E_ARG; }
+  if ((rc = check_device(device_id))) return rc;
+  std::lock_guard<std::mutex> lock(g_mu[device_id]);
+  HIPCHK(hipSetDevice(device_id));
+  hipStream_t stream = (hipStream_t)stream_;
+  const int K = o->n_nodes - 1;
+  double *ws = nullptr;
+  if ((rc = trim_ws_claim(device_id, jac_ws_bytes(K, (long)batch), stream, &ws))) return rc;
+  if (ptr_is_device) {
+    rc = jac_run(p, (long)batch, K, o->formulation, substeps, sol_blob, jac_out, jac_u_out, ws, stream, g_err, sizeof g_err);
+    if (rc) return rc;
+    if ((rc = trim_ws_release(device_id, stream))) return rc;
+    if (!stream) HIPCHK(hipStreamSynchronize(stream));
+    return ASCENT_OK;
+  }
+  const size_t nb = (21 * (size_t)K + NSC) * batch, nj = (size_t)9 * 24 * batch, nu = (size_t)9 * K * batch;
+  DevBuf<ascent_params> bp;
+  DevBuf<double> bb, bj, bu;
+  HIPCHK(bp.alloc(batch)); HIPCHK(bb.alloc(nb)); HIPCHK(bj.alloc(nj));
+  if (jac_u_out) HIPCHK(bu.alloc(nu));
+  HIPCHK(hipMemcpyAsync(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(bb.d, sol_blob, nb * sizeof(double), hipMemcpyHostToDevice, stream));
+  rc = jac_run(bp.d, (long)batch, K, o->formulation, substeps, bb.d, bj.d, bu.d, ws, stream, g_err, sizeof g_err);
+  if (rc) return rc;
+  if ((rc = trim_ws_release(device_id, stream))) return rc;
+  HIPCHK(hipMemcpyAsync(jac_out, bj.d, nj * sizeof(double), hipMemcpyDeviceToHost, stream));
+  if (jac_u_out) HIPCHK(hipMemcpyAsync(jac_u_out, bu.d, nu * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  return ASCENT_OK;
+}
+
+int ascent_trim_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                      int32_t rounds, double tol, double *trim_blob_out, double *summary_out, int device_id, void *stream_,
+                      int ptr_is_device) {
+  int rc = check_flight_like(p, batch, o, sol_blob, substeps, device_id, ptr_is_device);
+  if (rc) return rc;
+  if (!trim_blob_out || !summary_out) { snprintf(g_err, sizeof g_err, "null trim_blob_out or summary_out"); return ASCENT_E_ARG; }
+  if (rounds < 0 || rounds > 32) { snprintf(g_err, sizeof g_err, "rounds out of range (1 .. 32, 0 = 6)"); return ASCENT_E_ARG; }
+  if ((rc = check_device(device_id))) return rc;
+  if (rounds == 0) rounds = 6;
+  if (!(tol > 0.0)) tol = 1e-10;
+  std::lock_guard<std::mutex> lock(g_mu[device_id]);
+  HIPCHK(hipSetDevice(device_id));
+  hipStream_t stream = (hipStream_t)stream_;
+  const int K = o->n_nodes - 1;
+  double *ws = nullptr;
+  if ((rc = trim_ws_claim(device_id, trim_ws_bytes(K, (long)batch), stream, &ws))) return rc;
+  if (ptr_is_device) {
+    rc = trim_run(p, (long)batch, K, o->formulation, o->terminal, substeps, rounds, tol, sol_blob, trim_blob_out, summary_out, ws, stream,
+                  g_err, sizeof g_err);
+    if (rc) return rc;
+    if ((rc = trim_ws_release(device_id, stream))) return rc;
+    if (!stream) HIPCHK(hipStreamSynchronize(stream));
+    return ASCENT_OK;
+  }
+  const size_t nb = (21 * (size_t)K + NSC) * batch, ns = (size_t)ASCENT_TRIM_ROWS * batch;
+  DevBuf<ascent_params> bp;
+  DevBuf<double> bb, bo, bs;
+  HIPCHK(bp.alloc(batch)); HIPCHK(bb.alloc(nb)); HIPCHK(bo.alloc(nb)); HIPCHK(bs.alloc(ns));
+  HIPCHK(hipMemcpyAsync(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(bb.d, sol_blob, nb * sizeof(double), hipMemcpyHostToDevice, stream));
+  rc = trim_run(bp.d, (long)batch, K, o->formulation, o->terminal, substeps, rounds, tol, bb.d, bo.d, bs.d, ws, stream, g_err, sizeof g_err);
+  if (rc) return rc;
+  if ((rc = trim_ws_release(device_id, stream))) return rc;
+  HIPCHK(hipMemcpyAsync(trim_blob_out, bo.d, nb * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(summary_out, bs.d, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   return ASCENT_OK;
 }

@@ -1,0 +1,456 @@
+// Flight Jacobian and trim (include/ascent.h: ascent_flight_jacobian, ascent_trim_batch).
+//
+// The map: F(z_0, p, t_f, u_1..u_K) -> the flown state at the last node exactly as f_fly computes it (ascent_flight.hip): K
+// collocation steps of m classical RK4 substeps each, the control held over a step, m as flight_substeps picks it at the blob
+// and then held fixed.  The Jacobian is that of the discrete map (the tangent of every RK4 stage, not the variational ODE
+// integrated separately), linearised about the states f_fly itself wrote into the workspace trajectory.
+//
+// j_jac    one workgroup of JB = 256 threads per NLP; the grid is worked through in chunks of CH = 16 steps, last chunk first.
+//   evaluation  group g (16 lanes) takes step g of the chunk: every lane carries the 7-state through the step's m substeps
+//          (redundant across the group, uniform inside it) and one tangent column of the step map z_k = S(z_{k-1}, u_k, dt; Der):
+//          columns 0..6 Phi_k = dz_k/dz_{k-1}, 7 the control, 8 dt, 9..15 the Der constants the right-hand side reads (rho0, gam,
+//          thr, M0, ms, alpha, mrate; formulation 1 does not read alpha and takes angle_ub, which enters through the reset of
+//          the angle, in its place).  d f/d z from accel<1>, d f/d Der from accel_dder.
+//   staging     the 16 step records of a chunk (7 x 16 doubles each, 14 KB) go to LDS as rec[step][state][column] and never to
+//          HBM.  A wave stores 4 steps x 16 columns of one state row at a time: doubles 112 g + 16 i + col; 112 = 16 mod 32,
+//          so the two steps of each half wave fill 32 different 8-byte slots -- no bank conflict.  The sweep reads one address
+//          per instruction for the whole wave (a broadcast).
+//   sweep       wave 0, lane q = row q of Lambda (9 rows: the 7 flown states, periapsis, apoapsis): Lambda_K = I / grad apsides,
+//          Lambda_{k-1} = Lambda_k Phi_k; Lambda_k g_k goes to jac_u, Lambda_k Gamma_k is summed into 8 accumulators, steps in
+//          descending order -- a fixed order, so a problem gives the same bits alone as inside any batch.
+//   epilogue    chain rule d(dt, Der)/d(params, t_f) (derive of ascent_device.hpp) plus the direct dependence of the apsis rows
+//          on G, M, R0, r_peri; Lambda_0 gives the z_0 columns.
+// t_update one wavefront per NLP, lanes over the steps: the conditions c = (e3, g1, g2) of terminal_eval at the flown last
+//          node, A = grad c [J_tf | J_u], the 3 x 3 normal matrix A W A' (per-lane partial sums over k = lane, lane + 64, ..,
+//          then a butterfly of cross-lane shuffles: a fixed order), delta = -W A' (A W A')^-1 c, the update in place.
+// t_final  the state rows of the trimmed blob from the last fly-out, and the summary.
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cmath>
+
+#include "ascent.h"
+#include "ascent_device.hpp"
+#include "ascent_flight.hpp"
+#include "ascent_flight_dev.hpp"
+#include "ascent_trim.hpp"
+
+namespace ascent {
+namespace {
+
+constexpr int JB = 256;                    // j_jac: threads per workgroup
+constexpr int CH = 16;                     // steps per chunk = groups per workgroup
+constexpr int NCOL = 16;                   // tangent columns per step = lanes per group
+constexpr int REC = 7 * NCOL;              // doubles per step record
+constexpr int C_U = 7, C_DT = 8, C_DER = 9, C_ALPHA = 14, C_MRATE = 15;      // C_DER + ACC_RHO0 .. ACC_MS, then alpha | angle_ub, mrate
+constexpr int NACC = 8;                    // accumulators of the sweep: columns C_DT .. C_MRATE
+constexpr int JROWS = 9, JCOLS = 24;
+constexpr int TW = 64;                     // t_update / t_final: one wavefront per NLP
+// per-problem state of the trim between its kernels, rows of [ST_ROWS][batch]
+constexpr int ST_FLAG = 0 /* 0 active, 1 converged, 2 non-finite or singular */, ST_ROUNDS = 1, ST_C0 = 2, ST_NFREE = 3, ST_ROWS = 4;
+
+// the 7-state of node k in a trajectory of ascent_fly_batch's layout (fields x y xdot ydot ax ay angle angledot u mass)
+ASC_DEV void load_node(const double *__restrict__ tr, size_t B, int nt, int k, double *z) {
+  z[IX] = tr[((size_t)0 * nt + k) * B];
+  z[IY] = tr[((size_t)1 * nt + k) * B];
+  z[IVX] = tr[((size_t)2 * nt + k) * B];
+  z[IVY] = tr[((size_t)3 * nt + k) * B];
+  z[IA] = tr[((size_t)6 * nt + k) * B];
+  z[IW] = tr[((size_t)7 * nt + k) * B];
+  z[IM] = tr[((size_t)9 * nt + k) * B];
+}
+
+// f(z, u) and its tangent dF = f_z dz + (the column's own forcing): (fx, fy) picked from d accel / d Der for the columns
+// C_DER .. C_DER + 4, cw on the angledot row (alpha for the control column, u for the alpha column), cm on the mass row (mrate)
+template <int FORM>
+ASC_DEV void stage(const Der &d, const double *z, const double *dz, double u, int col, double cw, double cm, double *F, double *dF) {
+  double ax, ay, G[8], dax[ACC_NDER], day[ACC_NDER];
+  accel<1>(d, z[IX], z[IY], z[IA], z[IM], 0.0, 0.0, ax, ay, G, nullptr);
+  accel_dder(d, z[IX], z[IY], z[IA], z[IM], dax, day);
+  rhs_f<FORM>(d, z, u, ax, ay, F);
+  double fx = 0.0, fy = 0.0;
+  ASC_UNROLL
+  for (int j = 0; j < ACC_NDER; j++) {
+    const bool s = col == C_DER + j;
+    fx = s ? dax[j] : fx;
+    fy = s ? day[j] : fy;
+  }
+  dF[IX] = dz[IVX];
+  dF[IY] = dz[IVY];
+  dF[IVX] = G[0] * dz[IX] + G[1] * dz[IY] + G[2] * dz[IA] + G[3] * dz[IM] + fx;
+  dF[IVY] = G[4] * dz[IX] + G[5] * dz[IY] + G[6] * dz[IA] + G[7] * dz[IM] + fy;
+  dF[IA] = FORM == 1 ? 0.0 : dz[IW];
+  dF[IW] = FORM == 1 ? 0.0 : cw;
+  dF[IM] = cm;
+}
+
+// fly_step (ascent_flight_dev.hpp) with one tangent column carried along: z the same arithmetic, dz the exact derivative of it
+template <int FORM>
+ASC_DEV void fly_step_tangent(const Der &d, double *z, double *dz, double u, double hs, int m, int col) {
+  double cw = 0.0, cm = col == C_MRATE ? 1.0 : 0.0;
+  const double dhs = col == C_DT ? 1.0 / m : 0.0;      // hs = dt / m
+  if (FORM == 1) {
+    z[IA] = 0.5 * d.aub * (u + 1.0); z[IW] = 0.0;
+    dz[IA] = col == C_U ? 0.5 * d.aub : col == C_ALPHA ? 0.5 * (u + 1.0) : 0.0;
+    dz[IW] = 0.0;
+  } else {
+    cw = col == C_U ? d.alpha : col == C_ALPHA ? u : 0.0;
+  }
+  for (int j = 0; j < m; j++) {
+    double k1[7], k2[7], k3[7], k4[7], w[7], d1[7], d2[7], d3[7], d4[7], dw[7];
+    stage<FORM>(d, z, dz, u, col, cw, cm, k1, d1);
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) { w[i] = z[i] + 0.5 * hs * k1[i]; dw[i] = dz[i] + 0.5 * (hs * d1[i] + dhs * k1[i]); }
+    stage<FORM>(d, w, dw, u, col, cw, cm, k2, d2);
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) { w[i] = z[i] + 0.5 * hs * k2[i]; dw[i] = dz[i] + 0.5 * (hs * d2[i] + dhs * k2[i]); }
+    stage<FORM>(d, w, dw, u, col, cw, cm, k3, d3);
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) { w[i] = z[i] + hs * k3[i]; dw[i] = dz[i] + (hs * d3[i] + dhs * k3[i]); }
+    stage<FORM>(d, w, dw, u, col, cw, cm, k4, d4);
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) {
+      const double ks = k1[i] + 2.0 * (k2[i] + k3[i]) + k4[i], ds = d1[i] + 2.0 * (d2[i] + d3[i]) + d4[i];
+      z[i] += hs * (1.0 / 6.0) * ks;
+      dz[i] += (1.0 / 6.0) * (hs * ds + dhs * ks);
+    }
+  }
+}
+
+// Gradients of apsides_of's periapsis / apoapsis altitude with respect to (X, Y, VX, VY, GM) in SI units at a scaled state;
+// returns false where the specific energy is >= 0 (the apoapsis gradient is then NaN).  From E = v^2/2 - GM/r, h = X VY - Y VX,
+// e^2 = 1 + 2 E h^2 / GM^2, a = -GM / (2 E): periapsis a (1 - e), apoapsis a (1 + e); E >= 0: periapsis h^2 / (GM (1 + e)).
+ASC_DEV bool apsides_grad(const ascent_params &prm, double x, double y, double vx, double vy, double *gp, double *ga) {
+  const double S = prm.r_peri, GM = prm.G * prm.M;
+  const double X = x * S, Y = y * S + prm.R0, VX = vx * S, VY = vy * S;
+  const double r = sqrt(X * X + Y * Y), v2 = VX * VX + VY * VY;
+  const double E = 0.5 * v2 - GM / r, h = X * VY - Y * VX;
+  const double e = sqrt(1.0 + 2.0 * E * h * h / (GM * GM));
+  const double ir3 = 1.0 / (r * r * r);
+  const double dE[5] = {GM * X * ir3, GM * Y * ir3, VX, VY, -1.0 / r};
+  const double dh[5] = {VY, -VX, -Y, X, 0.0};
+  double de[5];
+  ASC_UNROLL
+  for (int i = 0; i < 5; i++) de[i] = (h * h * dE[i] + 2.0 * E * h * dh[i]) / (GM * GM * e);
+  de[4] -= 2.0 * E * h * h / (GM * GM * GM * e);
+  if (E >= 0.0) {
+    const double q = 1.0 / (GM * (1.0 + e));
+    ASC_UNROLL
+    for (int i = 0; i < 5; i++) { gp[i] = 2.0 * h * q * dh[i] - h * h * q / (1.0 + e) * de[i]; ga[i] = NAN; }
+    gp[4] -= h * h * q / GM;
+    return false;
+  }
+  const double a = -GM / (2.0 * E);
+  double da[5];
+  ASC_UNROLL
+  for (int i = 0; i < 5; i++) da[i] = GM / (2.0 * E * E) * dE[i];
+  da[4] -= 1.0 / (2.0 * E);
+  ASC_UNROLL
+  for (int i = 0; i < 5; i++) { gp[i] = (1.0 - e) * da[i] - a * de[i]; ga[i] = (1.0 + e) * da[i] + a * de[i]; }
+  return true;
+}
+
+template <int FORM>
+__global__ __launch_bounds__(JB) void j_jac(const ascent_params *__restrict__ P, long batch, int K, int substeps,
+                                            const double *__restrict__ blob, const double *__restrict__ traj,
+                                            const double *__restrict__ skip, double *__restrict__ jac, double *__restrict__ jac_u) {
+  __shared__ double rec[CH * REC];
+  const long p = blockIdx.x;
+  const size_t B = (size_t)batch;
+  if (skip && skip[p] != 0.0) return;         // a frozen problem of the trim (uniform over the workgroup)
+  const int t = threadIdx.x, g = t >> 4, col = t & (NCOL - 1);
+  const int nt = K + 1;
+  const double *b = blob + p, *tr = traj + p;
+  const ascent_params prm = P[p];
+  const Der d = derive(prm);
+  const double tf = b[(size_t)(21 * K + S_TH) * B];
+  const double dt = (tf * d.T) / K;
+  const int m = flight_substeps(dt, substeps);
+  const double hs = dt / m;
+
+  // the sweep's state, wave 0: lane q holds row q of Lambda, its accumulators and (rows 7, 8) the direct parameter terms
+  double L[7], A[NACC], dirG = 0.0, dirM = 0.0, dirR0 = 0.0, dirS = 0.0;
+  ASC_UNROLL
+  for (int i = 0; i < 7; i++) L[i] = t == i ? 1.0 : 0.0;
+  ASC_UNROLL
+  for (int a = 0; a < NACC; a++) A[a] = 0.0;
+  if (t < TW) {
+    double zK[7], gp[5], ga[5];
+    load_node(tr, B, nt, K, zK);
+    apsides_grad(prm, zK[IX], zK[IY], zK[IVX], zK[IVY], gp, ga);
+    if (t == 7 || t == 8) {
+      const double *gq = t == 7 ? gp : ga;
+      const double S = prm.r_peri;
+      L[IX] = S * gq[0]; L[IY] = S * gq[1]; L[IVX] = S * gq[2]; L[IVY] = S * gq[3];
+      dirS = zK[IX] * gq[0] + zK[IY] * gq[1] + zK[IVX] * gq[2] + zK[IVY] * gq[3];
+      dirR0 = gq[1] - 1.0;
+      dirG = prm.M * gq[4];
+      dirM = prm.G * gq[4];
+    }
+  }
+
+  const int nch = (K + CH - 1) / CH;
+  for (int c = nch - 1; c >= 0; c--) {
+    const int k = c * CH + g + 1;             // this group's step: node k-1 -> k
+    if (k <= K) {
+      double z[7], dz[7];
+      load_node(tr, B, nt, k - 1, z);
+      const double u = b[(size_t)(7 * K + k - 1) * B];
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) dz[i] = col == i ? 1.0 : 0.0;
+      fly_step_tangent<FORM>(d, z, dz, u, hs, m, col);
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) rec[g * REC + i * NCOL + col] = dz[i];
+    }
+    __syncthreads();
+    if (t < TW) {
+      const int top = K - c * CH < CH ? K - c * CH : CH;
+      for (int s = top - 1; s >= 0; s--) {
+        const double *R = rec + s * REC;
+        double o[NCOL];
+        ASC_UNROLL
+        for (int cc = 0; cc < NCOL; cc++) {
+          double a = 0.0;
+          ASC_UNROLL
+          for (int i = 0; i < 7; i++) a += L[i] * R[i * NCOL + cc];
+          o[cc] = a;
+        }
+        if (jac_u && t < JROWS) jac_u[((size_t)t * K + (c * CH + s)) * B + p] = o[C_U];
+        ASC_UNROLL
+        for (int a = 0; a < NACC; a++) A[a] += o[C_DT + a];
+        ASC_UNROLL
+        for (int i = 0; i < 7; i++) L[i] = o[i];
+      }
+    }
+    __syncthreads();
+  }
+
+  if (t < JROWS) {
+    const double S = prm.r_peri, R0 = prm.R0;
+    const double aDT = A[0], aRHO0 = A[1 + ACC_RHO0], aGAM = A[1 + ACC_GAM], aTHR = A[1 + ACC_THR], aM0 = A[1 + ACC_M0],
+                 aMS = A[1 + ACC_MS], aAL = A[C_ALPHA - C_DT], aMR = A[C_MRATE - C_DT];
+    double o[JCOLS];
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) o[i] = L[i];
+    const double S3 = S * S * S;
+    o[7 + 0] = aGAM * prm.M / S3 + dirG;                              // G
+    o[7 + 1] = aGAM * prm.G / S3 + dirM;                              // M
+    o[7 + 2] = aRHO0 / S + dirR0;                                     // R0
+    o[7 + 3] = aTHR / S;                                              // Ft
+    o[7 + 4] = aM0;                                                   // M0
+    o[7 + 5] = aMR / prm.fuel_mass;                                   // mdot
+    o[7 + 6] = -aMR * d.mrate / prm.fuel_mass;                        // fuel_mass
+    o[7 + 7] = aMS;                                                   // mass_scalar
+    o[7 + 8] = FORM == 1 ? 0.0 : aAL / 3.0;                           // ang_acc_max
+    o[7 + 9] = -aRHO0 * R0 / (S * S) - 3.0 * aGAM * d.gam / S - aTHR * d.thr / S + dirS;     // r_peri
+    o[7 + 10] = 0.0;                                                  // r_apo
+    o[7 + 11] = aDT * (tf / K);                                       // T_scale
+    o[7 + 12] = FORM == 1 ? aAL : 0.0;                                // angle_ub
+    o[7 + 13] = 0.0; o[7 + 14] = 0.0; o[7 + 15] = 0.0;                // tf_lb, tf_ub, dcost
+    o[23] = aDT * (d.T / K);                                          // t_f
+    ASC_UNROLL
+    for (int cc = 0; cc < JCOLS; cc++) jac[((size_t)t * JCOLS + cc) * B + p] = o[cc];
+  }
+}
+
+ASC_DEV double wave_sum(double v) {          // butterfly: every lane ends with the same bits
+  ASC_UNROLL
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+ASC_DEV double max_nan2(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
+ASC_DEV double wave_max_nan(double v) {
+  ASC_UNROLL
+  for (int off = 32; off >= 1; off >>= 1) v = max_nan2(v, __shfl_xor(v, off));
+  return v;
+}
+ASC_DEV bool finite3(double a, double b, double c) {
+  const double big = 1.79769313486231570815e308;
+  return fabs(a) <= big && fabs(b) <= big && fabs(c) <= big;
+}
+
+// one round of the trim: after f_fly and j_jac of the current control
+__global__ __launch_bounds__(TW) void t_update(const ascent_params *__restrict__ P, long batch, int K, int terminal, double tol,
+                                               int first, double *__restrict__ blob, const double *__restrict__ traj,
+                                               const double *__restrict__ jac, const double *__restrict__ jac_u,
+                                               double *__restrict__ st) {
+  const long p = blockIdx.x;
+  const size_t B = (size_t)batch;
+  const int lane = threadIdx.x, nt = K + 1;
+  if (st[(size_t)ST_FLAG * B + p] != 0.0) return;
+  double *b = blob + p;
+  const Der d = derive_t(P[p], terminal);
+  double zK[7];
+  load_node(traj + p, B, nt, K, zK);
+  const Terminal tm = terminal_eval(d, zK);
+  const double c[3] = {tm.e3, tm.g1, tm.g2};
+  const bool fin = finite3(c[0], c[1], c[2]);
+  const double cn = fin ? fmax(fabs(c[0]), fmax(fabs(c[1]), fabs(c[2]))) : NAN;
+  double nf = 0.0;
+  for (int k = lane; k < K; k += TW) nf += fabs(b[(size_t)(7 * K + k) * B]) < 0.999 ? 1.0 : 0.0;
+  nf = wave_sum(nf);
+  if (lane == 0) {
+    if (first) st[(size_t)ST_C0 * B + p] = cn;
+    st[(size_t)ST_NFREE * B + p] = nf;
+  }
+  if (!fin) { if (lane == 0) st[(size_t)ST_FLAG * B + p] = 2.0; return; }
+  if (cn <= tol) { if (lane == 0) st[(size_t)ST_FLAG * B + p] = 1.0; return; }
+  // grad c (3 x 4 on x, y, xdot, ydot)
+  const double gc[3][4] = {{tm.e3g[0], tm.e3g[1], tm.e3g[2], tm.e3g[3]}, {tm.g1g[0], tm.g1g[1], 0.0, 0.0}, {0.0, 0.0, tm.g2g[0], tm.g2g[1]}};
+  double at[3];
+  {
+    double j[4];
+    ASC_UNROLL
+    for (int q = 0; q < 4; q++) j[q] = jac[((size_t)q * JCOLS + 23) * B + p];
+    ASC_UNROLL
+    for (int r = 0; r < 3; r++) at[r] = gc[r][0] * j[0] + gc[r][1] * j[1] + gc[r][2] * j[2] + gc[r][3] * j[3];
+  }
+  double n[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};       // 11 12 13 22 23 33
+  for (int k = lane; k < K; k += TW) {
+    if (!(fabs(b[(size_t)(7 * K + k) * B]) < 0.999)) continue;
+    double j[4], a[3];
+    ASC_UNROLL
+    for (int q = 0; q < 4; q++) j[q] = jac_u[((size_t)q * K + k) * B + p];
+    ASC_UNROLL
+    for (int r = 0; r < 3; r++) a[r] = gc[r][0] * j[0] + gc[r][1] * j[1] + gc[r][2] * j[2] + gc[r][3] * j[3];
+    n[0] += a[0] * a[0]; n[1] += a[0] * a[1]; n[2] += a[0] * a[2];
+    n[3] += a[1] * a[1]; n[4] += a[1] * a[2]; n[5] += a[2] * a[2];
+  }
+  ASC_UNROLL
+  for (int i = 0; i < 6; i++) n[i] = wave_sum(n[i]);
+  n[0] += at[0] * at[0]; n[1] += at[0] * at[1]; n[2] += at[0] * at[2];
+  n[3] += at[1] * at[1]; n[4] += at[1] * at[2]; n[5] += at[2] * at[2];
+  // (A W A') y = c by L D L' without pivoting (the matrix is symmetric positive definite or the problem is frozen)
+  const double d1 = n[0];
+  bool ok = d1 > 1e-300;
+  const double l21 = n[1] / d1, l31 = n[2] / d1;
+  const double d2 = n[3] - l21 * n[1];
+  ok = ok && d2 > 1e-300;
+  const double s32 = n[4] - l21 * n[2], l32 = s32 / d2;
+  const double d3 = n[5] - l31 * n[2] - l32 * s32;
+  ok = ok && d3 > 1e-300;
+  const double w1 = c[0], w2 = c[1] - l21 * w1, w3 = c[2] - l31 * w1 - l32 * w2;
+  const double y3 = w3 / d3, y2 = w2 / d2 - l32 * y3, y1 = w1 / d1 - l21 * y2 - l31 * y3;
+  if (!ok || !finite3(y1, y2, y3)) { if (lane == 0) st[(size_t)ST_FLAG * B + p] = 2.0; return; }
+  for (int k = lane; k < K; k += TW) {
+    const double u = b[(size_t)(7 * K + k) * B];
+    if (!(fabs(u) < 0.999)) continue;
+    double j[4], a[3];
+    ASC_UNROLL
+    for (int q = 0; q < 4; q++) j[q] = jac_u[((size_t)q * K + k) * B + p];
+    ASC_UNROLL
+    for (int r = 0; r < 3; r++) a[r] = gc[r][0] * j[0] + gc[r][1] * j[1] + gc[r][2] * j[2] + gc[r][3] * j[3];
+    const double un = u - (a[0] * y1 + a[1] * y2 + a[2] * y3);
+    b[(size_t)(7 * K + k) * B] = fmin(1.0, fmax(-1.0, un));
+  }
+  if (lane == 0) {
+    b[(size_t)(21 * K + S_TH) * B] -= at[0] * y1 + at[1] * y2 + at[2] * y3;
+    st[(size_t)ST_ROUNDS * B + p] += 1.0;
+  }
+}
+
+// after the last fly-out: the flown states into the trimmed blob, and the summary rows
+__global__ __launch_bounds__(TW) void t_final(const ascent_params *__restrict__ P, long batch, int K, int terminal, double tol,
+                                              const double *__restrict__ blob_in, double *__restrict__ blob,
+                                              const double *__restrict__ traj, const double *__restrict__ st,
+                                              double *__restrict__ summary) {
+  const long p = blockIdx.x;
+  const size_t B = (size_t)batch;
+  const int lane = threadIdx.x, nt = K + 1;
+  double *b = blob + p;
+  const double *bi = blob_in + p, *tr = traj + p;
+  const ascent_params prm = P[p];
+  const Der d = derive_t(prm, terminal);
+  double du = 0.0, viol = 0.0;
+  for (int k = lane; k < K; k += TW) {
+    double z[7];
+    load_node(tr, B, nt, k + 1, z);
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) b[(size_t)(7 * k + i) * B] = z[i];
+    du = fmax(du, fabs(b[(size_t)(7 * K + k) * B] - bi[(size_t)(7 * K + k) * B]));
+    viol = max_nan2(viol, fmax(-z[IA], z[IA] - d.aub));
+  }
+  du = wave_max_nan(du);
+  viol = wave_max_nan(viol);
+  if (lane != 0) return;
+  double zK[7];
+  load_node(tr, B, nt, K, zK);
+  const Terminal tm = terminal_eval(d, zK);
+  const bool fin = finite3(tm.e3, tm.g1, tm.g2);
+  const double cn = fin ? fmax(fabs(tm.e3), fmax(fabs(tm.g1), fabs(tm.g2))) : NAN;
+  const double flag = st[(size_t)ST_FLAG * B + p];
+  double peri, apo;
+  apsides_of(prm, zK[IX], zK[IY], zK[IVX], zK[IVY], peri, apo);
+  summary[(size_t)0 * B + p] = (flag == 2.0 || !fin) ? 2.0 : cn <= tol ? 0.0 : 1.0;
+  summary[(size_t)1 * B + p] = st[(size_t)ST_ROUNDS * B + p];
+  summary[(size_t)2 * B + p] = cn;
+  summary[(size_t)3 * B + p] = st[(size_t)ST_C0 * B + p];
+  summary[(size_t)4 * B + p] = (b[(size_t)(21 * K + S_TH) * B] - bi[(size_t)(21 * K + S_TH) * B]) * d.T;
+  summary[(size_t)5 * B + p] = du;
+  summary[(size_t)6 * B + p] = st[(size_t)ST_NFREE * B + p];
+  summary[(size_t)7 * B + p] = peri;
+  summary[(size_t)8 * B + p] = apo;
+  summary[(size_t)9 * B + p] = viol;
+}
+
+struct TrimWs { double *traj, *fsum, *jac, *jac_u, *st; };
+TrimWs carve(double *ws, int K, long batch) {
+  TrimWs w;
+  const size_t B = (size_t)batch;
+  w.traj = ws;
+  w.fsum = w.traj + (size_t)ASCENT_TRAJ_FIELDS * (K + 1) * B;
+  w.jac = w.fsum + (size_t)ASCENT_FLIGHT_ROWS * B;
+  w.jac_u = w.jac + (size_t)JROWS * JCOLS * B;
+  w.st = w.jac_u + (size_t)JROWS * K * B;
+  return w;
+}
+
+}  // namespace
+
+#define TCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #call, hipGetErrorString(e_)); return ASCENT_E_HIP; } } while (0)
+
+size_t jac_ws_bytes(int K, long batch) {
+  return ((size_t)ASCENT_TRAJ_FIELDS * (K + 1) + ASCENT_FLIGHT_ROWS) * (size_t)batch * sizeof(double);
+}
+size_t trim_ws_bytes(int K, long batch) {
+  return jac_ws_bytes(K, batch) + ((size_t)JROWS * JCOLS + (size_t)JROWS * K + ST_ROWS) * (size_t)batch * sizeof(double);
+}
+
+static int jac_launch(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob,
+                      const double *dtraj, const double *dskip, double *djac, double *djac_u, hipStream_t stream, char *err,
+                      size_t errlen) {
+  const dim3 grid((unsigned)batch), block(JB);
+  if (formulation == 1)
+    hipLaunchKernelGGL((j_jac<1>), grid, block, 0, stream, dp, batch, K, substeps, dblob, dtraj, dskip, djac, djac_u);
+  else
+    hipLaunchKernelGGL((j_jac<0>), grid, block, 0, stream, dp, batch, K, substeps, dblob, dtraj, dskip, djac, djac_u);
+  TCHK(hipGetLastError());
+  return ASCENT_OK;
+}
+
+int jac_run(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *djac,
+            double *djac_u, double *ws, hipStream_t stream, char *err, size_t errlen) {
+  const TrimWs w = carve(ws, K, batch);
+  if (const int rc = flight_fly_only(dp, batch, K, formulation, substeps, dblob, w.traj, w.fsum, stream, err, errlen)) return rc;
+  return jac_launch(dp, batch, K, formulation, substeps, dblob, w.traj, nullptr, djac, djac_u, stream, err, errlen);
+}
+
+int trim_run(const ascent_params *dp, long batch, int K, int formulation, int terminal, int substeps, int rounds, double tol,
+             const double *dblob, double *dblob_out, double *dsummary, double *ws, hipStream_t stream, char *err, size_t errlen) {
+  const TrimWs w = carve(ws, K, batch);
+  const size_t B = (size_t)batch;
+  TCHK(hipMemcpyAsync(dblob_out, dblob, (21 * (size_t)K + NSC) * B * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  TCHK(hipMemsetAsync(w.st, 0, (size_t)ST_ROWS * B * sizeof(double), stream));
+  const dim3 grid((unsigned)batch), block(TW);
+  for (int r = 0; r < rounds; r++) {
+    if (const int rc = flight_fly_only(dp, batch, K, formulation, substeps, dblob_out, w.traj, w.fsum, stream, err, errlen)) return rc;
+    if (const int rc = jac_launch(dp, batch, K, formulation, substeps, dblob_out, w.traj, w.st, w.jac, w.jac_u, stream, err, errlen)) return rc;
+    hipLaunchKernelGGL(t_update, grid, block, 0, stream, dp, batch, K, terminal, tol, r == 0 ? 1 : 0, dblob_out, w.traj, w.jac, w.jac_u, w.st);
+    TCHK(hipGetLastError());
+  }
+  if (const int rc = flight_fly_only(dp, batch, K, formulation, substeps, dblob_out, w.traj, w.fsum, stream, err, errlen)) return rc;
+  hipLaunchKernelGGL(t_final, grid, block, 0, stream, dp, batch, K, terminal, tol, dblob, dblob_out, w.traj, w.st, dsummary);
+  TCHK(hipGetLastError());
+  return ASCENT_OK;
+}
+
+}  // namespace ascent

@@ -57,6 +57,78 @@ for _i, _n in enumerate(FLIGHT_ROWS):   # the summary columns by name: .miss_pos
     setattr(FlightResult, _n, property(lambda self, _i=_i: self.summary[:, _i]))
 
 
+JACOBIAN_ROWS = ("x", "y", "xdot", "ydot", "angle", "angledot", "mass", "periapsis_alt", "apoapsis_alt")
+TRIM_ROWS = ("status", "rounds", "residual", "residual_before", "delta_tf_seconds", "max_delta_u", "free_controls",
+             "flown_periapsis_alt", "flown_apoapsis_alt", "angle_violation")
+TRIM_STATUS_NAMES = {0: "converged", 1: "rounds_exhausted", 2: "frozen"}
+
+
+@dataclasses.dataclass
+class FlightJacobian:
+    """Derivative of what a blob's control reaches when it is flown (flight_jacobian; include/ascent.h:
+    ascent_flight_jacobian).  Rows JACOBIAN_ROWS: the flown z_K in scaled units, then the flown periapsis / apoapsis altitude
+    in metres.  Problem index first."""
+    dz0: np.ndarray                 # (batch, 9, 7) with respect to the initial state, scaled units
+    dparams: np.ndarray             # (batch, 9, 16) per SI unit of every parameter field (PARAM_FIELDS order), blob held fixed
+    dtf: np.ndarray                 # (batch, 9) with respect to the scaled t_f
+    dcontrols: np.ndarray | None    # (batch, 9, K) column k-1: with respect to u_k
+
+    def predict(self, dparams=None, dtf=None, dcontrols=None, dz0=None) -> np.ndarray:
+        """(batch, 9) first-order change of the nine end quantities under the given changes: dparams (16,) or (batch, 16) in
+        SI units, dtf scalar or (batch,) scaled, dcontrols (K,) or (batch, K), dz0 (7,) or (batch, 7); each may be None."""
+        out = np.zeros(self.dtf.shape)
+        if dparams is not None:
+            out += np.einsum("bqc,bc->bq", self.dparams, np.broadcast_to(np.asarray(dparams, dtype=np.float64), self.dparams[:, 0].shape))
+        if dtf is not None:
+            out += self.dtf * np.broadcast_to(np.asarray(dtf, dtype=np.float64), self.dtf.shape[:1])[:, None]
+        if dcontrols is not None:
+            if self.dcontrols is None:
+                raise ValueError("this FlightJacobian was computed without the control columns")
+            out += np.einsum("bqk,bk->bq", self.dcontrols, np.broadcast_to(np.asarray(dcontrols, dtype=np.float64), self.dcontrols[:, 0].shape))
+        if dz0 is not None:
+            out += np.einsum("bqc,bc->bq", self.dz0, np.broadcast_to(np.asarray(dz0, dtype=np.float64), self.dz0[:, 0].shape))
+        return out
+
+    def sigma(self, param_sigma=None, control_sigma=None) -> np.ndarray:
+        """(batch, 9) root-sum-square 1-sigma of every row for independent errors: param_sigma (16,) or (batch, 16) the
+        standard deviation of every parameter field in SI units, control_sigma a scalar, (K,) or (batch, K) per-step standard
+        deviation of u."""
+        var = np.zeros(self.dtf.shape)
+        if param_sigma is not None:
+            var += ((self.dparams * np.broadcast_to(np.asarray(param_sigma, dtype=np.float64), self.dparams[:, 0].shape)[:, None, :]) ** 2).sum(axis=2)
+        if control_sigma is not None:
+            if self.dcontrols is None:
+                raise ValueError("this FlightJacobian was computed without the control columns")
+            var += ((self.dcontrols * np.broadcast_to(np.asarray(control_sigma, dtype=np.float64), self.dcontrols[:, 0].shape)[:, None, :]) ** 2).sum(axis=2)
+        return np.sqrt(var)
+
+
+@dataclasses.dataclass
+class TrimResult:
+    """A batch of trimmed solutions (trim_batch; include/ascent.h: ascent_trim_batch)."""
+    blob: np.ndarray       # (21K+10, batch) the trimmed blob: u, t_f and the flown states replaced; multipliers stale
+    summary: np.ndarray    # (batch, 10) columns TRIM_ROWS
+    nt: int
+
+    @property
+    def tf(self) -> np.ndarray:
+        return self.blob[21 * (self.nt - 1)]
+
+    @property
+    def controls(self) -> np.ndarray:
+        """(batch, K)"""
+        K = self.nt - 1
+        return np.ascontiguousarray(self.blob[7 * K:8 * K].T)
+
+    @property
+    def converged(self) -> np.ndarray:
+        return self.summary[:, 0] == 0
+
+
+for _i, _n in enumerate(TRIM_ROWS):     # the summary columns by name: .status, .rounds, .residual, ... -> (batch,)
+    setattr(TrimResult, _n, property(lambda self, _i=_i: self.summary[:, _i]))
+
+
 @dataclasses.dataclass
 class BatchResult:
     """Solutions of a batch. Arrays keep the library's layout: problem index last."""
@@ -70,6 +142,7 @@ class BatchResult:
     kernel_ms: float            # device time of the solve kernel
     sensitivity: np.ndarray | None = None   # (batch, 16) d(T_scale J*)/dp, s per SI unit (solve_batch(sensitivity=True))
     flight: FlightResult | None = None      # the solutions' controls flown with RK4 (solve_batch(flight=True))
+    trim: TrimResult | None = None          # the solutions trimmed so that the flown control reaches the orbit (solve_batch(trim=True))
 
     @property
     def converged(self) -> np.ndarray:
@@ -143,7 +216,8 @@ class BatchResult:
 def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, guess: np.ndarray | None = None,
                 warm_start: int | None = None, mu_init: float = 0.0, device: int = 0, want_traj: bool = True,
                 want_blob: bool = False, scheme=0, formulation=0, coarse_nodes: int = 0, terminal=0,
-                path: str = "auto", move_penalty: bool = False, sensitivity: bool = False, flight: bool = False) -> BatchResult:
+                path: str = "auto", move_penalty: bool = False, sensitivity: bool = False, flight: bool = False,
+                trim: bool = False) -> BatchResult:
     """Solve a batch of ascent NLPs on one GPU.  params: AscentParams | list | (batch,16) array.
     guess: (21K+10, batch) blob, with warm_start 1 (primal only) or 2 (primal-dual).
     scheme: 0 / "backward_euler" (the reference's NODES=2), 1 / "trapezoid" or 2 / "hermite_simpson" (both with the
@@ -163,7 +237,10 @@ def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, g
     converge are NaN.  Without the move penalty this is d t_f*/dp; with it, the penalised objective in seconds.
     flight: also set `BatchResult.flight`, a FlightResult: every solution's control flown with RK4 on the device (fly_batch,
     automatic substeps) -- the flown trajectory, the local error of every step and the miss at burnout; rows of problems that
-    did not converge are NaN."""
+    did not converge are NaN.
+    trim: also set `BatchResult.trim`, a TrimResult: (t_f, u) of every solution corrected so that the flown control meets the
+    terminal conditions (trim_batch with its defaults; terminal 0 / 1 only); problems that did not converge are trimmed from
+    whatever their blob holds and usually end with status 2."""
     L = _lib.load()
     P = pack(params)
     B = P.shape[0]
@@ -176,7 +253,7 @@ def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, g
             warm_start = 1
     warm_start = warm_start or 0
     traj = np.empty((10, nt, B)) if want_traj else None
-    blob = np.empty((rows, B)) if (want_blob or sensitivity or flight) else None
+    blob = np.empty((rows, B)) if (want_blob or sensitivity or flight or trim) else None
     tf = np.empty(B)
     status = np.empty(B, dtype=np.int32)
     iters = np.empty(B, dtype=np.int32)
@@ -196,7 +273,11 @@ def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, g
                        device=device)
         for a in (fl.traj, fl.local_error, fl.summary):
             a[status != 0] = np.nan
-    return BatchResult(P, nt, traj, tf, status, iters, blob if want_blob else None, kms, sens, fl)
+    tr = None
+    if trim:
+        tr = trim_batch(P, blob, nt, scheme=scheme, formulation=formulation, terminal=terminal, move_penalty=move_penalty,
+                        device=device)
+    return BatchResult(P, nt, traj, tf, status, iters, blob if want_blob else None, kms, sens, fl, tr)
 
 
 def _penalty_weight(P, formulation):
@@ -266,6 +347,47 @@ def fly_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, te
     return FlightResult(None if traj is None else np.ascontiguousarray(traj.transpose(2, 0, 1)),
                         None if local is None else np.ascontiguousarray(local.transpose(2, 0, 1)),
                         np.ascontiguousarray(summ.T))
+
+
+def flight_jacobian(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,
+                    substeps: int = 0, device: int = 0, want_controls: bool = True) -> FlightJacobian:
+    """Flight Jacobian (include/ascent.h: ascent_flight_jacobian): the exact derivative of the discrete RK4 flight of fly_batch
+    -- the flown last state (scaled) and the flown periapsis / apoapsis altitude (m) -- with respect to the initial state, the
+    16 parameter fields (blob held fixed), t_f and every control u_k, at the blob (21K+10, batch).  The open-loop counterpart
+    of param_sensitivity: what a dispersed vehicle does under the nominal control.  terminal 2 is refused."""
+    P = pack(params)
+    B, K = P.shape[0], nt - 1
+    blob = np.ascontiguousarray(sol_blob, dtype=np.float64)
+    if blob.shape != (blob_rows(nt), B):
+        raise ValueError(f"sol_blob must have shape {(blob_rows(nt), B)}")
+    L = _lib.load()
+    jac = np.empty((9, 24, B))
+    ju = np.empty((9, K, B)) if want_controls else None
+    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
+    _lib.check(L.ascent_flight_jacobian(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(jac), _ptr(ju), device, None, 0))
+    j = jac.transpose(2, 0, 1)
+    return FlightJacobian(np.ascontiguousarray(j[:, :, :7]), np.ascontiguousarray(j[:, :, 7:23]), np.ascontiguousarray(j[:, :, 23]),
+                          None if ju is None else np.ascontiguousarray(ju.transpose(2, 0, 1)))
+
+
+def trim_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,
+               substeps: int = 0, rounds: int = 0, tol: float = 0.0, device: int = 0) -> TrimResult:
+    """Trim (include/ascent.h: ascent_trim_batch): least-norm Newton corrections of (t_f, u) of every blob that drive the
+    flown terminal conditions to zero, saturated controls (|u_k| >= 0.999) kept where they are; `rounds` rounds (0: 6) to
+    `tol` (0: 1e-10) entirely on the device.  Returns a TrimResult: the trimmed blob (states = the flown states of the trimmed
+    control; multipliers stale) and the summary (TRIM_ROWS).  terminal 2 is refused."""
+    P = pack(params)
+    B = P.shape[0]
+    blob = np.ascontiguousarray(sol_blob, dtype=np.float64)
+    if blob.shape != (blob_rows(nt), B):
+        raise ValueError(f"sol_blob must have shape {(blob_rows(nt), B)}")
+    L = _lib.load()
+    out = np.empty_like(blob)
+    summ = np.empty((len(TRIM_ROWS), B))
+    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
+    _lib.check(L.ascent_trim_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), int(rounds), float(tol), _ptr(out), _ptr(summ),
+                                   device, None, 0))
+    return TrimResult(out, np.ascontiguousarray(summ.T), nt)
 
 
 def eval_nodes(params, iterate: np.ndarray, nt: int = 200, device: int = 0, path="auto", scheme=0, formulation=0):
