@@ -220,9 +220,21 @@ int ascent_dense_records(const ascent_params *p, int64_t batch, const ascent_opt
  * explicit Euler, PDF p28-29): Kepler-exact two-body propagation of every problem's final state to the next
  * apoapsis of its orbit, sampled uniformly in time.
  * final_state [4][batch]: scaled x, y, xdot, ydot of the last node (rows 0..3 of traj_out at node n_nodes-1);
- * coast_traj [4][coast_nodes+1][batch] (same scaled units; node 0 = the burnout state);
- * coast_tf [batch]: coast duration / T_scale;  apsides [2][batch]: periapsis and apoapsis altitude above R0, m.
- * Host or device pointers (ptr_is_device), optional stream. */
+ * coast_traj [4][coast_nodes+1][batch] (same scaled units), coast_nodes 1 .. 65535; node j is the state after
+ *   j * coast_tf * T_scale / coast_nodes seconds.  Node 0 is the input state, bit for bit: the arc is propagated from the
+ *   burnout state itself (Kepler's equation in the difference of the eccentric anomaly, Lagrange's f and g coefficients), with
+ *   e cos E0 = 1 - r/a and e sin E0 = r.v / sqrt(GM a) used as they are -- nothing is divided by the eccentricity, so the arc is
+ *   continuous through e -> 0 and there is no near-circular switch;
+ * coast_tf [batch]: coast duration / T_scale = (pi - M0) / n with M0 = E0 - e sin E0, E0 = atan2(e sin E0, e cos E0) in
+ *   (-pi, pi]: 0 <= duration < one period.  Near the circle E0, and with it the duration, is as ill-determined as the place of
+ *   the apsides themselves (an input rounding moves it by about eps / e); where e sin E0 and e cos E0 are both exactly 0 the
+ *   duration is half a period;
+ * apsides [2][batch]: periapsis and apoapsis altitude above R0, m: the one definition of the library (also rows 2..5 of
+ *   ascent_fly_batch): e = |eccentricity vector|, periapsis h^2 / (GM (1 + e)) - R0, apoapsis a (1 + e) - R0 with the semi-major
+ *   axis from the vis-viva equation.
+ * Specific energy >= 0 (parabolic or faster) is not an error: the call returns ASCENT_OK, that problem's coast_traj and coast_tf
+ *   are NaN, its periapsis is the same expression and its apoapsis +inf; the other problems of the batch are not affected.
+ * Host or device pointers (ptr_is_device), optional stream (device pointers and a stream: one kernel is enqueued). */
 int ascent_coast_batch(const ascent_params *p, int64_t batch, const double *final_state, int32_t coast_nodes,
                        double *coast_traj, double *coast_tf, double *apsides, int device_id,
                        void *hip_stream_or_null, int ptr_is_device);
@@ -261,7 +273,7 @@ int ascent_param_sensitivity(const ascent_params *p, int64_t batch, const ascent
  * summary_out [ASCENT_FLIGHT_ROWS][batch], SI units:
  *   0 position miss |flown - NLP| at the last node (m)        1 velocity miss (m/s)
  *   2 / 3 periapsis / apoapsis altitude above R0 of the flown burnout orbit (m)    4 / 5 the same for the NLP's last node
- *         (two-body formulas of ascent_coast_batch; specific energy >= 0 gives apoapsis +inf)
+ *         (the same function as ascent_coast_batch's apsides, bit for bit; specific energy >= 0 gives apoapsis +inf)
  *   6 max over steps of the local position error |eta_k(x, y)| (m)      7 of the local velocity error (m/s)
  *   8 the step k (1-based) where row 6 is attained         9 the m used
  * Options: refuses (ASCENT_E_ARG) exactly what ascent_solve_batch refuses for these options and this batch; max_iter, tol,
@@ -285,6 +297,9 @@ int ascent_fly_batch(const ascent_params *p, int64_t batch, const ascent_opts *o
  * agrees with finite differences of ascent_fly_batch to their truncation error.
  * Rows q (9): 0..6 the flown z_K in scaled units (x y xdot ydot angle angledot mass); 7 / 8 the flown periapsis / apoapsis
  *   altitude in metres (summary rows 2 / 3 of ascent_fly_batch); row 8 is NaN where the flown specific energy is >= 0.
+ *   The eccentricity and its derivative come from the eccentricity vector (relative error about eps / e).  On an exactly
+ *   circular flown orbit (e = 0) the apsides have a kink and no derivative: rows 7 and 8 are then both the gradient of a - R0
+ *   (the mean of the one-sided derivatives; finite); row 7 + row 8 is the gradient of 2 a - 2 R0 at every e.
  * jac_out [9][24][batch], element (q, c, problem) at jac_out[(q*24 + c)*batch + problem]: columns 0..6 the initial state z_0
  *   (zero in every blob; scaled units), 7..22 the 16 ascent_params fields in declaration order, per SI unit of the field with
  *   the blob held fixed in scaled units, 23 the scaled t_f.  Fields the flight does not read give exact zeros: r_apo, tf_lb,

@@ -32,6 +32,7 @@
 #include "ascent_tile.hpp"
 #include "ascent_dense.hpp"
 #include "ascent_blocktri.hpp"
+#include "ascent_flight_dev.hpp"
 
 using namespace ascent;
 
@@ -1357,6 +1358,13 @@ __global__ __launch_bounds__(WAVE) void d_dump_records(long batch, DGeo g, const
 // to the next apoapsis of its orbit, sampled uniformly in time.  Lane = (NLP, node): every node is an independent
 // solve of Kepler's equation (the explicit-Euler propagator of the reference's v1 script, PDF p28-29, stepped 6.6 million
 // times serially for the same picture).
+// The arc is propagated from the burnout state itself: Kepler's equation in the difference dE of the eccentric anomaly,
+//     dE - (e cos E0) sin dE + (e sin E0)(1 - cos dE) = n t,     e cos E0 = 1 - r0/a,   e sin E0 = r0.v0 / sqrt(GM a),
+// and the Lagrange coefficients f, g, fdot, gdot in dE applied to (r0, v0).  Nothing is divided by e and no perifocal frame is
+// built, so the arc is continuous through e -> 0, and node 0 (t = 0: dE = 0, f = gdot = 1, g = fdot = 0) is the input state
+// bit for bit: the nodes are written as input + (f - 1) r0 + g v0 in scaled units, the offset R0 never subtracted again.
+// Duration: (pi - M0) / n with M0 = E0 - e sin E0, E0 = atan2(e sin E0, e cos E0) in (-pi, pi]; both exactly 0: E0 = 0, half a
+// period.  Specific energy >= 0 (or a NaN state): trajectory and duration NaN, apsides as apsides_of gives them.
 // ==============================================================================================================
 __global__ __launch_bounds__(WAVE) void k_coast(const ascent_params *params, long batch, const double *state4, int nc,
                                                 double *coast, double *theta2, double *apsides) {
@@ -1364,45 +1372,46 @@ __global__ __launch_bounds__(WAVE) void k_coast(const ascent_params *params, lon
   const int jn = blockIdx.y;                  // node 0..nc
   if (p >= batch) return;
   const ascent_params &prm = params[p];
-  const double S = prm.r_peri, GM = prm.G * prm.M;
-  const double X = state4[0 * batch + p] * S, Y = state4[1 * batch + p] * S + prm.R0;
-  const double VX = state4[2 * batch + p] * S, VY = state4[3 * batch + p] * S;
-  const double r = sqrt(X * X + Y * Y), v2 = VX * VX + VY * VY, rv = X * VX + Y * VY;
-  const double a = 1.0 / (2.0 / r - v2 / GM);
-  const double h = X * VY - Y * VX;                     // signed angular momentum (the ascent flies towards -x: h > 0)
-  // eccentricity vector
-  const double ex = (v2 / GM - 1.0 / r) * X - rv / GM * VX, ey = (v2 / GM - 1.0 / r) * Y - rv / GM * VY;
-  const double e = sqrt(ex * ex + ey * ey);
-  const double n = sqrt(GM / (a * a * a));
-  // eccentric anomaly of the burnout state:  r = a(1 - e cos E),  r.v = sqrt(GM a) e sin E
-  const double E0 = e > 1e-12 ? atan2(rv / sqrt(GM * a), 1.0 - r / a) : 0.0;
-  const double M0 = E0 - e * sin(E0);
-  double Mend = M_PI;                                   // apoapsis
-  if (M0 > M_PI) Mend += 2.0 * M_PI;
-  const double T2 = (Mend - M0) / n;
-  const double M = M0 + (Mend - M0) * (double)jn / (double)nc;
-  double E = M + e * sin(M);
-  for (int it = 0; it < 12; it++) E -= (E - e * sin(E) - M) / (1.0 - e * cos(E));
-  // perifocal frame: P along the eccentricity vector, Q = h x P / |h| (90 degrees ahead in the direction of motion)
-  double px = 1.0, py = 0.0;
-  if (e > 1e-12) { px = ex / e; py = ey / e; } else { px = X / r; py = Y / r; }
-  const double sg = h >= 0.0 ? 1.0 : -1.0;
-  const double qx = -sg * py, qy = sg * px;
-  const double cE = cos(E), sE = sin(E), b = a * sqrt(fmax(0.0, 1.0 - e * e));
-  const double xp = a * (cE - e), yp = b * sE;
-  const double rr = a * (1.0 - e * cE);
-  const double vxp = -sqrt(GM * a) / rr * sE, vyp = sqrt(GM * a) / rr * sqrt(fmax(0.0, 1.0 - e * e)) * cE;
-  const double Xn = xp * px + yp * qx, Yn = xp * py + yp * qy, VXn = vxp * px + vyp * qx, VYn = vxp * py + vyp * qy;
+  const double S = prm.r_peri, GM = prm.G * prm.M, rho0 = prm.R0 / S;
+  const double x = state4[0 * batch + p], y = state4[1 * batch + p], vx = state4[2 * batch + p], vy = state4[3 * batch + p];
+  const double X = x * S, Y = y * S + prm.R0, VX = vx * S, VY = vy * S;
+  const double r0 = sqrt(X * X + Y * Y), v2 = VX * VX + VY * VY, rv = X * VX + Y * VY;
   const long npts = nc + 1;
-  coast[((long)0 * npts + jn) * batch + p] = Xn / S;
-  coast[((long)1 * npts + jn) * batch + p] = (Yn - prm.R0) / S;
-  coast[((long)2 * npts + jn) * batch + p] = VXn / S;
-  coast[((long)3 * npts + jn) * batch + p] = VYn / S;
+  double *out = coast + (long)jn * batch + p;
   if (jn == 0) {
-    theta2[p] = T2 / prm.T_scale;
-    apsides[0 * batch + p] = a * (1.0 - e) - prm.R0;
-    apsides[1 * batch + p] = a * (1.0 + e) - prm.R0;
+    double peri, apo;
+    apsides_of(prm, x, y, vx, vy, peri, apo);
+    apsides[0 * batch + p] = peri;
+    apsides[1 * batch + p] = apo;
   }
+  if (!(0.5 * v2 - GM / r0 < 0.0)) {          // not a bound orbit
+    ASC_UNROLL
+    for (int f = 0; f < 4; f++) out[(long)f * npts * batch] = NAN;
+    if (jn == 0) theta2[p] = NAN;
+    return;
+  }
+  const double a = 1.0 / (2.0 / r0 - v2 / GM);
+  const double sa = sqrt(GM * a), n = sa / (a * a);     // mean motion sqrt(GM / a^3)
+  const double ec = 1.0 - r0 / a, es = rv / sa;         // e cos E0, e sin E0
+  const double E0 = (ec == 0.0 && es == 0.0) ? 0.0 : atan2(es, ec);
+  const double M0 = E0 - es;
+  const double T2 = (M_PI - M0) / n;                    // to the next apoapsis: 0 <= T2 < one period
+  const double nt = n * (T2 * ((double)jn / (double)nc));
+  // Newton from the classical start E = M + e sin M, written so that it is exactly 0 at t = 0 (it only steers the iteration)
+  double dE = nt + sqrt(ec * ec + es * es) * (sin(M0 + nt) - sin(M0));
+  double sdE = sin(dE), sh = sin(0.5 * dE), omc = 2.0 * sh * sh;       // sin dE, 1 - cos dE
+  for (int it = 0; it < 16; it++) {
+    dE -= (dE - ec * sdE + es * omc - nt) / (1.0 - ec * (1.0 - omc) + es * sdE);
+    sdE = sin(dE); sh = sin(0.5 * dE); omc = 2.0 * sh * sh;
+  }
+  const double rr = r0 + a * (ec * omc + es * sdE);     // radius at the node
+  const double fm1 = -a / r0 * omc, g = a * (rv / GM) * omc + r0 * (a / sa) * sdE;
+  const double fd = -sa / (rr * r0) * sdE, gdm1 = -a / rr * omc;
+  out[0 * npts * batch] = x + (fm1 * x + g * vx);
+  out[1 * npts * batch] = y + (fm1 * (y + rho0) + g * vy);
+  out[2 * npts * batch] = vx + (fd * x + gdm1 * vx);
+  out[3 * npts * batch] = vy + (fd * (y + rho0) + gdm1 * vy);
+  if (jn == 0) theta2[p] = T2 / prm.T_scale;
 }
 
 }  // namespace

@@ -45,23 +45,19 @@ ASC_DEV void fly_step(const Der &d, double *z, double u, double hs, int m) {
   }
 }
 
-// periapsis / apoapsis altitude above R0 (m) of the two-body orbit through a scaled state: k_coast's formulas (semi-major axis
-// from the vis-viva equation, eccentricity vector); specific energy >= 0: periapsis from the semi-latus rectum, apoapsis +inf
+// periapsis / apoapsis altitude above R0 (m) of the two-body orbit through a scaled state, the library's one definition (the
+// flight summary, the trim and k_coast call it): eccentricity vector; periapsis from the semi-latus rectum, h^2 / (GM (1 + e)) --
+// a (1 - e) carries the rounding of a, 1 / (1 - e) times larger: 4e-9 m at e = 0.9 --; apoapsis a (1 + e) with the semi-major
+// axis from the vis-viva equation, +inf for specific energy >= 0
 ASC_DEV void apsides_of(const ascent_params &prm, double x, double y, double vx, double vy, double &peri, double &apo) {
   const double S = prm.r_peri, GM = prm.G * prm.M;
   const double X = x * S, Y = y * S + prm.R0, VX = vx * S, VY = vy * S;
   const double r = sqrt(X * X + Y * Y), v2 = VX * VX + VY * VY, rv = X * VX + Y * VY;
   const double ex = (v2 / GM - 1.0 / r) * X - rv / GM * VX, ey = (v2 / GM - 1.0 / r) * Y - rv / GM * VY;
   const double e = sqrt(ex * ex + ey * ey);
-  if (0.5 * v2 - GM / r >= 0.0) {
-    const double h = X * VY - Y * VX;
-    peri = h * h / (GM * (1.0 + e)) - prm.R0;
-    apo = INFINITY;
-  } else {
-    const double a = 1.0 / (2.0 / r - v2 / GM);
-    peri = a * (1.0 - e) - prm.R0;
-    apo = a * (1.0 + e) - prm.R0;
-  }
+  const double h = X * VY - Y * VX;
+  peri = h * h / (GM * (1.0 + e)) - prm.R0;
+  apo = 0.5 * v2 - GM / r >= 0.0 ? INFINITY : (1.0 + e) / (2.0 / r - v2 / GM) - prm.R0;
 }
 
 }  // namespace ascent

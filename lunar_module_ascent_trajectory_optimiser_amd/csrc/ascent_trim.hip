@@ -117,21 +117,31 @@ ASC_DEV void fly_step_tangent(const Der &d, double *z, double *dz, double u, dou
 }
 
 // Gradients of apsides_of's periapsis / apoapsis altitude with respect to (X, Y, VX, VY, GM) in SI units at a scaled state;
-// returns false where the specific energy is >= 0 (the apoapsis gradient is then NaN).  From E = v^2/2 - GM/r, h = X VY - Y VX,
-// e^2 = 1 + 2 E h^2 / GM^2, a = -GM / (2 E): periapsis a (1 - e), apoapsis a (1 + e); E >= 0: periapsis h^2 / (GM (1 + e)).
+// returns false where the specific energy is >= 0 (the apoapsis gradient is then NaN).  With E = v^2/2 - GM/r, h = X VY - Y VX,
+// a = -GM / (2 E) and the eccentricity vector (ex, ey) = (v^2/GM - 1/r) r - (r.v/GM) v of apsides_of: periapsis a (1 - e),
+// apoapsis a (1 + e); E >= 0: periapsis h^2 / (GM (1 + e)).  e and its gradient come from the vector, de = (ex dex + ey dey) / e
+// (accurate to about eps / e; e^2 = 1 + 2 E h^2 / GM^2 loses eps / e^2).  At e exactly 0 the apsides have a kink (e = |(ex, ey)|)
+// and no gradient: de is set to 0, so that both rows are the gradient of a - R0, the mean of the one-sided derivatives.
 ASC_DEV bool apsides_grad(const ascent_params &prm, double x, double y, double vx, double vy, double *gp, double *ga) {
   const double S = prm.r_peri, GM = prm.G * prm.M;
   const double X = x * S, Y = y * S + prm.R0, VX = vx * S, VY = vy * S;
-  const double r = sqrt(X * X + Y * Y), v2 = VX * VX + VY * VY;
+  const double r = sqrt(X * X + Y * Y), v2 = VX * VX + VY * VY, rv = X * VX + Y * VY;
   const double E = 0.5 * v2 - GM / r, h = X * VY - Y * VX;
-  const double e = sqrt(1.0 + 2.0 * E * h * h / (GM * GM));
   const double ir3 = 1.0 / (r * r * r);
+  const double c = v2 / GM - 1.0 / r, d = rv / GM;      // (ex, ey) = c (X, Y) - d (VX, VY)
+  const double ex = c * X - d * VX, ey = c * Y - d * VY;
+  const double e = sqrt(ex * ex + ey * ey);
   const double dE[5] = {GM * X * ir3, GM * Y * ir3, VX, VY, -1.0 / r};
   const double dh[5] = {VY, -VX, -Y, X, 0.0};
+  const double dc[5] = {X * ir3, Y * ir3, 2.0 * VX / GM, 2.0 * VY / GM, -v2 / (GM * GM)};
+  const double dd[5] = {VX / GM, VY / GM, X / GM, Y / GM, -rv / (GM * GM)};
   double de[5];
   ASC_UNROLL
-  for (int i = 0; i < 5; i++) de[i] = (h * h * dE[i] + 2.0 * E * h * dh[i]) / (GM * GM * e);
-  de[4] -= 2.0 * E * h * h / (GM * GM * GM * e);
+  for (int i = 0; i < 5; i++) {
+    const double dex = dc[i] * X - dd[i] * VX + (i == 0 ? c : 0.0) - (i == 2 ? d : 0.0);
+    const double dey = dc[i] * Y - dd[i] * VY + (i == 1 ? c : 0.0) - (i == 3 ? d : 0.0);
+    de[i] = e > 0.0 ? (ex * dex + ey * dey) / e : 0.0;
+  }
   if (E >= 0.0) {
     const double q = 1.0 / (GM * (1.0 + e));
     ASC_UNROLL

@@ -166,12 +166,17 @@ class BatchResult:
         S, R0, GM = P[:, 9], P[:, 2], P[:, 0] * P[:, 1]
         X, Y = self.traj[0, -1] * S, self.traj[1, -1] * S + R0
         VX, VY = self.traj[2, -1] * S, self.traj[3, -1] * S
-        r, v2 = np.hypot(X, Y), VX * VX + VY * VY
-        a = 1.0 / (2.0 / r - v2 / GM)
+        r, v2, rv = np.hypot(X, Y), VX * VX + VY * VY, X * VX + Y * VY
         h = X * VY - Y * VX
-        e = np.sqrt(np.maximum(0.0, 1.0 - h * h / (GM * a)))
-        return dict(periapsis_alt=a * (1 - e) - R0, apoapsis_alt=a * (1 + e) - R0, semi_major_axis=a, eccentricity=e,
-                    flight_path_angle=np.arcsin(np.clip((X * VX + Y * VY) / (r * np.sqrt(v2)), -1, 1)))
+        # the device's formulas (apsides_of): eccentricity from the eccentricity vector -- 1 - h^2 / (GM a) loses eps / e near
+        # the circle --, periapsis from the semi-latus rectum; specific energy >= 0: apoapsis +inf
+        ex, ey = (v2 / GM - 1.0 / r) * X - rv / GM * VX, (v2 / GM - 1.0 / r) * Y - rv / GM * VY
+        e = np.hypot(ex, ey)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a = 1.0 / (2.0 / r - v2 / GM)
+            apo = np.where(0.5 * v2 - GM / r < 0.0, a * (1 + e) - R0, np.inf)
+        return dict(periapsis_alt=h * h / (GM * (1 + e)) - R0, apoapsis_alt=apo, semi_major_axis=a, eccentricity=e,
+                    flight_path_angle=np.arcsin(np.clip(rv / (r * np.sqrt(v2)), -1, 1)))
 
     def coast(self, coast_nodes: int = 200, device: int = 0, flown: bool = False) -> dict:
         """The second phase: coast from every problem's burnout state to the apoapsis of its orbit, propagated on the
@@ -447,7 +452,8 @@ def dense_records(params, iterate: np.ndarray, nt: int = 200, scheme=2, device: 
 def coast_batch(params, final_state: np.ndarray, coast_nodes: int = 200, device: int = 0) -> dict:
     """Kepler-exact coast arc from every problem's burnout state (4, batch: scaled x, y, xdot, ydot) to the next apoapsis of
     its orbit (ascent_coast_batch): dict(traj (4, coast_nodes+1, batch), tf (batch,) = duration / T_scale,
-    periapsis_alt, apoapsis_alt (m))."""
+    periapsis_alt, apoapsis_alt (m)).  Node 0 is the input state; a state of specific energy >= 0 gives a NaN arc and duration
+    and an apoapsis of +inf (include/ascent.h)."""
     L = _lib.load()
     P = pack(params)
     B = P.shape[0]

@@ -57,9 +57,13 @@ def apsides(p, z):
     X, Y, VX, VY = z[0] * S, z[1] * S + R0, z[2] * S, z[3] * S
     GM = G * M
     r = np.sqrt(X * X + Y * Y)
-    E = 0.5 * (VX * VX + VY * VY) - GM / r
+    v2, rv = VX * VX + VY * VY, X * VX + Y * VY
+    E = 0.5 * v2 - GM / r
     h = X * VY - Y * VX
-    e = np.sqrt(1.0 + 2.0 * E * h * h / (GM * GM))
+    # e from the eccentricity vector (1 + 2 E h^2 / GM^2 loses eps / e^2 near the circle); sqrt of the sum of squares, not abs:
+    # it stays analytic for the complex step
+    ex, ey = (v2 / GM - 1.0 / r) * X - rv / GM * VX, (v2 / GM - 1.0 / r) * Y - rv / GM * VY
+    e = np.sqrt(ex * ex + ey * ey)
     bound = np.real(E) < 0.0
     with np.errstate(all="ignore"):
         a = -GM / (2.0 * E)

@@ -70,14 +70,15 @@ def _step(p, z, u, dt, m, formulation, integrator):
 
 def apsides(p, x, y, xd, yd):
     """periapsis / apoapsis altitude above R0 (m) of the two-body orbit through a scaled state, from the specific energy and
-    angular momentum; energy >= 0: apoapsis +inf"""
+    the eccentricity vector (1 + 2 E h^2 / GM^2 loses eps / e^2 near the circle); energy >= 0: apoapsis +inf"""
     G, M, R0, S = p[0], p[1], p[2], p[9]
     X, Y, VX, VY = x * S, y * S + R0, xd * S, yd * S
     GM = G * M
     r = math.hypot(X, Y)
-    E = 0.5 * (VX * VX + VY * VY) - GM / r
+    v2, rv = VX * VX + VY * VY, X * VX + Y * VY
+    E = 0.5 * v2 - GM / r
     h = X * VY - Y * VX
-    e = math.sqrt(max(0.0, 1.0 + 2.0 * E * h * h / (GM * GM)))
+    e = math.hypot((v2 / GM - 1.0 / r) * X - rv / GM * VX, (v2 / GM - 1.0 / r) * Y - rv / GM * VY)
     if E >= 0.0:
         return h * h / (GM * (1.0 + e)) - R0, math.inf
     a = -GM / (2.0 * E)
