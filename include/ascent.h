@@ -104,6 +104,8 @@ enum ascent_status {           /* function return codes */
   ASCENT_E_NOTERM = -5         /* the host-steered pipeline exceeded its round budget (a solver
                                   condition that the per-problem statuses could not express)   */
 };
+/* Every entry point refuses argument errors (ASCENT_E_ARG) before it looks at the device, so a bad argument is reported
+   as such on a machine without a GPU as well, not as ASCENT_E_NODEVICE. */
 
 enum ascent_problem_status {   /* values written to status_out[] */
   ASCENT_CONVERGED = 0,

@@ -239,7 +239,6 @@ size_t blocktri_ws_bytes(int n, long batch, int algo) {
 }
 size_t blocktri_node_doubles() { return node_doubles(); }
 
-#define BCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #call, hipGetErrorString(e_)); return ASCENT_E_HIP; } } while (0)
 
 // device pointers; Y [batch][n][bs][1+nb] receives T^-1 [rhs | border]; *singular is set when a pivot vanished
 int blocktri_run(long batch, int n, int bs, int nb, const double *ddiag, const double *dlower, const double *dupper,
@@ -247,11 +246,11 @@ int blocktri_run(long batch, int n, int bs, int nb, const double *ddiag, const d
                  hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, char *err, size_t errlen) {
   const size_t per = (size_t)batch * n * node_doubles();
   int *flag = (int *)((char *)ws + per * sizeof(double) * (algo == 1 ? 2 : 1));     // [batch] per-system flags + 1 summary
-  BCHK(hipMemsetAsync(flag, 0, ((size_t)batch + 1) * sizeof(int), stream));
+  ASC_CHK(err, errlen, hipMemsetAsync(flag, 0, ((size_t)batch + 1) * sizeof(int), stream));
   const dim3 g((unsigned)n, (unsigned)batch);
   hipLaunchKernelGGL(bt_pack, g, dim3(WAVE), 0, stream, batch, n, bs, nb, ddiag, dlower, dupper, dborder, drhs, ws);
-  BCHK(hipGetLastError());
-  if (ev0) BCHK(hipEventRecord(ev0, stream));
+  ASC_CHK(err, errlen, hipGetLastError());
+  if (ev0) ASC_CHK(err, errlen, hipEventRecord(ev0, stream));
   if (algo == 0) {
     hipLaunchKernelGGL(bt_thomas, dim3((unsigned)batch), dim3(WAVE), 0, stream, n, bs, nb, ws, dY, flag);
   } else {
@@ -263,11 +262,11 @@ int blocktri_run(long batch, int n, int bs, int nb, const double *ddiag, const d
     }
     hipLaunchKernelGGL(bt_finish, g, dim3(WAVE), 0, stream, n, bs, nb, (const double *)a, dY);
   }
-  BCHK(hipGetLastError());
-  if (ev1) BCHK(hipEventRecord(ev1, stream));
+  ASC_CHK(err, errlen, hipGetLastError());
+  if (ev1) ASC_CHK(err, errlen, hipEventRecord(ev1, stream));
   hipLaunchKernelGGL(bt_any, dim3(1), dim3(256), 0, stream, (const int *)flag, batch, flag + batch);
-  BCHK(hipMemcpyAsync(singular, flag + batch, sizeof(int), hipMemcpyDeviceToHost, stream));
-  BCHK(hipStreamSynchronize(stream));
+  ASC_CHK(err, errlen, hipMemcpyAsync(singular, flag + batch, sizeof(int), hipMemcpyDeviceToHost, stream));
+  ASC_CHK(err, errlen, hipStreamSynchronize(stream));
   return ASCENT_OK;
 }
 
@@ -283,7 +282,7 @@ int blocktri_pcr_assembled(long batch, int n, int bs, int nb, double *a, double 
     double *t = a; a = b; b = t;
   }
   hipLaunchKernelGGL(bt_finish, g, dim3(WAVE), 0, stream, n, bs, nb, (const double *)a, dY);
-  BCHK(hipGetLastError());
+  ASC_CHK(err, errlen, hipGetLastError());
   return ASCENT_OK;
 }
 

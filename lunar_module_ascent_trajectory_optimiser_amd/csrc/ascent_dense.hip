@@ -1438,43 +1438,46 @@ static PcrWs pcr_ws(double *ws, int K, long batch) {
   return q;
 }
 
-#define DCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #call, hipGetErrorString(e_)); return ASCENT_E_HIP; } } while (0)
-
-static int pcr_newton(const ascent_params *dp, long batch, DGeo g, double *ws, int probe, int *counters, hipStream_t stream,
-                      char *err, size_t errlen) {
+static int pcr_newton(const Call &c, DGeo g, double *ws, int probe, int *counters) {
+  const ascent_params *dp = c.dp;
+  const long batch = c.batch;
+  hipStream_t stream = c.stream;
   const int K = g.K;
   const PcrWs q = pcr_ws(ws, K, batch);
-  DCHK(hipMemsetAsync(q.flags, 0, (size_t)batch * sizeof(int), stream));
+  ASC_CHK(c.err, c.errlen, hipMemsetAsync(q.flags, 0, (size_t)batch * sizeof(int), stream));
   if (g.dc) hipLaunchKernelGGL(pc_assemble<1>, dim3((unsigned)K, (unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, (const double *)ws, q.bt_a, q.bcols, blocktri_node_doubles());
   else hipLaunchKernelGGL(pc_assemble<0>, dim3((unsigned)K, (unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, (const double *)ws, q.bt_a, q.bcols, blocktri_node_doubles());
-  DCHK(hipGetLastError());
-  int rc = blocktri_pcr_assembled(batch, K, g.dc ? 16 : PC_BS, PC_NB, q.bt_a, q.bt_b, q.Y, q.flags, stream, err, errlen);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
+  int rc = blocktri_pcr_assembled(batch, K, g.dc ? 16 : PC_BS, PC_NB, q.bt_a, q.bt_b, q.Y, q.flags, stream, c.err, c.errlen);
   if (rc) return rc;
   if (g.dc) hipLaunchKernelGGL(pc_step<1>, dim3((unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, ws, (const double *)q.Y, (const double *)q.bcols, (const int *)q.flags, probe, counters);
   else hipLaunchKernelGGL(pc_step<0>, dim3((unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, ws, (const double *)q.Y, (const double *)q.bcols, (const int *)q.flags, probe, counters);
-  DCHK(hipGetLastError());
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 
-int dense_run(const ascent_params *dp, long batch, int K, int scheme, int terminal, double *ws, const double *dguess, int warm,
-              int max_iter, double tol, double mu0, double *dtraj, double *dtf, int *dstatus, int *diters, double *dblob,
-              hipStream_t stream, char *err, size_t errlen, int pcr, int move_penalty) {
-  DGeo g{K, scheme, terminal, move_penalty ? 1 : 0};
+int dense_run(const Call &c, double *ws, const SolveIO &io, bool pcr) {
+  const ascent_params *dp = c.dp;
+  const long batch = c.batch;
+  const int K = c.K, max_iter = io.max_iter;
+  const double tol = io.tol;
+  hipStream_t stream = c.stream;
+  DGeo g{K, c.scheme, c.term, c.mp ? 1 : 0};
   int *counters = (int *)((char *)ws + (size_t)batch * g.nlp_doubles() * sizeof(double));
   static int *host_cnt_dev[64] = {nullptr};
   int dev_ = 0;
-  DCHK(hipGetDevice(&dev_));
+  ASC_CHK(c.err, c.errlen, hipGetDevice(&dev_));
   dev_ &= 63;
-  if (!host_cnt_dev[dev_]) DCHK(hipHostMalloc((void **)&host_cnt_dev[dev_], 4 * sizeof(int)));
+  if (!host_cnt_dev[dev_]) ASC_CHK(c.err, c.errlen, hipHostMalloc((void **)&host_cnt_dev[dev_], 4 * sizeof(int)));
   int *host_cnt = host_cnt_dev[dev_];
   const dim3 ngrid((unsigned)((K + WAVE - 1) / WAVE), (unsigned)batch);
-  hipLaunchKernelGGL(d_init, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, dguess, warm, mu0, 0, (const double *)nullptr);
-  DCHK(hipGetLastError());
+  hipLaunchKernelGGL(d_init, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, io.guess, io.warm, io.mu0, 0, (const double *)nullptr);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   const int burst = 4;
   for (long round = 0;;) {
-    if (round > 50L * (max_iter + 2)) { snprintf(err, errlen, "dense path did not terminate within %ld rounds", round); return ASCENT_E_NOTERM; }
+    if (round > 50L * (max_iter + 2)) { snprintf(c.err, c.errlen, "dense path did not terminate within %ld rounds", round); return ASCENT_E_NOTERM; }
     for (int r = 0; r < burst; r++, round++) {
-      DCHK(hipMemsetAsync(counters, 0, sizeof(int), stream));
+      ASC_CHK(c.err, c.errlen, hipMemsetAsync(counters, 0, sizeof(int), stream));
       hipLaunchKernelGGL(d_eval, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws);
       if (!pcr) {
         if (batch <= 1024)       // (at most one wavefront per SIMD: the pipelined variant)
@@ -1487,54 +1490,56 @@ int dense_run(const ascent_params *dp, long batch, int K, int scheme, int termin
         hipLaunchKernelGGL(d_newton<1>, dim3((unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, ws, max_iter, tol, 0,
                            (const double *)nullptr, counters);
         // (an NLP that goes on is counted by both kernels; the host only asks whether the counter is zero)
-        const int rc = pcr_newton(dp, batch, g, ws, 0, counters, stream, err, errlen);
+        const int rc = pcr_newton(c, g, ws, 0, counters);
         if (rc) return rc;
       }
-      DCHK(hipGetLastError());
+      ASC_CHK(c.err, c.errlen, hipGetLastError());
     }
-    DCHK(hipMemcpyAsync(host_cnt, counters, sizeof(int), hipMemcpyDeviceToHost, stream));
-    DCHK(hipStreamSynchronize(stream));
+    ASC_CHK(c.err, c.errlen, hipMemcpyAsync(host_cnt, counters, sizeof(int), hipMemcpyDeviceToHost, stream));
+    ASC_CHK(c.err, c.errlen, hipStreamSynchronize(stream));
     if (host_cnt[0] == 0) break;          // no NLP asked for another trial point in the last round
   }
-  hipLaunchKernelGGL(d_finish, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, dtraj, dtf, dstatus, diters, dblob, 0);
-  DCHK(hipGetLastError());
+  hipLaunchKernelGGL(d_finish, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, io.traj, io.tf, io.status, io.iters, io.blob, 0);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 
-int dense_probe(const ascent_params *dp, long batch, int K, int scheme, int terminal, double *ws, const double *diterate,
-                const double *dmu, const double *ddw, bool step_too, double *dstep, int *dinertia, double *drecords,
-                hipStream_t stream, char *err, size_t errlen, int pcr, int move_penalty) {
-  DGeo g{K, scheme, terminal, move_penalty ? 1 : 0};
+int dense_probe(const Call &c, double *ws, const ProbeIO &io, bool pcr) {
+  const ascent_params *dp = c.dp;
+  const long batch = c.batch;
+  const int K = c.K;
+  hipStream_t stream = c.stream;
+  const bool step_too = io.step != nullptr;
+  DGeo g{K, c.scheme, c.term, c.mp ? 1 : 0};
   int *counters = (int *)((char *)ws + (size_t)batch * g.nlp_doubles() * sizeof(double));
   const dim3 ngrid((unsigned)((K + WAVE - 1) / WAVE), (unsigned)batch);
-  hipLaunchKernelGGL(d_init, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, diterate, 2, 0.1, 1, dmu);
+  hipLaunchKernelGGL(d_init, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, io.iterate, 2, 0.1, 1, io.mu);
   hipLaunchKernelGGL(d_eval, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws);
-  DCHK(hipGetLastError());
-  if (drecords) {
-    hipLaunchKernelGGL(d_dump_records, dim3((unsigned)K, (unsigned)batch), dim3(WAVE), 0, stream, batch, g, ws, drecords);
-    DCHK(hipGetLastError());
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
+  if (io.records) {
+    hipLaunchKernelGGL(d_dump_records, dim3((unsigned)K, (unsigned)batch), dim3(WAVE), 0, stream, batch, g, ws, io.records);
+    ASC_CHK(c.err, c.errlen, hipGetLastError());
   }
   if (step_too && pcr) {
-    hipLaunchKernelGGL(d_newton<1>, dim3((unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, ws, 1 << 30, -1.0, 1, ddw, counters);
-    const int rc = pcr_newton(dp, batch, g, ws, 1, counters, stream, err, errlen);
+    hipLaunchKernelGGL(d_newton<1>, dim3((unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, ws, 1 << 30, -1.0, 1, io.dw, counters);
+    const int rc = pcr_newton(c, g, ws, 1, counters);
     if (rc) return rc;
-    hipLaunchKernelGGL(d_finish, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, (double *)nullptr, (double *)nullptr, dinertia,
-                       (int *)nullptr, dstep, 1);
-    DCHK(hipGetLastError());
+    hipLaunchKernelGGL(d_finish, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, (double *)nullptr, (double *)nullptr, io.inertia,
+                       (int *)nullptr, io.step, 1);
+    ASC_CHK(c.err, c.errlen, hipGetLastError());
   } else if (step_too) {
-    hipLaunchKernelGGL(d_newton<0>, dim3((unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, ws, 1 << 30, -1.0, 1, ddw, counters);
-    hipLaunchKernelGGL(d_finish, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, (double *)nullptr, (double *)nullptr, dinertia,
-                       (int *)nullptr, dstep, 1);
-    DCHK(hipGetLastError());
+    hipLaunchKernelGGL(d_newton<0>, dim3((unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, ws, 1 << 30, -1.0, 1, io.dw, counters);
+    hipLaunchKernelGGL(d_finish, ngrid, dim3(WAVE), 0, stream, dp, batch, g, ws, (double *)nullptr, (double *)nullptr, io.inertia,
+                       (int *)nullptr, io.step, 1);
+    ASC_CHK(c.err, c.errlen, hipGetLastError());
   }
   return ASCENT_OK;
 }
 
-int coast_run(const ascent_params *dp, long batch, const double *dstate4, int nc, double *dcoast, double *dtheta2,
-              double *dapsides, hipStream_t stream, char *err, size_t errlen) {
-  hipLaunchKernelGGL(k_coast, dim3((unsigned)((batch + WAVE - 1) / WAVE), (unsigned)(nc + 1)), dim3(WAVE), 0, stream, dp, batch,
+int coast_run(const Call &c, const double *dstate4, int nc, double *dcoast, double *dtheta2, double *dapsides) {
+  hipLaunchKernelGGL(k_coast, dim3((unsigned)((c.batch + WAVE - 1) / WAVE), (unsigned)(nc + 1)), dim3(WAVE), 0, c.stream, c.dp, c.batch,
                      dstate4, nc, dcoast, dtheta2, dapsides);
-  DCHK(hipGetLastError());
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 

@@ -164,29 +164,25 @@ __global__ __launch_bounds__(LB) void f_local(const ascent_params *__restrict__ 
 
 }  // namespace
 
-#define FCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #call, hipGetErrorString(e_)); return ASCENT_E_HIP; } } while (0)
-
-int flight_fly_only(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
-                    double *dsummary, hipStream_t stream, char *err, size_t errlen) {
-  const dim3 gfly((unsigned)((batch + FW - 1) / FW)), bfly(FW);
-  if (formulation == 1)
-    hipLaunchKernelGGL((f_fly<1>), gfly, bfly, 0, stream, dp, batch, K, substeps, dblob, dtraj, dsummary);
+int flight_fly_only(const Call &c, int substeps, const double *dblob, double *dtraj, double *dsummary) {
+  const dim3 gfly((unsigned)((c.batch + FW - 1) / FW)), bfly(FW);
+  if (c.form == 1)
+    hipLaunchKernelGGL((f_fly<1>), gfly, bfly, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, dtraj, dsummary);
   else
-    hipLaunchKernelGGL((f_fly<0>), gfly, bfly, 0, stream, dp, batch, K, substeps, dblob, dtraj, dsummary);
-  FCHK(hipGetLastError());
+    hipLaunchKernelGGL((f_fly<0>), gfly, bfly, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, dtraj, dsummary);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 
-int flight_run(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
-               double *dlocal, double *dsummary, hipStream_t stream, char *err, size_t errlen) {
-  if (const int rc = flight_fly_only(dp, batch, K, formulation, substeps, dblob, dtraj, dsummary, stream, err, errlen)) return rc;
-  const int pb = sens_problems_per_group(batch);      // the same split of a workgroup between NLPs and steps as s_sens
-  const dim3 gloc((unsigned)((batch + pb - 1) / pb)), bloc(LB);
-  if (formulation == 1)
-    hipLaunchKernelGGL((f_local<1>), gloc, bloc, 0, stream, dp, batch, K, pb, substeps, dblob, dlocal, dsummary);
+int flight_run(const Call &c, int substeps, const double *dblob, double *dtraj, double *dlocal, double *dsummary) {
+  if (const int rc = flight_fly_only(c, substeps, dblob, dtraj, dsummary)) return rc;
+  const int pb = sens_problems_per_group(c.batch);      // the same split of a workgroup between NLPs and steps as s_sens
+  const dim3 gloc((unsigned)((c.batch + pb - 1) / pb)), bloc(LB);
+  if (c.form == 1)
+    hipLaunchKernelGGL((f_local<1>), gloc, bloc, 0, c.stream, c.dp, c.batch, c.K, pb, substeps, dblob, dlocal, dsummary);
   else
-    hipLaunchKernelGGL((f_local<0>), gloc, bloc, 0, stream, dp, batch, K, pb, substeps, dblob, dlocal, dsummary);
-  FCHK(hipGetLastError());
+    hipLaunchKernelGGL((f_local<0>), gloc, bloc, 0, c.stream, c.dp, c.batch, c.K, pb, substeps, dblob, dlocal, dsummary);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 

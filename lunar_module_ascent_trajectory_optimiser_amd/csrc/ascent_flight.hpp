@@ -3,19 +3,18 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "ascent.h"
+#include "ascent_host.hpp"
 
 namespace ascent {
 
 // Fly every NLP's control with RK4 and compare with its solution blob (include/ascent.h: ascent_fly_batch).  Device pointers:
-// dp[batch], dblob [21K+10][batch], dtraj [10(K+1)][batch] or null, dlocal [7K][batch] or null, dsummary
+// c.dp[batch], dblob [21K+10][batch], dtraj [10(K+1)][batch] or null, dlocal [7K][batch] or null, dsummary
 // [ASCENT_FLIGHT_ROWS][batch].  Options already checked by the caller (formulation 0 / 1, substeps 0 .. ASCENT_FLIGHT_MAX_SUBSTEPS).
-// Only enqueues two kernels on `stream` (f_fly, f_local; they write disjoint rows).  Returns ASCENT_OK / ASCENT_E_HIP.
-int flight_run(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
-               double *dlocal, double *dsummary, hipStream_t stream, char *err, size_t errlen);
+// Only enqueues two kernels on c.stream (f_fly, f_local; they write disjoint rows).  Returns ASCENT_OK / ASCENT_E_HIP.
+int flight_run(const Call &c, int substeps, const double *dblob, double *dtraj, double *dlocal, double *dsummary);
 
 // The serial fly-out alone (f_fly; summary rows 0..5 and 9 only): the linearisation point of the flight Jacobian and every
 // round of the trim (ascent_trim.hip).
-int flight_fly_only(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *dtraj,
-                    double *dsummary, hipStream_t stream, char *err, size_t errlen);
+int flight_fly_only(const Call &c, int substeps, const double *dblob, double *dtraj, double *dsummary);
 
 }  // namespace ascent

@@ -823,35 +823,31 @@ __global__ __launch_bounds__(WAVE) void k_kkt_step(const ascent_params *params, 
 
 namespace ascent {
 
-static int launched(char *err, size_t errlen) {      // ASCENT_OK, or ASCENT_E_HIP when the launch just made was refused
+static int launched(const Call &c) {      // ASCENT_OK, or ASCENT_E_HIP when the launch just made was refused
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) return ASCENT_OK;
-  snprintf(err, errlen, "fused kernel launch: %s", hipGetErrorString(e));
+  snprintf(c.err, c.errlen, "fused kernel launch: %s", hipGetErrorString(e));
   return ASCENT_E_HIP;
 }
 
 size_t fused_ws_bytes(int K, long batch) { return (size_t)((batch + WAVE - 1) / WAVE) * tile_doubles(K) * sizeof(double); }
 
-int fused_run(const ascent_params *dp, long batch, int K, double *ws, const double *dguess, int warm, int max_iter, double tol,
-              double mu0, double *dtraj, double *dtf, int *dstatus, int *diters, double *dblob, hipStream_t stream, char *err,
-              size_t errlen) {
-  hipLaunchKernelGGL(k_solve, dim3((unsigned)((batch + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, dp, batch, K, ws, dguess, warm,
-                     max_iter, tol, mu0, dtraj, dtf, dstatus, diters, dblob);
-  return launched(err, errlen);
+int fused_run(const Call &c, double *ws, const SolveIO &io) {
+  hipLaunchKernelGGL(k_solve, dim3((unsigned)((c.batch + WAVE - 1) / WAVE)), dim3(WAVE), 0, c.stream, c.dp, c.batch, c.K, ws, io.guess, io.warm,
+                     io.max_iter, io.tol, io.mu0, io.traj, io.tf, io.status, io.iters, io.blob);
+  return launched(c);
 }
 
-int fused_probe(const ascent_params *dp, long batch, int K, double *ws, const double *diterate, const double *dmu, const double *ddw,
-                double *dstep, int *dinertia, hipStream_t stream, char *err, size_t errlen) {
-  hipLaunchKernelGGL(k_kkt_step, dim3((unsigned)((batch + WAVE - 1) / WAVE)), dim3(WAVE), 0, stream, dp, batch, K, ws, diterate, dmu,
-                     ddw, dstep, dinertia);
-  return launched(err, errlen);
+int fused_probe(const Call &c, double *ws, const ProbeIO &io) {
+  hipLaunchKernelGGL(k_kkt_step, dim3((unsigned)((c.batch + WAVE - 1) / WAVE)), dim3(WAVE), 0, c.stream, c.dp, c.batch, c.K, ws, io.iterate, io.mu,
+                     io.dw, io.step, io.inertia);
+  return launched(c);
 }
 
-int fused_eval_nodes(const ascent_params *dp, long batch, int K, const double *diterate, double *ddefects, double *djac, double *dhess,
-                     hipStream_t stream, char *err, size_t errlen) {
-  hipLaunchKernelGGL(k_eval_nodes, dim3((unsigned)((batch + 255) / 256), K), dim3(256), 0, stream, dp, batch, K, diterate, ddefects,
-                     djac, dhess);
-  return launched(err, errlen);
+int fused_eval_nodes(const Call &c, const ProbeIO &io) {
+  hipLaunchKernelGGL(k_eval_nodes, dim3((unsigned)((c.batch + 255) / 256), c.K), dim3(256), 0, c.stream, c.dp, c.batch, c.K, io.iterate, io.defects,
+                     io.jac, io.hess);
+  return launched(c);
 }
 
 }  // namespace ascent

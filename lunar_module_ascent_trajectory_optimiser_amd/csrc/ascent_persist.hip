@@ -1487,7 +1487,19 @@ size_t persist_ws_bytes_nested(const int *levels, int nlev, long batch, int mp) 
   return b;
 }
 
-#define PCHK2(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #call, hipGetErrorString(e_)); return ASCENT_E_HIP; } } while (0)
+// The twenty instantiations of p_solve: ten variants (scheme, formulation, move penalty, terminal), each with four NLPs per
+// wavefront and with one.  A tuple that is not among them was refused by the C ABI; it would run the plain variant.
+using SolveKernel = void (*)(const ascent_params *, long, PGeo, double *, int, double);
+struct SolveVariant { int scheme, form, mp, term, wide; SolveKernel kernel; };
+#define ASC_VARIANT(S, F, M, T, W) {S, F, M, T, W, p_solve<S, F, M, T, W>}
+static const SolveVariant solve_variants[] = {
+    ASC_VARIANT(1, 0, 1, 2, 1), ASC_VARIANT(0, 0, 1, 2, 1), ASC_VARIANT(1, 0, 0, 2, 1), ASC_VARIANT(0, 0, 0, 2, 1),
+    ASC_VARIANT(1, 0, 1, 0, 1), ASC_VARIANT(0, 1, 1, 0, 1), ASC_VARIANT(0, 1, 0, 0, 1), ASC_VARIANT(0, 0, 1, 0, 1),
+    ASC_VARIANT(1, 0, 0, 0, 1), ASC_VARIANT(0, 0, 0, 0, 1),
+    ASC_VARIANT(1, 0, 1, 2, 0), ASC_VARIANT(0, 0, 1, 2, 0), ASC_VARIANT(1, 0, 0, 2, 0), ASC_VARIANT(0, 0, 0, 2, 0),
+    ASC_VARIANT(1, 0, 1, 0, 0), ASC_VARIANT(0, 1, 1, 0, 0), ASC_VARIANT(0, 0, 1, 0, 0), ASC_VARIANT(1, 0, 0, 0, 0),
+    ASC_VARIANT(0, 1, 0, 0, 0), ASC_VARIANT(0, 0, 0, 0, 0)};
+#undef ASC_VARIANT
 
 static void launch_solve(int scheme, int form, int mp, long batch, hipStream_t stream, const ascent_params *dp, const PGeo &g, double *w,
                          int max_iter, double tol) {
@@ -1495,52 +1507,29 @@ static void launch_solve(int scheme, int form, int mp, long batch, hipStream_t s
     hs_launch_solve(batch, stream, dp, g.K, g.Kp, g.nch, g.term, g.wide, w, max_iter, tol);
     return;
   }
-  if (g.wide) {      // one NLP per wavefront
-    const dim3 gw((unsigned)batch), bw(WAVE);
-    if (g.term == 2) {      // burnout anywhere on the ellipse (formulation 0)
-      if (mp && scheme == 1) hipLaunchKernelGGL((p_solve<1, 0, 1, 2, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-      else if (mp) hipLaunchKernelGGL((p_solve<0, 0, 1, 2, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-      else if (scheme == 1) hipLaunchKernelGGL((p_solve<1, 0, 0, 2, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-      else hipLaunchKernelGGL((p_solve<0, 0, 0, 2, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-      return;
-    }
-    if (mp && scheme == 1) hipLaunchKernelGGL((p_solve<1, 0, 1, 0, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-    else if (mp && form == 1) hipLaunchKernelGGL((p_solve<0, 1, 1, 0, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-    else if (form == 1) hipLaunchKernelGGL((p_solve<0, 1, 0, 0, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-    else if (mp) hipLaunchKernelGGL((p_solve<0, 0, 1, 0, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-    else if (scheme == 1) hipLaunchKernelGGL((p_solve<1, 0, 0, 0, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-    else hipLaunchKernelGGL((p_solve<0, 0, 0, 0, 1>), gw, bw, 0, stream, dp, batch, g, w, max_iter, tol);
-    return;
-  }
-  const dim3 grid((unsigned)((batch + NPW - 1) / NPW)), block(WAVE);
-  if (g.term == 2) {      // burnout anywhere on the ellipse (formulation 0)
-    if (mp && scheme == 1) hipLaunchKernelGGL((p_solve<1, 0, 1, 2>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
-    else if (mp) hipLaunchKernelGGL((p_solve<0, 0, 1, 2>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
-    else if (scheme == 1) hipLaunchKernelGGL((p_solve<1, 0, 0, 2>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
-    else hipLaunchKernelGGL((p_solve<0, 0, 0, 2>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
-    return;
-  }
-  if (mp && scheme == 1) hipLaunchKernelGGL((p_solve<1, 0, 1>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
-  else if (mp && form == 1) hipLaunchKernelGGL((p_solve<0, 1, 1>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
-  else if (mp) hipLaunchKernelGGL((p_solve<0, 0, 1>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
-  else if (scheme == 1) hipLaunchKernelGGL((p_solve<1, 0, 0>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
-  else if (form == 1) hipLaunchKernelGGL((p_solve<0, 1, 0>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
-  else hipLaunchKernelGGL((p_solve<0, 0, 0>), grid, block, 0, stream, dp, batch, g, w, max_iter, tol);
+  SolveKernel kernel = g.wide ? p_solve<0, 0, 0, 0, 1> : p_solve<0, 0, 0, 0, 0>;
+  for (const SolveVariant &v : solve_variants)
+    if (v.scheme == scheme && v.form == form && v.mp == (mp ? 1 : 0) && v.term == g.term && v.wide == g.wide) kernel = v.kernel;
+  // one NLP per wavefront, or four
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(g.wide ? batch : (batch + NPW - 1) / NPW)), dim3(WAVE), 0, stream, dp, batch, g, w, max_iter, tol);
 }
 
 // All grid levels of the nested iteration (levels[0] = the requested grid, finest first; the coarsest is solved first, cold or
 // from the caller's guess): p_init, then per level p_solve and p_transfer to the next finer grid, p_finish at the end.  Two
 // workspace regions alternate between the levels.  mp: with the l1 move penalty (schemes 0 / 1, formulation 0).
-int persist_run_nested(const ascent_params *dp, long batch, int scheme, int form, int mp, int term, int wide, const int *levels, int nlev, double *ws, const double *dguess, int warm,
-                       int max_iter, double tol, double tol_coarse, double mu0, double mu_first, double mu_next, double *dtraj,
-                       double *dtf, int *dstatus, int *diters, double *dblob, hipStream_t stream, char *err, size_t errlen) {
+int persist_run_nested(const Call &c, bool wide, const int *levels, int nlev, double *ws, const SolveIO &io, double tol_coarse,
+                       double mu_first, double mu_next) {
+  const ascent_params *dp = c.dp;
+  const long batch = c.batch;
+  const int scheme = c.scheme, form = c.form, mp = c.mp, term = c.term;
+  hipStream_t stream = c.stream;
   double *region[2] = {ws, (double *)((char *)ws + persist_region1_offset(levels, batch, mp))};
   PGeo g = geo_of(levels[nlev - 1] - 1, form, mp, term, wide, scheme);
   double *w = region[(nlev - 1) & 1];
-  hipLaunchKernelGGL(p_init, dim3((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, w, dguess,
-                     warm, mu0, (const double *)nullptr, (const double *)nullptr, 0);
+  hipLaunchKernelGGL(p_init, dim3((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)batch), dim3(WAVE), 0, stream, dp, batch, g, w, io.guess,
+                     io.warm, io.mu0, (const double *)nullptr, (const double *)nullptr, 0);
   for (int l = nlev - 1; l >= 0; l--) {
-    launch_solve(scheme, form, mp, batch, stream, dp, g, w, max_iter, l == 0 ? tol : tol_coarse);
+    launch_solve(scheme, form, mp, batch, stream, dp, g, w, io.max_iter, l == 0 ? io.tol : tol_coarse);
     if (l > 0) {
       const PGeo gf = geo_of(levels[l - 1] - 1, form, mp, term, wide, scheme);
       double *wf = region[(l - 1) & 1];
@@ -1550,36 +1539,34 @@ int persist_run_nested(const ascent_params *dp, long batch, int scheme, int form
     }
   }
   hipLaunchKernelGGL(p_finish, dim3((unsigned)((g.K + CH - 1) / CH), (unsigned)((batch + WAVE - 1) / WAVE)), dim3(WAVE, FIN_WAVES), 0, stream, dp, batch, g,
-                     (const double *)w, dtraj, dtf, dstatus, diters, dblob);
-  PCHK2(hipGetLastError());
+                     (const double *)w, io.traj, io.tf, io.status, io.iters, io.blob);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 
 // One round of p_solve at a caller-supplied iterate (parity surface ascent_kkt_step_path): the iterate as it is, mu and
 // delta_w per problem from the caller; p_probe_out hands back the Newton step.  (mp: the slack pairs, which the blob does
 // not carry, are set around the iterate's own movement as every warm start sets them.)
-int persist_probe(const ascent_params *dp, long batch, int scheme, int form, int mp, int term, int wide, int K, double *ws, const double *diterate, const double *dmu, const double *ddw,
-                  double *dstep, int *dinertia, hipStream_t stream, char *err, size_t errlen) {
-  const PGeo g = geo_of(K, form, mp, term, wide, scheme);
-  const dim3 ng((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)batch);
-  hipLaunchKernelGGL(p_init, ng, dim3(WAVE), 0, stream, dp, batch, g, ws, diterate, 2, 0.1, dmu, ddw, 1);
-  launch_solve(scheme, form, mp, batch, stream, dp, g, ws, 1000, -1.0);
-  hipLaunchKernelGGL(p_probe_out, ng, dim3(WAVE), 0, stream, batch, g, (const double *)ws, dstep, dinertia);
-  PCHK2(hipGetLastError());
+int persist_probe(const Call &c, bool wide, double *ws, const ProbeIO &io) {
+  const PGeo g = geo_of(c.K, c.form, c.mp, c.term, wide, c.scheme);
+  const dim3 ng((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)c.batch);
+  hipLaunchKernelGGL(p_init, ng, dim3(WAVE), 0, c.stream, c.dp, c.batch, g, ws, io.iterate, 2, 0.1, io.mu, io.dw, 1);
+  launch_solve(c.scheme, c.form, c.mp, c.batch, c.stream, c.dp, g, ws, 1000, -1.0);
+  hipLaunchKernelGGL(p_probe_out, ng, dim3(WAVE), 0, c.stream, c.batch, g, (const double *)ws, io.step, io.inertia);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 
 // The node rows of the same kernel (parity surface ascent_eval_nodes_path): one round of p_solve up to the point where the
-// blocks of every chunk stand in LDS; they are copied out instead of being swept.  dzero: a device array of `batch` zeros
-// (mu and delta_w do not enter the rows).
-int persist_probe_rows(const ascent_params *dp, long batch, int scheme, int form, int wide, int K, double *ws, const double *diterate, const double *dzero,
-                       double *ddefects, double *djac, double *dhess, hipStream_t stream, char *err, size_t errlen) {
-  const PGeo g = geo_of(K, form, 0, 0, wide);
-  const dim3 ng((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)batch);
-  hipLaunchKernelGGL(p_init, ng, dim3(WAVE), 0, stream, dp, batch, g, ws, diterate, 2, 0.1, dzero, dzero, 2);
-  launch_solve(scheme, form, 0, batch, stream, dp, g, ws, 1000, -1.0);
-  hipLaunchKernelGGL(p_probe_rows_out, ng, dim3(WAVE), 0, stream, dp, batch, g, (const double *)ws, ddefects, djac, dhess);
-  PCHK2(hipGetLastError());
+// blocks of every chunk stand in LDS; they are copied out instead of being swept.  io.mu: a device array of `batch` zeros
+// (mu and delta_w do not enter the rows, nor do the move penalty and the terminal condition).
+int persist_probe_rows(const Call &c, bool wide, double *ws, const ProbeIO &io) {
+  const PGeo g = geo_of(c.K, c.form, 0, 0, wide);
+  const dim3 ng((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)c.batch);
+  hipLaunchKernelGGL(p_init, ng, dim3(WAVE), 0, c.stream, c.dp, c.batch, g, ws, io.iterate, 2, 0.1, io.mu, io.mu, 2);
+  launch_solve(c.scheme, c.form, 0, c.batch, c.stream, c.dp, g, ws, 1000, -1.0);
+  hipLaunchKernelGGL(p_probe_rows_out, ng, dim3(WAVE), 0, c.stream, c.dp, c.batch, g, (const double *)ws, io.defects, io.jac, io.hess);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 

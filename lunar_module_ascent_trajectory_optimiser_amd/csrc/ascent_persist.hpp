@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "ascent.h"
+#include "ascent_host.hpp"
 
 namespace ascent {
 
@@ -18,19 +19,17 @@ size_t persist_ws_bytes(int K, long batch, int mp);
 size_t persist_region1_offset(const int *levels, long batch, int mp);
 size_t persist_ws_bytes_nested(const int *levels, int nlev, long batch, int mp);
 size_t persist_level_bytes_used(int K, long batch, int mp);      // bytes the kernels of one level touch from the start of its region
-int persist_run_nested(const ascent_params *dp, long batch, int scheme, int form, int mp, int term, int wide, const int *levels, int nlev, double *ws, const double *dguess, int warm,
-                       int max_iter, double tol, double tol_coarse, double mu0, double mu_first, double mu_next, double *dtraj,
-                       double *dtf, int *dstatus, int *diters, double *dblob, hipStream_t stream, char *err, size_t errlen);
+// io: the request of the finest level (its guess, warm and mu0 go to the coarsest level, which is solved first).
+int persist_run_nested(const Call &c, bool wide, const int *levels, int nlev, double *ws, const SolveIO &io, double tol_coarse,
+                       double mu_first, double mu_next);
 
 // One interior-point round of the same kernel at a caller-supplied iterate, mu and delta_w (parity surface): the Newton step in
 // the blob layout, inertia[p] = 1 where the factorisation was refused.
-int persist_probe(const ascent_params *dp, long batch, int scheme, int form, int mp, int term, int wide, int K, double *ws, const double *diterate, const double *dmu, const double *ddw,
-                  double *dstep, int *dinertia, hipStream_t stream, char *err, size_t errlen);
+int persist_probe(const Call &c, bool wide, double *ws, const ProbeIO &io);
 
 // The node rows (defects, Jacobian and Hessian blocks in the layout of ascent_eval_nodes) that one round of the same kernel
-// leaves in LDS for its factorisation sweep, copied out instead of swept.  dzero: `batch` zeros on the device.
-int persist_probe_rows(const ascent_params *dp, long batch, int scheme, int form, int wide, int K, double *ws, const double *diterate, const double *dzero,
-                       double *ddefects, double *djac, double *dhess, hipStream_t stream, char *err, size_t errlen);
+// leaves in LDS for its factorisation sweep, copied out instead of swept.  io.mu: `batch` zeros on the device.
+int persist_probe_rows(const Call &c, bool wide, double *ws, const ProbeIO &io);
 
 // Hermite-Simpson (scheme 2) in the same layout: ascent_hs.hip.  One launch = one grid level of the batch; the node arrays are padded to
 // chunks of hs_chunk_nodes(wide) nodes (12: four NLPs per wavefront, 48: one).

@@ -1595,26 +1595,28 @@ size_t pipeline_ws_bytes(int K, long batch) {
     else if (scheme == 1) hipLaunchKernelGGL((KERNEL<1, 0>), wgrid, dim3(WIDE_THREADS), 0, stream, __VA_ARGS__);   \
     else hipLaunchKernelGGL((KERNEL<0, 0>), wgrid, dim3(WIDE_THREADS), 0, stream, __VA_ARGS__);                     \
   } while (0)
-#define PCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #call, hipGetErrorString(e_)); return ASCENT_E_HIP; } } while (0)
 
-int pipeline_run(const ascent_params *dp, long batch, int K, int scheme, int form, double *ws, const double *dguess, int warm,
-                 int max_iter, double tol, double mu0, double *dtraj, double *dtf, int *dstatus, int *diters,
-                 double *dblob, bool wide, hipStream_t stream, PipelineStats *stats, char *err, size_t errlen) {
+int pipeline_run(const Call &c, double *ws, const SolveIO &io, bool wide, PipelineStats *stats) {
+  const ascent_params *dp = c.dp;
+  const long batch = c.batch;
+  const int K = c.K, scheme = c.scheme, form = c.form, max_iter = io.max_iter;
+  const double tol = io.tol;
+  hipStream_t stream = c.stream;
   Geo g{K, (K + CHUNK - 1) / CHUNK, form, 0};
   const unsigned tiles = (unsigned)((batch + WAVE - 1) / WAVE);
   int *counters = (int *)((char *)ws + (size_t)tiles * g.tile_doubles() * sizeof(double));
   // pinned mirror of the device counters (a copy into pageable memory stalls the stream for ~20 us per burst)
   static int *host_cnt_dev[64] = {nullptr};      // per device: calls on one device are serialised by the caller's mutex
   int dev_ = 0;
-  PCHK(hipGetDevice(&dev_));
+  ASC_CHK(c.err, c.errlen, hipGetDevice(&dev_));
   dev_ &= 63;
-  if (!host_cnt_dev[dev_]) PCHK(hipHostMalloc((void **)&host_cnt_dev[dev_], 4 * sizeof(int)));
+  if (!host_cnt_dev[dev_]) ASC_CHK(c.err, c.errlen, hipHostMalloc((void **)&host_cnt_dev[dev_], 4 * sizeof(int)));
   int *host_cnt = host_cnt_dev[dev_];
   const bool debug = getenv("ASCENT_DEBUG") != nullptr;
   int launches = 0;
-  hipLaunchKernelGGL(q_init, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws, dguess, warm, mu0,
+  hipLaunchKernelGGL(q_init, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws, io.guess, io.warm, io.mu0,
                      (const double *)nullptr, (const double *)nullptr);
-  PCHK(hipGetLastError());
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   // Each round advances every lane by one stage of its own state machine: a lane in its normal flow
   // completes one interior-point iteration per round; a rejected line-search trial or a wrong-inertia
   // factorisation costs that lane (only) one more round.  Every kernel is guarded by the lanes' states, so a
@@ -1626,29 +1628,29 @@ int pipeline_run(const ascent_params *dp, long batch, int K, int scheme, int for
   int burst = 4;
   if (const char *e = getenv("ASCENT_ROUNDS_PER_SYNC")) { const int v = atoi(e); if (v >= 1 && v <= 64) burst = v; }
   for (long round = 0;;) {
-    if (round > 100L * (max_iter + 2)) { snprintf(err, errlen, "pipeline did not terminate within %ld rounds (solver condition, not a HIP error)", round); return ASCENT_E_NOTERM; }
+    if (round > 100L * (max_iter + 2)) { snprintf(c.err, c.errlen, "pipeline did not terminate within %ld rounds (solver condition, not a HIP error)", round); return ASCENT_E_NOTERM; }
     for (int r = 0; r < burst; r++, round++) {
       ASC_LAUNCH(q_trial_eval, dim3(tiles, g.nch), dp, batch, g, ws, counters);
       if (!wide) ASC_LAUNCH(q_decide_factor, dim3(tiles), dp, batch, g, ws, max_iter, tol, counters);
       const dim3 wgrid((unsigned)((batch + WIDE_NLP_PER_BLOCK - 1) / WIDE_NLP_PER_BLOCK));
       if (wide) ASC_LAUNCH_WIDE(q_factor_wide, dp, batch, g, ws, max_iter, tol, counters);
-      if (r == burst - 1) PCHK(hipMemcpyAsync(host_cnt, counters, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
+      if (r == burst - 1) ASC_CHK(c.err, c.errlen, hipMemcpyAsync(host_cnt, counters, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
       if (!wide) ASC_LAUNCH(q_forward, dim3(tiles), dp, batch, g, ws);
       else ASC_LAUNCH_WIDE(q_forward_wide, dp, batch, g, ws);
       hipLaunchKernelGGL(q_local, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws);
       if (!wide) ASC_LAUNCH(q_adjoint, dim3(tiles), dp, batch, g, ws);
       else ASC_LAUNCH_WIDE(q_adjoint_wide, dp, batch, g, ws);
       launches += 5;
-      PCHK(hipGetLastError());      // a refused launch must not hide behind the rest of the burst
+      ASC_CHK(c.err, c.errlen, hipGetLastError());      // a refused launch must not hide behind the rest of the burst
     }
-    PCHK(hipStreamSynchronize(stream));
+    ASC_CHK(c.err, c.errlen, hipStreamSynchronize(stream));
     const int n_pending = host_cnt[0], n_factored = host_cnt[1];   // retrial/refactor lanes; lanes with a step to take
     if (debug) fprintf(stderr, "[ascent pipeline] after round %ld: pending %d (refactor %d), stepping %d\n", round - 1, n_pending, host_cnt[2], n_factored);
     if (n_pending == 0 && n_factored == 0) break;
   }
-  hipLaunchKernelGGL(q_finish, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws, dtraj, dtf, dstatus, diters,
-                     dblob, getenv("ASCENT_DEBUG_ROUNDS") != nullptr);
-  PCHK(hipGetLastError());
+  hipLaunchKernelGGL(q_finish, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws, io.traj, io.tf, io.status, io.iters,
+                     io.blob, getenv("ASCENT_DEBUG_ROUNDS") != nullptr);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   if (stats) stats->launches = launches + 2;
   return ASCENT_OK;
 }
@@ -1657,16 +1659,19 @@ int pipeline_run(const ascent_params *dp, long batch, int K, int scheme, int for
 // One round of the pipeline at a caller-supplied iterate (parity surface): q_init takes the iterate as it is, then exactly
 // the kernels a solve launches per round -- q_trial_eval, the factorisation (one-lane or 16-lane), forward, q_local,
 // adjoint -- with mu and delta_w per problem from the caller; q_probe_out hands back the Newton step and/or the node rows.
-int pipeline_probe(const ascent_params *dp, long batch, int K, int scheme, int form, double *ws, const double *diterate,
-                   const double *dmu, const double *ddw, bool wide, bool step_too, double *dstep, int *dinertia,
-                   double *ddefects, double *djac, double *dhess, hipStream_t stream, char *err, size_t errlen) {
+int pipeline_probe(const Call &c, double *ws, const ProbeIO &io, bool wide) {
+  const ascent_params *dp = c.dp;
+  const long batch = c.batch;
+  const int K = c.K, scheme = c.scheme, form = c.form;
+  hipStream_t stream = c.stream;
+  const bool step_too = io.step != nullptr;
   Geo g{K, (K + CHUNK - 1) / CHUNK, form, 1};
   const unsigned tiles = (unsigned)((batch + WAVE - 1) / WAVE);
   int *counters = (int *)((char *)ws + (size_t)tiles * g.tile_doubles() * sizeof(double));
-  hipLaunchKernelGGL(q_init, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws, diterate, 2, 0.1, dmu, ddw);
-  PCHK(hipGetLastError());
+  hipLaunchKernelGGL(q_init, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws, io.iterate, 2, 0.1, io.mu, io.dw);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   ASC_LAUNCH(q_trial_eval, dim3(tiles, g.nch), dp, batch, g, ws, counters);
-  PCHK(hipGetLastError());
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   if (step_too) {
     const dim3 wgrid((unsigned)((batch + WIDE_NLP_PER_BLOCK - 1) / WIDE_NLP_PER_BLOCK));
     if (wide) {
@@ -1676,15 +1681,15 @@ int pipeline_probe(const ascent_params *dp, long batch, int K, int scheme, int f
       ASC_LAUNCH(q_decide_factor, dim3(tiles), dp, batch, g, ws, 1 << 30, -1.0, counters);
       ASC_LAUNCH(q_forward, dim3(tiles), dp, batch, g, ws);
     }
-    PCHK(hipGetLastError());
+    ASC_CHK(c.err, c.errlen, hipGetLastError());
     hipLaunchKernelGGL(q_local, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws);
     if (wide) ASC_LAUNCH_WIDE(q_adjoint_wide, dp, batch, g, ws);
     else ASC_LAUNCH(q_adjoint, dim3(tiles), dp, batch, g, ws);
-    PCHK(hipGetLastError());
+    ASC_CHK(c.err, c.errlen, hipGetLastError());
   }
-  hipLaunchKernelGGL(q_probe_out, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws, step_too ? dstep : nullptr,
-                     step_too ? dinertia : nullptr, ddefects, djac, dhess);
-  PCHK(hipGetLastError());
+  hipLaunchKernelGGL(q_probe_out, dim3(tiles, g.nch), dim3(WAVE), 0, stream, dp, batch, g, ws, io.step,
+                     step_too ? io.inertia : nullptr, io.defects, io.jac, io.hess);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 

@@ -258,10 +258,11 @@ int sens_problems_per_group(long batch) {
   return pb;
 }
 
-#define SCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #call, hipGetErrorString(e_)); return ASCENT_E_HIP; } } while (0)
-
-int sens_run(const ascent_params *dp, long batch, int K, int scheme, int formulation, int terminal, int move_penalty,
-             const double *dblob, double *dgrad, hipStream_t stream, char *err, size_t errlen) {
+int sens_run(const Call &c, int terminal, const double *dblob, double *dgrad) {
+  const ascent_params *dp = c.dp;
+  const long batch = c.batch;
+  const int K = c.K, scheme = c.scheme, formulation = c.form, move_penalty = c.mp;
+  hipStream_t stream = c.stream;
   const int pb = sens_problems_per_group(batch);
   const dim3 grid((unsigned)((batch + pb - 1) / pb)), block(SB);
   if (scheme == 0 && formulation == 1)
@@ -272,7 +273,7 @@ int sens_run(const ascent_params *dp, long batch, int K, int scheme, int formula
     hipLaunchKernelGGL((s_sens<1, 0>), grid, block, 0, stream, dp, batch, K, pb, terminal, move_penalty, dblob, dgrad);
   else
     hipLaunchKernelGGL((s_sens<2, 0>), grid, block, 0, stream, dp, batch, K, pb, terminal, move_penalty, dblob, dgrad);
-  SCHK(hipGetLastError());
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 

@@ -3,14 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "ascent.h"
+#include "ascent_host.hpp"
 
 namespace ascent {
 
 // dJ*/dp of every NLP at its solution blob (envelope theorem; include/ascent.h: ascent_param_sensitivity).  Device pointers:
-// dp[batch], dblob [21K+10][batch], dgrad [16][batch].  Options already checked by the caller (schemes 0/1/2, formulation 1 with
-// scheme 0 only, terminals 0/1/2).  Only enqueues on `stream`.  Returns ASCENT_OK / ASCENT_E_HIP.
-int sens_run(const ascent_params *dp, long batch, int K, int scheme, int formulation, int terminal, int move_penalty,
-             const double *dblob, double *dgrad, hipStream_t stream, char *err, size_t errlen);
+// c.dp[batch], dblob [21K+10][batch], dgrad [16][batch].  Options already checked by the caller (schemes 0/1/2, formulation 1 with
+// scheme 0 only).  terminal: ascent_opts.terminal itself, 0/1/2 (the chain rule of terminal 1 is the kernel's own; c.dp are the
+// caller's parameters).  Only enqueues on c.stream.  Returns ASCENT_OK / ASCENT_E_HIP.
+int sens_run(const Call &c, int terminal, const double *dblob, double *dgrad);
 
 // problems per workgroup of sens_run for a batch (a power of two, 1 .. 64; the rest of the workgroup's lanes split the steps)
 int sens_problems_per_group(long batch);

@@ -3,8 +3,10 @@
 // m.solve() call at Launch_Optimiser.py:177 (GEKKO -> APMonitor -> IPOPT/MUMPS).
 //
 // This file is the C ABI (include/ascent.h): argument checks, workspaces, staging of host pointers, the nested
-// iteration over grid levels, and route(), which picks the kernel family of a call.  The families sit behind their
-// own host interfaces:
+// iteration over grid levels, and route(), which picks the kernel family of a call.  Every entry point refuses argument errors
+// first, then looks at the device, then takes the device's lock; it describes the call to the families in one Call
+// (ascent_host.hpp), and the entry points that allocate per call stage host pointers through one Staging.  The families sit
+// behind their own host interfaces:
 //   persistent p_solve / h_solve    ascent_persist.hpp (ascent_persist.hip, ascent_hs.hip)
 //   dense blocks d_* / pc_*         ascent_dense.hpp (ascent_dense.hip, ascent_blocktri.hip)
 //   split pipeline q_*              ascent_pipeline.hpp (ascent_pipeline.hip)
@@ -22,6 +24,7 @@
 #include <cmath>
 
 #include "ascent.h"
+#include "ascent_host.hpp"
 #include "ascent_device.hpp"
 #include "ascent_tile.hpp"
 #include "ascent_pipeline.hpp"
@@ -42,11 +45,7 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 thread_local char g_err[512] = "";
 
-int hip_fail(hipError_t e, const char *what) {
-  snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-  return ASCENT_E_HIP;
-}
-#define HIPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail(e_, #call); } while (0)
+#define HIPCHK(call) ASC_CHK(g_err, sizeof g_err, call)
 
 // ---------------------------------------------------------------------------------------------
 // Nested iteration (mesh continuation).  A cold start on a grid of >= 40 nodes first solves the same NLP on a
@@ -153,7 +152,7 @@ struct Route {
   bool wide;      // ASCENT_PATH_PERSIST: one NLP per wavefront (else four)
 };
 
-// What a kernel family does not carry (beyond the option checks of check_common): nullptr, or the reason for refusing the call.
+// What a kernel family does not carry (beyond the option checks of check_options): nullptr, or the reason for refusing the call.
 const char *unsupported(int path, const ascent_opts *o) {
   switch (path) {
     case ASCENT_PATH_PERSIST:      // backward Euler (both formulations), the trapezoid, Hermite-Simpson without the move penalty
@@ -324,11 +323,6 @@ int check_options(const ascent_params *p, int64_t batch, const ascent_opts *o) {
   if (o->move_penalty != 0 && o->move_penalty != 1) { snprintf(g_err, sizeof g_err, "move_penalty must be 0 or 1"); return ASCENT_E_ARG; }
   return 0;
 }
-int check_common(const ascent_params *p, int64_t batch, const ascent_opts *o, int device_id) {
-  if (const int rc = check_options(p, batch, o)) return rc;
-  return check_device(device_id);
-}
-
 // move_penalty = 1 on host-resident parameter sets: every weight must be positive
 int check_dcost(const ascent_params *p, int64_t batch) {
   for (int64_t i = 0; i < batch; i++)
@@ -346,11 +340,71 @@ size_t ws_bytes(const Route &r, int K, int64_t batch, int mp) {
   }
 }
 
-template <typename T>
-struct DevBuf {  // device staging buffer for host-pointer calls
-  T *d = nullptr;
-  ~DevBuf() { if (d) (void)hipFree(d); }
-  hipError_t alloc(size_t n) { return hipMalloc(&d, n * sizeof(T)); }
+// What ascent_solve_batch can solve for this batch, for every entry point that takes a solve's options: the route of the
+// solve, what its family does not carry, and (host-resident parameter sets only) the weights of the move penalty.
+int check_solvable(const ascent_params *p, int64_t batch, const ascent_opts *o, int ptr_is_device, Route *route_out = nullptr) {
+  const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
+  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
+  // (device-resident parameter sets are the caller's to check: the weight must be positive)
+  if (o->move_penalty && !ptr_is_device) if (const int rc = check_dcost(p, batch)) return rc;
+  if (route_out) *route_out = r;
+  return 0;
+}
+
+Call call_of(const ascent_params *dp, int64_t batch, const ascent_opts *o, hipStream_t stream) {
+  return ascent::call_of(dp, (long)batch, o, stream, g_err, sizeof g_err);
+}
+
+// Device copies of the arrays of a host-pointer call, freed when the call returns.  With device pointers every member hands
+// its argument back.  The first failure is kept: ask failed() before launching on what in / out / scratch returned.
+class Staging {
+ public:
+  Staging(hipStream_t stream, int ptr_is_device) : stream_(stream), device_(ptr_is_device != 0) {}
+  ~Staging() { for (void *d : owned_) (void)hipFree(d); }
+  Staging(const Staging &) = delete;
+  Staging &operator=(const Staging &) = delete;
+  template <typename T>
+  T *scratch(size_t n) {      // device memory of this call, neither copied in nor out
+    void *d = nullptr;
+    if (rc_ || note(hipMalloc(&d, n * sizeof(T)), "staging hipMalloc")) return nullptr;
+    owned_.push_back(d);
+    return (T *)d;
+  }
+  template <typename T>
+  const T *in(const T *p, size_t n) {      // the copy is enqueued on the stream
+    if (device_ || !p) return p;
+    T *d = scratch<T>(n);
+    if (d) note(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, stream_), "staging hipMemcpyAsync");
+    return d;
+  }
+  template <typename T>
+  T *out(T *p, size_t n) {      // null stays null: an optional output the caller did not ask for
+    if (device_ || !p) return p;
+    T *d = scratch<T>(n);
+    if (d) outs_.push_back({p, d, n * sizeof(T)});
+    return d;
+  }
+  int failed() const { return rc_; }
+  // Host pointers: the outputs back in the order they were registered, then wait for the stream.  Device pointers: the call
+  // stays asynchronous on a caller's stream; the null stream is waited for.
+  int finish() {
+    if (rc_) return rc_;
+    for (const Out &o : outs_) HIPCHK(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, stream_));
+    if (!device_ || !stream_) HIPCHK(hipStreamSynchronize(stream_));
+    return ASCENT_OK;
+  }
+
+ private:
+  struct Out { void *host, *dev; size_t bytes; };
+  int note(hipError_t e, const char *what) {
+    if (e != hipSuccess) { snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e)); rc_ = ASCENT_E_HIP; }
+    return rc_;
+  }
+  hipStream_t stream_;
+  bool device_;
+  int rc_ = 0;
+  std::vector<void *> owned_;
+  std::vector<Out> outs_;
 };
 
 }  // namespace
@@ -418,20 +472,19 @@ int ascent_solve_batch(const ascent_params *p, int64_t batch, const ascent_opts 
                        const double *guess, double *traj_out, double *tf_out, int32_t *status_out,
                        int32_t *iters_out, double *sol_blob_out, int device_id, void *stream_,
                        int ptr_is_device) {
-  int rc = check_common(p, batch, o, device_id);
+  int rc = check_options(p, batch, o);
   if (rc) return rc;
   if (!tf_out || !status_out || !iters_out) { snprintf(g_err, sizeof g_err, "null output pointer"); return ASCENT_E_ARG; }
   if (o->warm_start < 0 || o->warm_start > 2 || (o->warm_start && !guess)) { snprintf(g_err, sizeof g_err, "warm_start needs a guess blob"); return ASCENT_E_ARG; }
   if (!(o->tol > 0) || o->max_iter < 0) { snprintf(g_err, sizeof g_err, "tol must be > 0, max_iter >= 0"); return ASCENT_E_ARG; }
-  // (device-resident parameter sets are the caller's to check: the weight must be positive)
-  if (o->move_penalty && !ptr_is_device && (rc = check_dcost(p, batch))) return rc;
+  Route r{};
+  if ((rc = check_solvable(p, batch, o, ptr_is_device, &r))) return rc;
+  if ((rc = check_device(device_id))) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   hipStream_t stream = (hipStream_t)stream_;
   const int K = o->n_nodes - 1, nt = o->n_nodes;
   const size_t rows = 21 * (size_t)K + NSC;
-  const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
-  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
   const bool persist = r.path == ASCENT_PATH_PERSIST;
   int levels[8];
   const int nlev = nested_levels(o, levels);
@@ -486,34 +539,29 @@ int ascent_solve_batch(const ascent_params *p, int64_t batch, const ascent_opts 
   HIPCHK(hipEventRecord(w.ev0, stream));
   double mu_first = o->move_penalty ? NESTED_MU_FIRST_MP : NESTED_MU_FIRST, mu_next = o->move_penalty ? nested_mu_next_mp(o->tol) : nested_mu_next(o->tol);
   if (const char *e = getenv("ASCENT_NESTED_MU")) sscanf(e, "%lf,%lf", &mu_first, &mu_next);      // experiments only ("first,next")
+  const Call c = call_of(dp, batch, o, stream);
+  const double tol_coarse = fmax(o->tol, NESTED_COARSE_TOL);
   if (persist) {      // all levels inside the kernel's own layout
-    rc = persist_run_nested(dp, (long)batch, (int)o->scheme, (int)o->formulation, (int)o->move_penalty, o->terminal == 2 ? 2 : 0, r.wide, levels, nlev, w.ws, dguess, (int)o->warm_start, (int)o->max_iter, o->tol,
-                            fmax(o->tol, NESTED_COARSE_TOL), mu0, mu_first, mu_next, dtraj, dtf, dstatus, diters,
-                            dblob, stream, g_err, sizeof g_err);
-    if (rc) return rc;
+    const SolveIO io{dguess, (int)o->warm_start, (int)o->max_iter, o->tol, mu0, dtraj, dtf, dstatus, diters, dblob};
+    if ((rc = persist_run_nested(c, r.wide, levels, nlev, w.ws, io, tol_coarse, mu_first, mu_next))) return rc;
   }
   for (int l = nlev - 1; l >= 0 && !persist; l--) {
-    const int Kl = levels[l] - 1;
     const bool fin = l == 0, first = l == nlev - 1;
-    const double *g_l = first ? dguess : w.gss;
-    const int warm_l = first ? (int)o->warm_start : 2;
-    const double mu_l = first ? mu0 : (l == nlev - 2 ? mu_first : mu_next);
-    const double tol_l = fin ? o->tol : fmax(o->tol, NESTED_COARSE_TOL);
-    double *traj_l = fin ? dtraj : nullptr, *tf_l = fin ? dtf : w.tfc, *blob_l = fin ? dblob : w.sol;
-    int *st_l = fin ? dstatus : w.st_c, *it_l = fin ? diters : w.it_c;
-    if (r.path == ASCENT_PATH_DENSE)
-      rc = dense_run(dp, (long)batch, Kl, (int)o->scheme, o->terminal == 2 ? 2 : 0, w.ws, g_l, warm_l, (int)o->max_iter, tol_l, mu_l, traj_l, tf_l, st_l,
-                     it_l, blob_l, stream, g_err, sizeof g_err, r.pcr ? 1 : 0, (int)o->move_penalty);
-    else if (r.path == ASCENT_PATH_FUSED)
-      rc = fused_run(dp, (long)batch, Kl, w.ws, g_l, warm_l, (int)o->max_iter, tol_l, mu_l, traj_l, tf_l, st_l, it_l, blob_l, stream, g_err, sizeof g_err);
-    else
-      rc = pipeline_run(dp, (long)batch, Kl, (int)o->scheme, (int)o->formulation, w.ws, g_l, warm_l, (int)o->max_iter, tol_l, mu_l,
-                        traj_l, tf_l, st_l, it_l, blob_l, r.path == ASCENT_PATH_SPLIT_WIDE, stream, nullptr, g_err, sizeof g_err);
+    Call cl = c;
+    cl.K = levels[l] - 1;
+    const SolveIO io{first ? dguess : w.gss, first ? (int)o->warm_start : 2, (int)o->max_iter, fin ? o->tol : tol_coarse,
+                     first ? mu0 : (l == nlev - 2 ? mu_first : mu_next), fin ? dtraj : nullptr, fin ? dtf : w.tfc,
+                     fin ? dstatus : w.st_c, fin ? diters : w.it_c, fin ? dblob : w.sol};
+    switch (r.path) {
+      case ASCENT_PATH_DENSE: rc = dense_run(cl, w.ws, io, r.pcr); break;
+      case ASCENT_PATH_FUSED: rc = fused_run(cl, w.ws, io); break;
+      default: rc = pipeline_run(cl, w.ws, io, r.path == ASCENT_PATH_SPLIT_WIDE, nullptr);
+    }
     if (rc) return rc;
     if (!fin) {
       const int Kf = levels[l - 1] - 1;
       hipLaunchKernelGGL(k_prolong, dim3((unsigned)((batch + WAVE - 1) / WAVE), (unsigned)Kf), dim3(WAVE), 0, stream, w.sol,
-                         w.st_c, w.it_c, Kl, w.gss, Kf, (long)batch, (int)o->formulation, w.acc, first ? 1 : 0);
+                         w.st_c, w.it_c, cl.K, w.gss, Kf, (long)batch, (int)o->formulation, w.acc, first ? 1 : 0);
       HIPCHK(hipGetLastError());
     }
   }
@@ -552,7 +600,7 @@ int ascent_default_path(int64_t batch, const ascent_opts *o) {
 
 int ascent_eval_nodes_path(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,
                            double *defects, double *jac_blocks, double *hess_blocks, int device_id, int path) {
-  int rc = check_common(p, batch, o, device_id);
+  int rc = check_options(p, batch, o);
   if (rc) return rc;
   if (o->move_penalty) { snprintf(g_err, sizeof g_err, "the parity surfaces take the unpenalised NLP only (move_penalty = 1 is an option of ascent_solve_batch)"); return ASCENT_E_ARG; }
   if (!iterate || !defects || !jac_blocks || !hess_blocks) { snprintf(g_err, sizeof g_err, "null pointer"); return ASCENT_E_ARG; }
@@ -563,36 +611,33 @@ int ascent_eval_nodes_path(const ascent_params *p, int64_t batch, const ascent_o
   ascent_opts rows_o = *o;
   rows_o.terminal = 0;      // (the node rows do not see the terminal condition)
   if (const char *why = unsupported(r.path, &rows_o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
+  if ((rc = check_device(device_id))) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
-  { const int rc0 = claim_slot0(device_id); if (rc0) return rc0; }
+  if ((rc = claim_slot0(device_id))) return rc;
   const int K = o->n_nodes - 1;
-  const size_t rows = 21 * (size_t)K + NSC;
-  DevBuf<ascent_params> bp;
-  DevBuf<double> bit, bd, bj, bh, bz;
-  HIPCHK(bp.alloc(batch)); HIPCHK(bit.alloc(rows * batch));
-  HIPCHK(bd.alloc((size_t)7 * K * batch)); HIPCHK(bj.alloc((size_t)8 * K * batch)); HIPCHK(bh.alloc((size_t)10 * K * batch));
-  HIPCHK(hipMemcpy(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(bit.d, iterate, rows * batch * sizeof(double), hipMemcpyHostToDevice));
+  Staging st(nullptr, 0);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, &rows_o, nullptr);
+  ProbeIO io{};
+  io.iterate = st.in(iterate, (21 * (size_t)K + NSC) * batch);
+  io.defects = st.out(defects, (size_t)7 * K * batch);
+  io.jac = st.out(jac_blocks, (size_t)8 * K * batch);
+  io.hess = st.out(hess_blocks, (size_t)10 * K * batch);
+  double *ws = nullptr;
   if (r.path != ASCENT_PATH_FUSED) {      // (k_eval_nodes needs no workspace)
-    rc = ensure_ws(g_ws_slot0(device_id), ws_bytes(r, K, batch, 0));
-    if (rc) return rc;
-    HIPCHK(bz.alloc(batch));                       // mu, delta_w: not used by the node evaluation
-    HIPCHK(hipMemset(bz.d, 0, batch * sizeof(double)));
+    if ((rc = ensure_ws(g_ws_slot0(device_id), ws_bytes(r, K, batch, 0)))) return rc;
+    ws = g_ws_slot0(device_id).ws;
+    double *zero = st.scratch<double>((size_t)batch);      // mu, delta_w: not used by the node evaluation
+    if (zero) HIPCHK(hipMemset(zero, 0, batch * sizeof(double)));
+    io.mu = io.dw = zero;
   }
-  if (r.path == ASCENT_PATH_FUSED)
-    rc = fused_eval_nodes(bp.d, (long)batch, K, bit.d, bd.d, bj.d, bh.d, 0, g_err, sizeof g_err);
-  else if (r.path == ASCENT_PATH_PERSIST)
-    rc = persist_probe_rows(bp.d, (long)batch, (int)o->scheme, (int)o->formulation, r.wide, K, g_ws_slot0(device_id).ws, bit.d, bz.d, bd.d, bj.d, bh.d, 0,
-                            g_err, sizeof g_err);
-  else
-    rc = pipeline_probe(bp.d, (long)batch, K, (int)o->scheme, (int)o->formulation, g_ws_slot0(device_id).ws, bit.d, bz.d, bz.d,
-                        r.path == ASCENT_PATH_SPLIT_WIDE, false, nullptr, nullptr, bd.d, bj.d, bh.d, 0, g_err, sizeof g_err);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(defects, bd.d, (size_t)7 * K * batch * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(jac_blocks, bj.d, (size_t)8 * K * batch * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(hess_blocks, bh.d, (size_t)10 * K * batch * sizeof(double), hipMemcpyDeviceToHost));
-  return ASCENT_OK;
+  if ((rc = st.failed())) return rc;
+  switch (r.path) {
+    case ASCENT_PATH_FUSED: rc = fused_eval_nodes(c, io); break;
+    case ASCENT_PATH_PERSIST: rc = persist_probe_rows(c, r.wide, ws, io); break;
+    default: rc = pipeline_probe(c, ws, io, r.path == ASCENT_PATH_SPLIT_WIDE);
+  }
+  return rc ? rc : st.finish();
 }
 
 int ascent_eval_nodes(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,
@@ -600,85 +645,80 @@ int ascent_eval_nodes(const ascent_params *p, int64_t batch, const ascent_opts *
   return ascent_eval_nodes_path(p, batch, o, iterate, defects, jac_blocks, hess_blocks, device_id, ASCENT_PATH_AUTO);
 }
 
+// ascent_opts.terminal = 1 on a parity surface: in place on the call's private copy of the parameters
+static int terminal_params_in_place(const ascent_opts *o, const ascent_params *dp, int64_t batch) {
+  if (o->terminal != 1) return 0;
+  hipLaunchKernelGGL(k_terminal_params, dim3((unsigned)((batch + WAVE - 1) / WAVE)), dim3(WAVE), 0, 0, dp, const_cast<ascent_params *>(dp), (long)batch);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int ascent_kkt_step_path(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,
                          const double *mu, const double *delta_w, double *step, int32_t *inertia_out, int device_id,
                          int path) {
-  int rc = check_common(p, batch, o, device_id);
+  int rc = check_options(p, batch, o);
   if (rc) return rc;
   if (!iterate || !mu || !delta_w || !step || !inertia_out) { snprintf(g_err, sizeof g_err, "null pointer"); return ASCENT_E_ARG; }
   if (path < ASCENT_PATH_AUTO || path > ASCENT_PATH_PERSIST) { snprintf(g_err, sizeof g_err, "unknown path %d", path); return ASCENT_E_ARG; }
   const Route r = route(o, batch, path, true);
   if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
   if (o->move_penalty && (rc = check_dcost(p, batch))) return rc;
+  if ((rc = check_device(device_id))) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
-  { const int rc0 = claim_slot0(device_id); if (rc0) return rc0; }
+  if ((rc = claim_slot0(device_id))) return rc;
   const int K = o->n_nodes - 1;
   const size_t rows = 21 * (size_t)K + NSC;
-  rc = ensure_ws(g_ws_slot0(device_id), ws_bytes(r, K, batch, (int)o->move_penalty));
-  if (rc) return rc;
-  DevBuf<ascent_params> bp;
-  DevBuf<double> bit, bmu, bdw, bst;
-  DevBuf<int> bin;
-  HIPCHK(bp.alloc(batch)); HIPCHK(bit.alloc(rows * batch)); HIPCHK(bmu.alloc(batch)); HIPCHK(bdw.alloc(batch));
-  HIPCHK(bst.alloc(rows * batch)); HIPCHK(bin.alloc(batch));
-  HIPCHK(hipMemcpy(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(bit.d, iterate, rows * batch * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(bmu.d, mu, batch * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(bdw.d, delta_w, batch * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(bst.d, 0, rows * batch * sizeof(double)));
-  if (o->terminal == 1) {     // in place on the private copy
-    hipLaunchKernelGGL(k_terminal_params, dim3((unsigned)((batch + WAVE - 1) / WAVE)), dim3(WAVE), 0, 0, bp.d, bp.d, (long)batch);
-    HIPCHK(hipGetLastError());
-  }
+  if ((rc = ensure_ws(g_ws_slot0(device_id), ws_bytes(r, K, batch, (int)o->move_penalty)))) return rc;
   double *ws = g_ws_slot0(device_id).ws;
-  if (r.path == ASCENT_PATH_DENSE)
-    rc = dense_probe(bp.d, (long)batch, K, (int)o->scheme, o->terminal == 2 ? 2 : 0, ws, bit.d, bmu.d, bdw.d, true, bst.d, bin.d, nullptr,
-                     0, g_err, sizeof g_err, r.pcr ? 1 : 0, (int)o->move_penalty);
-  else if (r.path == ASCENT_PATH_PERSIST)
-    rc = persist_probe(bp.d, (long)batch, (int)o->scheme, (int)o->formulation, (int)o->move_penalty, o->terminal == 2 ? 2 : 0, r.wide, K, ws, bit.d, bmu.d, bdw.d,
-                       bst.d, bin.d, 0, g_err, sizeof g_err);
-  else if (r.path == ASCENT_PATH_FUSED)
-    rc = fused_probe(bp.d, (long)batch, K, ws, bit.d, bmu.d, bdw.d, bst.d, bin.d, 0, g_err, sizeof g_err);
-  else
-    rc = pipeline_probe(bp.d, (long)batch, K, (int)o->scheme, (int)o->formulation, ws, bit.d, bmu.d, bdw.d,
-                        r.path == ASCENT_PATH_SPLIT_WIDE, true, bst.d, bin.d, nullptr, nullptr, nullptr, 0, g_err, sizeof g_err);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(step, bst.d, rows * batch * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(inertia_out, bin.d, batch * sizeof(int), hipMemcpyDeviceToHost));
+  Staging st(nullptr, 0);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, o, nullptr);
+  ProbeIO io{};
+  io.iterate = st.in(iterate, rows * batch);
+  io.mu = st.in(mu, (size_t)batch);
+  io.dw = st.in(delta_w, (size_t)batch);
+  io.step = st.out(step, rows * batch);
+  io.inertia = st.out(inertia_out, (size_t)batch);
+  if ((rc = st.failed())) return rc;
+  HIPCHK(hipMemset(io.step, 0, rows * batch * sizeof(double)));
+  if ((rc = terminal_params_in_place(o, c.dp, batch))) return rc;
+  switch (r.path) {
+    case ASCENT_PATH_DENSE: rc = dense_probe(c, ws, io, r.pcr); break;
+    case ASCENT_PATH_PERSIST: rc = persist_probe(c, r.wide, ws, io); break;
+    case ASCENT_PATH_FUSED: rc = fused_probe(c, ws, io); break;
+    default: rc = pipeline_probe(c, ws, io, r.path == ASCENT_PATH_SPLIT_WIDE);
+  }
+  if (rc || (rc = st.finish())) return rc;
   for (int64_t q = 0; q < batch; q++) inertia_out[q] = inertia_out[q] != 0;     // (the dense path reports a status code)
   return ASCENT_OK;
 }
 
 int ascent_dense_records(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,
                          double *records, int device_id) {
-  int rc = check_common(p, batch, o, device_id);
+  int rc = check_options(p, batch, o);
   if (rc) return rc;
   if (o->move_penalty) { snprintf(g_err, sizeof g_err, "the parity surfaces take the unpenalised NLP only (move_penalty = 1 is an option of ascent_solve_batch)"); return ASCENT_E_ARG; }
   if (!iterate || !records) { snprintf(g_err, sizeof g_err, "null pointer"); return ASCENT_E_ARG; }
   if (const char *why = unsupported(ASCENT_PATH_DENSE, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
+  if ((rc = check_device(device_id))) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
-  { const int rc0 = claim_slot0(device_id); if (rc0) return rc0; }
+  if ((rc = claim_slot0(device_id))) return rc;
   const int K = o->n_nodes - 1;
-  const size_t rows = 21 * (size_t)K + NSC, nrec = (size_t)batch * K * 6 * 64;
-  rc = ensure_ws(g_ws_slot0(device_id), dense_ws_bytes(K, (long)batch));
-  if (rc) return rc;
-  DevBuf<ascent_params> bp;
-  DevBuf<double> bit, bz, br;
-  HIPCHK(bp.alloc(batch)); HIPCHK(bit.alloc(rows * batch)); HIPCHK(bz.alloc(batch)); HIPCHK(br.alloc(nrec));
-  HIPCHK(hipMemcpy(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(bit.d, iterate, rows * batch * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(bz.d, 0, batch * sizeof(double)));
-  if (o->terminal == 1) {
-    hipLaunchKernelGGL(k_terminal_params, dim3((unsigned)((batch + WAVE - 1) / WAVE)), dim3(WAVE), 0, 0, bp.d, bp.d, (long)batch);
-    HIPCHK(hipGetLastError());
-  }
-  rc = dense_probe(bp.d, (long)batch, K, (int)o->scheme, 0, g_ws_slot0(device_id).ws, bit.d, bz.d, bz.d, false, nullptr, nullptr, br.d, 0,
-                   g_err, sizeof g_err);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(records, br.d, nrec * sizeof(double), hipMemcpyDeviceToHost));
-  return ASCENT_OK;
+  if ((rc = ensure_ws(g_ws_slot0(device_id), dense_ws_bytes(K, (long)batch)))) return rc;
+  Staging st(nullptr, 0);
+  Call c = call_of(st.in(p, (size_t)batch), batch, o, nullptr);
+  c.term = 0;      // (the stage records do not see the terminal condition)
+  ProbeIO io{};
+  io.iterate = st.in(iterate, (21 * (size_t)K + NSC) * batch);
+  io.records = st.out(records, (size_t)batch * K * 6 * 64);
+  double *zero = st.scratch<double>((size_t)batch);      // mu, delta_w: not used by the records
+  if ((rc = st.failed())) return rc;
+  HIPCHK(hipMemset(zero, 0, batch * sizeof(double)));
+  io.mu = io.dw = zero;
+  if ((rc = terminal_params_in_place(o, c.dp, batch))) return rc;
+  if ((rc = dense_probe(c, g_ws_slot0(device_id).ws, io, false))) return rc;
+  return st.finish();
 }
 
 int ascent_coast_batch(const ascent_params *p, int64_t batch, const double *final_state, int32_t coast_nodes,
@@ -686,99 +726,59 @@ int ascent_coast_batch(const ascent_params *p, int64_t batch, const double *fina
                        int ptr_is_device) {
   if (!p || batch <= 0 || !final_state || !coast_traj || !coast_tf || !apsides) { snprintf(g_err, sizeof g_err, "null pointer or batch <= 0"); return ASCENT_E_ARG; }
   if (coast_nodes < 1 || coast_nodes > 65535) { snprintf(g_err, sizeof g_err, "coast_nodes out of range (1 .. 65535)"); return ASCENT_E_ARG; }
-  if (const int rc0 = check_device(device_id)) return rc0;
+  int rc = check_device(device_id);
+  if (rc) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   hipStream_t stream = (hipStream_t)stream_;
-  const size_t nco = (size_t)4 * (coast_nodes + 1) * batch;
-  if (ptr_is_device) {
-    int rc = coast_run(p, (long)batch, final_state, coast_nodes, coast_traj, coast_tf, apsides, stream, g_err, sizeof g_err);
-    if (rc) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(stream));
-    return ASCENT_OK;
-  }
-  DevBuf<ascent_params> bp;
-  DevBuf<double> bs, bc, bt, ba;
-  HIPCHK(bp.alloc(batch)); HIPCHK(bs.alloc((size_t)4 * batch)); HIPCHK(bc.alloc(nco)); HIPCHK(bt.alloc(batch)); HIPCHK(ba.alloc((size_t)2 * batch));
-  HIPCHK(hipMemcpyAsync(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(bs.d, final_state, (size_t)4 * batch * sizeof(double), hipMemcpyHostToDevice, stream));
-  int rc = coast_run(bp.d, (long)batch, bs.d, coast_nodes, bc.d, bt.d, ba.d, stream, g_err, sizeof g_err);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(coast_traj, bc.d, nco * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(coast_tf, bt.d, batch * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(apsides, ba.d, (size_t)2 * batch * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  return ASCENT_OK;
+  Staging st(stream, ptr_is_device);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, nullptr, stream);
+  const double *ds = st.in(final_state, (size_t)4 * batch);
+  double *dc = st.out(coast_traj, (size_t)4 * (coast_nodes + 1) * batch), *dt = st.out(coast_tf, (size_t)batch), *da = st.out(apsides, (size_t)2 * batch);
+  if ((rc = st.failed()) || (rc = coast_run(c, ds, coast_nodes, dc, dt, da))) return rc;
+  return st.finish();
 }
 
 int ascent_param_sensitivity(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
                              double *grad_out, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_common(p, batch, o, device_id);
+  int rc = check_options(p, batch, o);
   if (rc) return rc;
   if (!sol_blob || !grad_out) { snprintf(g_err, sizeof g_err, "null solution blob or output pointer"); return ASCENT_E_ARG; }
-  // the options ascent_solve_batch refuses for this batch are refused here: the same route, the same check
-  const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
-  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
-  if (o->move_penalty && !ptr_is_device && (rc = check_dcost(p, batch))) return rc;
+  if ((rc = check_solvable(p, batch, o, ptr_is_device)) || (rc = check_device(device_id))) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   hipStream_t stream = (hipStream_t)stream_;
-  const int K = o->n_nodes - 1;
-  if (ptr_is_device) {
-    rc = sens_run(p, (long)batch, K, o->scheme, o->formulation, o->terminal, o->move_penalty, sol_blob, grad_out, stream, g_err, sizeof g_err);
-    if (rc) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(stream));
-    return ASCENT_OK;
-  }
-  const size_t nb = (21 * (size_t)K + NSC) * batch, ng = (size_t)16 * batch;
-  DevBuf<ascent_params> bp;
-  DevBuf<double> bb, bg;
-  HIPCHK(bp.alloc(batch)); HIPCHK(bb.alloc(nb)); HIPCHK(bg.alloc(ng));
-  HIPCHK(hipMemcpyAsync(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(bb.d, sol_blob, nb * sizeof(double), hipMemcpyHostToDevice, stream));
-  rc = sens_run(bp.d, (long)batch, K, o->scheme, o->formulation, o->terminal, o->move_penalty, bb.d, bg.d, stream, g_err, sizeof g_err);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(grad_out, bg.d, ng * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  return ASCENT_OK;
+  Staging st(stream, ptr_is_device);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
+  const double *db = st.in(sol_blob, (21 * (size_t)c.K + NSC) * batch);
+  double *dg = st.out(grad_out, (size_t)16 * batch);
+  if ((rc = st.failed()) || (rc = sens_run(c, o->terminal, db, dg))) return rc;
+  return st.finish();
 }
+
+namespace {
+int check_substeps(int32_t substeps) {
+  if (substeps < 0 || substeps > ASCENT_FLIGHT_MAX_SUBSTEPS) { snprintf(g_err, sizeof g_err, "substeps out of range (0 = automatic, 1 .. %d)", ASCENT_FLIGHT_MAX_SUBSTEPS); return ASCENT_E_ARG; }
+  return 0;
+}
+}  // namespace
 
 int ascent_fly_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
                      double *flown_traj, double *local_err, double *summary, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_common(p, batch, o, device_id);
+  int rc = check_options(p, batch, o);
   if (rc) return rc;
   if (!sol_blob || !summary) { snprintf(g_err, sizeof g_err, "null solution blob or summary pointer"); return ASCENT_E_ARG; }
-  if (substeps < 0 || substeps > ASCENT_FLIGHT_MAX_SUBSTEPS) { snprintf(g_err, sizeof g_err, "substeps out of range (0 = automatic, 1 .. %d)", ASCENT_FLIGHT_MAX_SUBSTEPS); return ASCENT_E_ARG; }
-  // the options ascent_solve_batch refuses for this batch are refused here: the same route, the same check
-  const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
-  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
-  if (o->move_penalty && !ptr_is_device && (rc = check_dcost(p, batch))) return rc;
+  if ((rc = check_substeps(substeps)) || (rc = check_solvable(p, batch, o, ptr_is_device)) || (rc = check_device(device_id))) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
   hipStream_t stream = (hipStream_t)stream_;
-  const int K = o->n_nodes - 1;
-  if (ptr_is_device) {
-    rc = flight_run(p, (long)batch, K, o->formulation, substeps, sol_blob, flown_traj, local_err, summary, stream, g_err, sizeof g_err);
-    if (rc) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(stream));
-    return ASCENT_OK;
-  }
-  const size_t nb = (21 * (size_t)K + NSC) * batch, ntr = (size_t)ASCENT_TRAJ_FIELDS * o->n_nodes * batch, nl = (size_t)7 * K * batch,
-               ns = (size_t)ASCENT_FLIGHT_ROWS * batch;
-  DevBuf<ascent_params> bp;
-  DevBuf<double> bb, bt, bl, bs;
-  HIPCHK(bp.alloc(batch)); HIPCHK(bb.alloc(nb)); HIPCHK(bs.alloc(ns));
-  if (flown_traj) HIPCHK(bt.alloc(ntr));
-  if (local_err) HIPCHK(bl.alloc(nl));
-  HIPCHK(hipMemcpyAsync(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(bb.d, sol_blob, nb * sizeof(double), hipMemcpyHostToDevice, stream));
-  rc = flight_run(bp.d, (long)batch, K, o->formulation, substeps, bb.d, bt.d, bl.d, bs.d, stream, g_err, sizeof g_err);
-  if (rc) return rc;
-  if (flown_traj) HIPCHK(hipMemcpyAsync(flown_traj, bt.d, ntr * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (local_err) HIPCHK(hipMemcpyAsync(local_err, bl.d, nl * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(summary, bs.d, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  return ASCENT_OK;
+  Staging st(stream, ptr_is_device);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
+  const double *db = st.in(sol_blob, (21 * (size_t)c.K + NSC) * batch);
+  double *dt = st.out(flown_traj, (size_t)ASCENT_TRAJ_FIELDS * o->n_nodes * batch), *dl = st.out(local_err, (size_t)7 * c.K * batch);
+  double *ds = st.out(summary, (size_t)ASCENT_FLIGHT_ROWS * batch);
+  if ((rc = st.failed()) || (rc = flight_run(c, substeps, db, dt, dl, ds))) return rc;
+  return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -812,24 +812,21 @@ int trim_ws_release(int dev, hipStream_t stream) {
   return 0;
 }
 
-// what ascent_fly_batch refuses, plus terminal = 2; every argument error before the device is looked at
+// what ascent_fly_batch refuses, plus terminal = 2
 int check_flight_like(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
-                      int device_id, int ptr_is_device) {
+                      int ptr_is_device) {
   int rc = check_options(p, batch, o);
   if (rc) return rc;
   if (!sol_blob) { snprintf(g_err, sizeof g_err, "null solution blob"); return ASCENT_E_ARG; }
-  if (substeps < 0 || substeps > ASCENT_FLIGHT_MAX_SUBSTEPS) { snprintf(g_err, sizeof g_err, "substeps out of range (0 = automatic, 1 .. %d)", ASCENT_FLIGHT_MAX_SUBSTEPS); return ASCENT_E_ARG; }
+  if ((rc = check_substeps(substeps))) return rc;
   if (o->terminal == 2) { snprintf(g_err, sizeof g_err, "terminal 2 is not supported by the flight Jacobian and the trim (its two conditions are nearly dependent where burnout sits at an apsis)"); return ASCENT_E_ARG; }
-  const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
-  if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
-  if (o->move_penalty && !ptr_is_device && (rc = check_dcost(p, batch))) return rc;
-  return 0;
+  return check_solvable(p, batch, o, ptr_is_device);
 }
 }  // namespace
 
 int ascent_flight_jacobian(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
                            double *jac_out, double *jac_u_out, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_flight_like(p, batch, o, sol_blob, substeps, device_id, ptr_is_device);
+  int rc = check_flight_like(p, batch, o, sol_blob, substeps, ptr_is_device);
   if (rc) return rc;
   if (!jac_out) { snprintf(g_err, sizeof g_err, "null jac_out"); return ASCENT_E_ARG; }
   if ((rc = check_device(device_id))) return rc;
@@ -839,33 +836,18 @@ int ascent_flight_jacobian(const ascent_params *p, int64_t batch, const ascent_o
   const int K = o->n_nodes - 1;
   double *ws = nullptr;
   if ((rc = trim_ws_claim(device_id, jac_ws_bytes(K, (long)batch), stream, &ws))) return rc;
-  if (ptr_is_device) {
-    rc = jac_run(p, (long)batch, K, o->formulation, substeps, sol_blob, jac_out, jac_u_out, ws, stream, g_err, sizeof g_err);
-    if (rc) return rc;
-    if ((rc = trim_ws_release(device_id, stream))) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(stream));
-    return ASCENT_OK;
-  }
-  const size_t nb = (21 * (size_t)K + NSC) * batch, nj = (size_t)9 * 24 * batch, nu = (size_t)9 * K * batch;
-  DevBuf<ascent_params> bp;
-  DevBuf<double> bb, bj, bu;
-  HIPCHK(bp.alloc(batch)); HIPCHK(bb.alloc(nb)); HIPCHK(bj.alloc(nj));
-  if (jac_u_out) HIPCHK(bu.alloc(nu));
-  HIPCHK(hipMemcpyAsync(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(bb.d, sol_blob, nb * sizeof(double), hipMemcpyHostToDevice, stream));
-  rc = jac_run(bp.d, (long)batch, K, o->formulation, substeps, bb.d, bj.d, bu.d, ws, stream, g_err, sizeof g_err);
-  if (rc) return rc;
-  if ((rc = trim_ws_release(device_id, stream))) return rc;
-  HIPCHK(hipMemcpyAsync(jac_out, bj.d, nj * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (jac_u_out) HIPCHK(hipMemcpyAsync(jac_u_out, bu.d, nu * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  return ASCENT_OK;
+  Staging st(stream, ptr_is_device);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
+  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch);
+  double *dj = st.out(jac_out, (size_t)9 * 24 * batch), *du = st.out(jac_u_out, (size_t)9 * K * batch);
+  if ((rc = st.failed()) || (rc = jac_run(c, substeps, db, dj, du, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
+  return st.finish();
 }
 
 int ascent_trim_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
                       int32_t rounds, double tol, double *trim_blob_out, double *summary_out, int device_id, void *stream_,
                       int ptr_is_device) {
-  int rc = check_flight_like(p, batch, o, sol_blob, substeps, device_id, ptr_is_device);
+  int rc = check_flight_like(p, batch, o, sol_blob, substeps, ptr_is_device);
   if (rc) return rc;
   if (!trim_blob_out || !summary_out) { snprintf(g_err, sizeof g_err, "null trim_blob_out or summary_out"); return ASCENT_E_ARG; }
   if (rounds < 0 || rounds > 32) { snprintf(g_err, sizeof g_err, "rounds out of range (1 .. 32, 0 = 6)"); return ASCENT_E_ARG; }
@@ -876,29 +858,15 @@ int ascent_trim_batch(const ascent_params *p, int64_t batch, const ascent_opts *
   HIPCHK(hipSetDevice(device_id));
   hipStream_t stream = (hipStream_t)stream_;
   const int K = o->n_nodes - 1;
+  const size_t nb = (21 * (size_t)K + NSC) * batch;
   double *ws = nullptr;
   if ((rc = trim_ws_claim(device_id, trim_ws_bytes(K, (long)batch), stream, &ws))) return rc;
-  if (ptr_is_device) {
-    rc = trim_run(p, (long)batch, K, o->formulation, o->terminal, substeps, rounds, tol, sol_blob, trim_blob_out, summary_out, ws, stream,
-                  g_err, sizeof g_err);
-    if (rc) return rc;
-    if ((rc = trim_ws_release(device_id, stream))) return rc;
-    if (!stream) HIPCHK(hipStreamSynchronize(stream));
-    return ASCENT_OK;
-  }
-  const size_t nb = (21 * (size_t)K + NSC) * batch, ns = (size_t)ASCENT_TRIM_ROWS * batch;
-  DevBuf<ascent_params> bp;
-  DevBuf<double> bb, bo, bs;
-  HIPCHK(bp.alloc(batch)); HIPCHK(bb.alloc(nb)); HIPCHK(bo.alloc(nb)); HIPCHK(bs.alloc(ns));
-  HIPCHK(hipMemcpyAsync(bp.d, p, batch * sizeof(ascent_params), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(bb.d, sol_blob, nb * sizeof(double), hipMemcpyHostToDevice, stream));
-  rc = trim_run(bp.d, (long)batch, K, o->formulation, o->terminal, substeps, rounds, tol, bb.d, bo.d, bs.d, ws, stream, g_err, sizeof g_err);
-  if (rc) return rc;
-  if ((rc = trim_ws_release(device_id, stream))) return rc;
-  HIPCHK(hipMemcpyAsync(trim_blob_out, bo.d, nb * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipMemcpyAsync(summary_out, bs.d, ns * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPCHK(hipStreamSynchronize(stream));
-  return ASCENT_OK;
+  Staging st(stream, ptr_is_device);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
+  const double *db = st.in(sol_blob, nb);
+  double *dout = st.out(trim_blob_out, nb), *ds = st.out(summary_out, (size_t)ASCENT_TRIM_ROWS * batch);
+  if ((rc = st.failed()) || (rc = trim_run(c, o->terminal, substeps, rounds, tol, db, dout, ds, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
+  return st.finish();
 }
 
 int ascent_kkt_step(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,
@@ -914,29 +882,28 @@ int ascent_kkt_solve(int64_t batch, int32_t n, int32_t bs, int32_t nb, const dou
     return ASCENT_E_ARG;
   }
   if (!diag || !lower || !upper || !rhs || !sol || (nb && (!border || !border_diag))) { snprintf(g_err, sizeof g_err, "null pointer"); return ASCENT_E_ARG; }
-  if (const int rc0 = check_device(device_id)) return rc0;
+  int rc = check_device(device_id);
+  if (rc) return rc;
   std::lock_guard<std::mutex> lock(g_mu[device_id]);
   HIPCHK(hipSetDevice(device_id));
-  { const int rc0 = claim_slot0(device_id); if (rc0) return rc0; }
-  int rc = ensure_ws(g_ws_slot0(device_id), blocktri_ws_bytes(n, (long)batch, algo));
-  if (rc) return rc;
+  if ((rc = claim_slot0(device_id))) return rc;
+  if ((rc = ensure_ws(g_ws_slot0(device_id), blocktri_ws_bytes(n, (long)batch, algo)))) return rc;
   DeviceWs &w = g_ws_slot0(device_id);
   const size_t nblk = (size_t)batch * n * bs * bs, nbor = (size_t)batch * n * bs * (nb ? nb : 1), nrow = (size_t)n * bs + nb;
   const size_t ny = (size_t)batch * n * bs * (1 + nb);
-  DevBuf<double> bd, bl, bu, bb, br, by;
-  HIPCHK(bd.alloc(nblk)); HIPCHK(bl.alloc(nblk)); HIPCHK(bu.alloc(nblk)); HIPCHK(bb.alloc(nbor)); HIPCHK(br.alloc(batch * nrow)); HIPCHK(by.alloc(ny));
-  HIPCHK(hipMemcpy(bd.d, diag, nblk * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(bl.d, lower, nblk * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(bu.d, upper, nblk * sizeof(double), hipMemcpyHostToDevice));
-  if (nb) HIPCHK(hipMemcpy(bb.d, border, (size_t)batch * n * bs * nb * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(br.d, rhs, batch * nrow * sizeof(double), hipMemcpyHostToDevice));
+  std::vector<double> Y(ny);
+  Staging st(nullptr, 0);
+  const double *dd = st.in(diag, nblk), *dl = st.in(lower, nblk), *du = st.in(upper, nblk);
+  const double *db = nb ? st.in(border, nbor) : st.scratch<double>(nbor);
+  const double *dr = st.in(rhs, batch * nrow);
+  double *dy = st.out(Y.data(), ny);
+  if ((rc = st.failed())) return rc;
   int singular = 0;
-  rc = blocktri_run((long)batch, n, bs, nb, bd.d, bl.d, bu.d, bb.d, br.d, w.ws, by.d, algo, &singular, 0, w.ev0, w.ev1, g_err, sizeof g_err);
+  rc = blocktri_run((long)batch, n, bs, nb, dd, dl, du, db, dr, w.ws, dy, algo, &singular, 0, w.ev0, w.ev1, g_err, sizeof g_err);
   if (rc) return rc;
   w.launched = true;
   if (singular) { snprintf(g_err, sizeof g_err, "ascent_kkt_solve: singular pivot inside a block (no pivoting)"); return ASCENT_E_ARG; }
-  std::vector<double> Y(ny);
-  HIPCHK(hipMemcpy(Y.data(), by.d, ny * sizeof(double), hipMemcpyDeviceToHost));
+  if ((rc = st.finish())) return rc;
   // close the border on the host: S = d - B'Y_B,  y = S^-1 (s - B'Y_r),  x = Y_r - Y_B y
   const int nc = 1 + nb;
   std::vector<double> S((size_t)nb * nb), t(nb), yv(nb);

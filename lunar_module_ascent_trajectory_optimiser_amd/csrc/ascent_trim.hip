@@ -416,8 +416,6 @@ TrimWs carve(double *ws, int K, long batch) {
 
 }  // namespace
 
-#define TCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { snprintf(err, errlen, "%s: %s", #call, hipGetErrorString(e_)); return ASCENT_E_HIP; } } while (0)
-
 size_t jac_ws_bytes(int K, long batch) {
   return ((size_t)ASCENT_TRAJ_FIELDS * (K + 1) + ASCENT_FLIGHT_ROWS) * (size_t)batch * sizeof(double);
 }
@@ -425,41 +423,43 @@ size_t trim_ws_bytes(int K, long batch) {
   return jac_ws_bytes(K, batch) + ((size_t)JROWS * JCOLS + (size_t)JROWS * K + ST_ROWS) * (size_t)batch * sizeof(double);
 }
 
-static int jac_launch(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob,
-                      const double *dtraj, const double *dskip, double *djac, double *djac_u, hipStream_t stream, char *err,
-                      size_t errlen) {
-  const dim3 grid((unsigned)batch), block(JB);
-  if (formulation == 1)
-    hipLaunchKernelGGL((j_jac<1>), grid, block, 0, stream, dp, batch, K, substeps, dblob, dtraj, dskip, djac, djac_u);
+static int jac_launch(const Call &c, int substeps, const double *dblob, const double *dtraj, const double *dskip, double *djac,
+                      double *djac_u) {
+  const dim3 grid((unsigned)c.batch), block(JB);
+  if (c.form == 1)
+    hipLaunchKernelGGL((j_jac<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, dtraj, dskip, djac, djac_u);
   else
-    hipLaunchKernelGGL((j_jac<0>), grid, block, 0, stream, dp, batch, K, substeps, dblob, dtraj, dskip, djac, djac_u);
-  TCHK(hipGetLastError());
+    hipLaunchKernelGGL((j_jac<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, dtraj, dskip, djac, djac_u);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 
-int jac_run(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *djac,
-            double *djac_u, double *ws, hipStream_t stream, char *err, size_t errlen) {
-  const TrimWs w = carve(ws, K, batch);
-  if (const int rc = flight_fly_only(dp, batch, K, formulation, substeps, dblob, w.traj, w.fsum, stream, err, errlen)) return rc;
-  return jac_launch(dp, batch, K, formulation, substeps, dblob, w.traj, nullptr, djac, djac_u, stream, err, errlen);
+int jac_run(const Call &c, int substeps, const double *dblob, double *djac, double *djac_u, double *ws) {
+  const TrimWs w = carve(ws, c.K, c.batch);
+  if (const int rc = flight_fly_only(c, substeps, dblob, w.traj, w.fsum)) return rc;
+  return jac_launch(c, substeps, dblob, w.traj, nullptr, djac, djac_u);
 }
 
-int trim_run(const ascent_params *dp, long batch, int K, int formulation, int terminal, int substeps, int rounds, double tol,
-             const double *dblob, double *dblob_out, double *dsummary, double *ws, hipStream_t stream, char *err, size_t errlen) {
+int trim_run(const Call &c, int terminal, int substeps, int rounds, double tol, const double *dblob, double *dblob_out,
+             double *dsummary, double *ws) {
+  const ascent_params *dp = c.dp;
+  const long batch = c.batch;
+  const int K = c.K;
+  hipStream_t stream = c.stream;
   const TrimWs w = carve(ws, K, batch);
   const size_t B = (size_t)batch;
-  TCHK(hipMemcpyAsync(dblob_out, dblob, (21 * (size_t)K + NSC) * B * sizeof(double), hipMemcpyDeviceToDevice, stream));
-  TCHK(hipMemsetAsync(w.st, 0, (size_t)ST_ROWS * B * sizeof(double), stream));
+  ASC_CHK(c.err, c.errlen, hipMemcpyAsync(dblob_out, dblob, (21 * (size_t)K + NSC) * B * sizeof(double), hipMemcpyDeviceToDevice, stream));
+  ASC_CHK(c.err, c.errlen, hipMemsetAsync(w.st, 0, (size_t)ST_ROWS * B * sizeof(double), stream));
   const dim3 grid((unsigned)batch), block(TW);
   for (int r = 0; r < rounds; r++) {
-    if (const int rc = flight_fly_only(dp, batch, K, formulation, substeps, dblob_out, w.traj, w.fsum, stream, err, errlen)) return rc;
-    if (const int rc = jac_launch(dp, batch, K, formulation, substeps, dblob_out, w.traj, w.st, w.jac, w.jac_u, stream, err, errlen)) return rc;
+    if (const int rc = flight_fly_only(c, substeps, dblob_out, w.traj, w.fsum)) return rc;
+    if (const int rc = jac_launch(c, substeps, dblob_out, w.traj, w.st, w.jac, w.jac_u)) return rc;
     hipLaunchKernelGGL(t_update, grid, block, 0, stream, dp, batch, K, terminal, tol, r == 0 ? 1 : 0, dblob_out, w.traj, w.jac, w.jac_u, w.st);
-    TCHK(hipGetLastError());
+    ASC_CHK(c.err, c.errlen, hipGetLastError());
   }
-  if (const int rc = flight_fly_only(dp, batch, K, formulation, substeps, dblob_out, w.traj, w.fsum, stream, err, errlen)) return rc;
+  if (const int rc = flight_fly_only(c, substeps, dblob_out, w.traj, w.fsum)) return rc;
   hipLaunchKernelGGL(t_final, grid, block, 0, stream, dp, batch, K, terminal, tol, dblob, dblob_out, w.traj, w.st, dsummary);
-  TCHK(hipGetLastError());
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }
 

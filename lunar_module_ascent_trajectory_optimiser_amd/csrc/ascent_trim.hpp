@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "ascent.h"
+#include "ascent_host.hpp"
 
 namespace ascent {
 
@@ -12,16 +13,15 @@ namespace ascent {
 size_t jac_ws_bytes(int K, long batch);
 size_t trim_ws_bytes(int K, long batch);
 
-// include/ascent.h: ascent_flight_jacobian.  Device pointers: dp[batch], dblob [21K+10][batch], djac [9][24][batch], djac_u
-// [9][K][batch] or null, ws of jac_ws_bytes.  Options already checked by the caller.  Only enqueues two kernels on `stream`
+// include/ascent.h: ascent_flight_jacobian.  Device pointers: c.dp[batch], dblob [21K+10][batch], djac [9][24][batch], djac_u
+// [9][K][batch] or null, ws of jac_ws_bytes.  Options already checked by the caller.  Only enqueues two kernels on c.stream
 // (f_fly, j_jac).  Returns ASCENT_OK / ASCENT_E_HIP.
-int jac_run(const ascent_params *dp, long batch, int K, int formulation, int substeps, const double *dblob, double *djac,
-            double *djac_u, double *ws, hipStream_t stream, char *err, size_t errlen);
+int jac_run(const Call &c, int substeps, const double *dblob, double *djac, double *djac_u, double *ws);
 
 // include/ascent.h: ascent_trim_batch.  Device pointers: dblob_out [21K+10][batch] (working copy and result), dsummary
-// [ASCENT_TRIM_ROWS][batch], ws of trim_ws_bytes.  rounds 1..32, tol > 0.  Only enqueues: one copy, one memset and
-// 3 rounds + 2 kernels.
-int trim_run(const ascent_params *dp, long batch, int K, int formulation, int terminal, int substeps, int rounds, double tol,
-             const double *dblob, double *dblob_out, double *dsummary, double *ws, hipStream_t stream, char *err, size_t errlen);
+// [ASCENT_TRIM_ROWS][batch], ws of trim_ws_bytes.  terminal: ascent_opts.terminal itself, 0 / 1.  rounds 1..32, tol > 0.  Only
+// enqueues: one copy, one memset and 3 rounds + 2 kernels.
+int trim_run(const Call &c, int terminal, int substeps, int rounds, double tol, const double *dblob, double *dblob_out,
+             double *dsummary, double *ws);
 
 }  // namespace ascent

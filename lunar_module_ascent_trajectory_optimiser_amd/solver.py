@@ -41,6 +41,18 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _blob_call(params, sol_blob, nt, scheme=0, formulation=0, terminal=0, move_penalty=False, what="sol_blob"):
+    """What every call at a blob begins with: (L, P, B, K, blob, o) -- the library, the packed parameters, batch and intervals,
+    the blob as a contiguous (21K+10, batch) float64 array (checked) and the options of a call that does not iterate."""
+    P = pack(params)
+    B = P.shape[0]
+    blob = np.ascontiguousarray(sol_blob, dtype=np.float64)
+    if blob.shape != (blob_rows(nt), B):
+        raise ValueError(f"sol_blob must have shape {(blob_rows(nt), B)}" if what == "sol_blob" else f"{what} has the wrong shape")
+    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
+    return _lib.load(), P, B, nt - 1, blob, o
+
+
 FLIGHT_ROWS = ("miss_position", "miss_velocity", "flown_periapsis_alt", "flown_apoapsis_alt", "nlp_periapsis_alt",
                "nlp_apoapsis_alt", "max_local_position_error", "max_local_velocity_error", "max_local_step", "substeps")
 
@@ -285,23 +297,25 @@ def solve_batch(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300, g
     return BatchResult(P, nt, traj, tf, status, iters, blob if want_blob else None, kms, sens, fl, tr)
 
 
-def _penalty_weight(P, formulation):
-    """weight of sum_k |u_k - u_{k-1}| in the scaled objective and u_{-1} (include/ascent.h: ascent_opts.move_penalty)"""
+def _penalised_objective(P, blob, K, formulation):
+    """tf + w sum_k |u_k - u_{k-1}| of every problem at its blob, (batch,): the weight w of the movement in the scaled objective
+    and u_{-1} depend on the formulation (include/ascent.h: ascent_opts.move_penalty).  P (batch, 16) and blob (21K+10, batch)
+    are numpy arrays or torch tensors alike.  The movements are laid out as (K, batch) rows and summed over the rows, u_0 - u_{-1}
+    first: the order of additions of a sum over the K + 1 controls with u_{-1} put in front."""
     form = FORMULATIONS.get(formulation, formulation)
-    return (P[:, 15] * P[:, 12] * 0.5, -1.0) if form == 1 else (P[:, 15], 0.0)
+    w, u0 = (P[:, 15] * P[:, 12] * 0.5, -1.0) if form == 1 else (P[:, 15], 0.0)
+    U = blob[7 * K:8 * K]
+    dU = abs(U - u0)
+    dU[1:] = abs(U[1:] - U[:-1])
+    return blob[21 * K] + w * dU.sum(0)
 
 
 def objective(params, sol_blob, nt: int, formulation=0, move_penalty: bool = False) -> np.ndarray:
     """J* of every problem at its solution blob (rows, batch): the scaled objective as solved -- tf, plus the move penalty
     dcost * sum_k |u_k - u_{k-1}| taken from the blob's controls when move_penalty is on."""
-    P = pack(params)
-    K = nt - 1
-    J = np.array(sol_blob[21 * K], dtype=np.float64)
     if move_penalty:
-        w, u0 = _penalty_weight(P, formulation)
-        U = np.vstack([np.full((1, P.shape[0]), u0), sol_blob[7 * K:8 * K]])
-        J = J + w * np.abs(np.diff(U, axis=0)).sum(axis=0)
-    return J
+        return _penalised_objective(pack(params), np.asarray(sol_blob, dtype=np.float64), nt - 1, formulation)
+    return np.array(sol_blob[21 * (nt - 1)], dtype=np.float64)
 
 
 def _seconds(P, blob, nt, g, formulation, move_penalty):
@@ -317,14 +331,8 @@ def param_sensitivity(params, sol_blob: np.ndarray, nt: int, scheme=0, formulati
     scaled objective J* to every ascent_params field (PARAM_FIELDS order, per SI unit), at the solution blob (21K+10, batch)
     that solve_batch returned with the same options.  One read of the blob on the device, no extra solve.  Rows of problems
     that did not converge are computed at whatever the blob holds and are meaningless."""
-    P = pack(params)
-    B = P.shape[0]
-    blob = np.ascontiguousarray(sol_blob, dtype=np.float64)
-    if blob.shape != (blob_rows(nt), B):
-        raise ValueError(f"sol_blob must have shape {(blob_rows(nt), B)}")
-    L = _lib.load()
+    L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     g = np.empty((16, B))
-    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
     _lib.check(L.ascent_param_sensitivity(_ptr(P), B, C.byref(o), _ptr(blob), _ptr(g), device, None, 0))
     return np.ascontiguousarray(g.T)
 
@@ -337,16 +345,10 @@ def fly_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, te
     trajectory.  Returns a FlightResult: the flown trajectory, the local discretisation error of every step (each step flown
     from the NLP's own z_{k-1}), and per problem the miss at the last node, the flown and the NLP's burnout orbit and the largest
     local error (FLIGHT_ROWS).  Rows of problems that did not converge are computed from whatever the blob holds."""
-    P = pack(params)
-    B, K = P.shape[0], nt - 1
-    blob = np.ascontiguousarray(sol_blob, dtype=np.float64)
-    if blob.shape != (blob_rows(nt), B):
-        raise ValueError(f"sol_blob must have shape {(blob_rows(nt), B)}")
-    L = _lib.load()
+    L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     traj = np.empty((10, nt, B)) if want_traj else None
     local = np.empty((K, 7, B)) if want_local else None
     summ = np.empty((len(FLIGHT_ROWS), B))
-    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
     _lib.check(L.ascent_fly_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(traj), _ptr(local), _ptr(summ),
                                   device, None, 0))
     return FlightResult(None if traj is None else np.ascontiguousarray(traj.transpose(2, 0, 1)),
@@ -360,15 +362,9 @@ def flight_jacobian(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation
     -- the flown last state (scaled) and the flown periapsis / apoapsis altitude (m) -- with respect to the initial state, the
     16 parameter fields (blob held fixed), t_f and every control u_k, at the blob (21K+10, batch).  The open-loop counterpart
     of param_sensitivity: what a dispersed vehicle does under the nominal control.  terminal 2 is refused."""
-    P = pack(params)
-    B, K = P.shape[0], nt - 1
-    blob = np.ascontiguousarray(sol_blob, dtype=np.float64)
-    if blob.shape != (blob_rows(nt), B):
-        raise ValueError(f"sol_blob must have shape {(blob_rows(nt), B)}")
-    L = _lib.load()
+    L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     jac = np.empty((9, 24, B))
     ju = np.empty((9, K, B)) if want_controls else None
-    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
     _lib.check(L.ascent_flight_jacobian(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(jac), _ptr(ju), device, None, 0))
     j = jac.transpose(2, 0, 1)
     return FlightJacobian(np.ascontiguousarray(j[:, :, :7]), np.ascontiguousarray(j[:, :, 7:23]), np.ascontiguousarray(j[:, :, 23]),
@@ -381,15 +377,9 @@ def trim_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, t
     flown terminal conditions to zero, saturated controls (|u_k| >= 0.999) kept where they are; `rounds` rounds (0: 6) to
     `tol` (0: 1e-10) entirely on the device.  Returns a TrimResult: the trimmed blob (states = the flown states of the trimmed
     control; multipliers stale) and the summary (TRIM_ROWS).  terminal 2 is refused."""
-    P = pack(params)
-    B = P.shape[0]
-    blob = np.ascontiguousarray(sol_blob, dtype=np.float64)
-    if blob.shape != (blob_rows(nt), B):
-        raise ValueError(f"sol_blob must have shape {(blob_rows(nt), B)}")
-    L = _lib.load()
+    L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     out = np.empty_like(blob)
     summ = np.empty((len(TRIM_ROWS), B))
-    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
     _lib.check(L.ascent_trim_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), int(rounds), float(tol), _ptr(out), _ptr(summ),
                                    device, None, 0))
     return TrimResult(out, np.ascontiguousarray(summ.T), nt)
@@ -399,14 +389,8 @@ def eval_nodes(params, iterate: np.ndarray, nt: int = 200, device: int = 0, path
     """Per-step defects (7K,batch), Jacobian blocks (8K,batch), Hessian blocks (10K,batch).
     path: "auto" (the kernels solve_batch would run for this batch), "fused", "split_lane", "split_wide"
     (enum ascent_path, include/ascent.h); the split paths take scheme 1 and formulation 1 as well."""
-    L = _lib.load()
-    P = pack(params)
-    B, K = P.shape[0], nt - 1
-    it = np.ascontiguousarray(iterate, dtype=np.float64)
-    if it.shape != (blob_rows(nt), B):
-        raise ValueError("iterate has the wrong shape")
+    L, P, B, K, it, o = _blob_call(params, iterate, nt, scheme, formulation, what="iterate")
     d, j, h = np.empty((7 * K, B)), np.empty((8 * K, B)), np.empty((10 * K, B))
-    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation)
     _lib.check(L.ascent_eval_nodes_path(_ptr(P), B, C.byref(o), _ptr(it), _ptr(d), _ptr(j), _ptr(h), device,
                                         _lib.PATHS[path]))
     return d, j, h
@@ -417,17 +401,11 @@ def kkt_step(params, iterate: np.ndarray, mu, delta_w, nt: int = 200, device: in
     """One Newton step of the barrier problem at `iterate` -> (step blob, inertia flags); `path` as in eval_nodes.
     move_penalty (paths "persist" and "dense"): with the l1 move penalty; the slack pairs, which the blob does not carry, are
     set around the iterate's own movement (p = max(du, 0) + 1e-4, n = max(-du, 0) + 1e-4, z_p = z_n = dcost, lambda_u = 0)."""
-    L = _lib.load()
-    P = pack(params)
-    B = P.shape[0]
-    it = np.ascontiguousarray(iterate, dtype=np.float64)
-    if it.shape != (blob_rows(nt), B):
-        raise ValueError("iterate has the wrong shape")
+    L, P, B, K, it, o = _blob_call(params, iterate, nt, scheme, formulation, terminal, move_penalty, what="iterate")
     mu = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float64), (B,)))
     dw = np.ascontiguousarray(np.broadcast_to(np.asarray(delta_w, dtype=np.float64), (B,)))
     step = np.empty_like(it)
     inertia = np.empty(B, dtype=np.int32)
-    o = _opts(nt, 0, 1.0, 0, 0.0, scheme, formulation, terminal=terminal, move_penalty=move_penalty)
     _lib.check(L.ascent_kkt_step_path(_ptr(P), B, C.byref(o), _ptr(it), _ptr(mu), _ptr(dw), _ptr(step), _ptr(inertia),
                                       device, _lib.PATHS[path]))
     return step, inertia
@@ -437,14 +415,8 @@ def dense_records(params, iterate: np.ndarray, nt: int = 200, scheme=2, device: 
     """The dense stage records of the dense-block path at `iterate`: (batch, K, 6, 8, 8) -- grids d c_k/d z_{k-1}, d c_k/d z_k,
     the three Hessian blocks of lambda_k'c_k and the vector grid (rows c_k, d c_k/du_k, d c_k/d tf, the two (z, tf) Hessian
     columns); see ascent_dense_records in include/ascent.h."""
-    L = _lib.load()
-    P = pack(params)
-    B, K = P.shape[0], nt - 1
-    it = np.ascontiguousarray(iterate, dtype=np.float64)
-    if it.shape != (blob_rows(nt), B):
-        raise ValueError("iterate has the wrong shape")
+    L, P, B, K, it, o = _blob_call(params, iterate, nt, scheme, what="iterate")
     rec = np.empty((B, K, 6, 8, 8))
-    o = _opts(nt, 0, 1.0, 0, 0.0, scheme)
     _lib.check(L.ascent_dense_records(_ptr(P), B, C.byref(o), _ptr(it), _ptr(rec), device))
     return rec
 
@@ -551,13 +523,7 @@ def solve_batch_torch(params_t, nt: int = 200, tol: float = 1e-9, max_iter: int 
         g = torch.empty((16, B), dtype=torch.float64, device=dev)
         _lib.check(L.ascent_param_sensitivity(params_t.data_ptr(), B, C.byref(o), blob.data_ptr(), g.data_ptr(),
                                               dev.index or 0, C.c_void_p(stream), 1))
-        K = nt - 1
-        J = blob[21 * K].clone()
-        if move_penalty:
-            form = FORMULATIONS.get(formulation, formulation)
-            w = params_t[:, 15] * params_t[:, 12] * 0.5 if form == 1 else params_t[:, 15]
-            U = torch.cat([torch.full((1, B), -1.0 if form == 1 else 0.0, dtype=torch.float64, device=dev), blob[7 * K:8 * K]])
-            J = J + w * (U[1:] - U[:-1]).abs().sum(0)
+        J = _penalised_objective(params_t, blob, nt - 1, formulation) if move_penalty else blob[21 * (nt - 1)]
         s_ = g.t() * params_t[:, 11:12]
         s_[:, 11] += J
         sens.copy_(torch.where((status == 0)[:, None], s_, torch.full_like(s_, float("nan"))))
@@ -592,15 +558,8 @@ class _FinalTime:
                     out = solve_batch_torch(params_t.detach().contiguous(), sensitivity=True, want_traj=False,
                                             want_blob=kw.get("move_penalty", False), **kw)
                     T = params_t[:, 11].detach()
-                    if kw.get("move_penalty", False):
-                        nt = kw.get("nt", 200)
-                        K = nt - 1
-                        form = FORMULATIONS.get(kw.get("formulation", 0), kw.get("formulation", 0))
-                        w = params_t[:, 15] * params_t[:, 12] * 0.5 if form == 1 else params_t[:, 15]
-                        B = params_t.shape[0]
-                        U = torch.cat([torch.full((1, B), -1.0 if form == 1 else 0.0, dtype=torch.float64,
-                                                  device=params_t.device), out["blob"][7 * K:8 * K]])
-                        y = T * (out["tf"] + w.detach() * (U[1:] - U[:-1]).abs().sum(0))
+                    if kw.get("move_penalty", False):       # (the blob's own tf row holds the bits of out["tf"])
+                        y = T * _penalised_objective(params_t.detach(), out["blob"], kw.get("nt", 200) - 1, kw.get("formulation", 0))
                     else:
                         y = T * out["tf"]
                     y = torch.where(out["status"] == 0, y, torch.full_like(y, float("nan")))

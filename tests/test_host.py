@@ -198,3 +198,61 @@ def test_one_hip_runtime_per_process(lib):
                          "\ntry:\n    _lib.require_single_hip_runtime(); print('no error')\nexcept _lib.AscentLibraryError as e:\n    print('refused' if 'two HIP runtimes' in str(e) else e)")
     out = subprocess.run([sys.executable, "-c", code2], capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0 and out.stdout.strip() == "refused", (out.stdout, out.stderr)
+
+
+# The five entry points that work on a solve's results: (name, call(lib, a, o, **changes)) where `a` holds the pointers of one
+# complete call (a changed entry replaces its pointer or integer) and `o` the options.
+def _post_solve_calls():
+    def sens(L, a, o): return L.ascent_param_sensitivity(a["p"], a["batch"], o, a["blob"], a["out"], 0, None, 0)
+    def fly(L, a, o): return L.ascent_fly_batch(a["p"], a["batch"], o, a["blob"], a["substeps"], a["opt"], a["opt"], a["out"], 0, None, 0)
+    def jac(L, a, o): return L.ascent_flight_jacobian(a["p"], a["batch"], o, a["blob"], a["substeps"], a["out"], a["opt"], 0, None, 0)
+    def trim(L, a, o): return L.ascent_trim_batch(a["p"], a["batch"], o, a["blob"], a["substeps"], a["rounds"], 0.0, a["out"], a["out2"], 0, None, 0)
+    def coast(L, a, o): return L.ascent_coast_batch(a["p"], a["batch"], a["blob"], a["coast_nodes"], a["out"], a["out2"], a["out3"], 0, None, 0)
+    return dict(ascent_param_sensitivity=sens, ascent_fly_batch=fly, ascent_flight_jacobian=jac, ascent_trim_batch=trim,
+                ascent_coast_batch=coast)
+
+
+@pytest.mark.parametrize("name", sorted(_post_solve_calls()))
+def test_post_solve_entry_points_refuse_bad_arguments_before_the_device(lib, name):
+    """Every argument error of the entry points that work on a solve's results is ASCENT_E_ARG with its own message, on a
+    machine with or without a GPU: refusals come before the device is looked at.  A refused call touches none of its arrays."""
+    call = _post_solve_calls()[name]
+    P = np.vstack([A.AscentParams().as_row()] * 2)
+    P0 = P.copy()
+    P0[1, 15] = 0.0
+    arrays = {k: np.full(8, 7.25) for k in ("blob", "out", "out2", "out3", "opt")}
+    good = dict({k: v.ctypes.data_as(C.c_void_p) for k, v in arrays.items()}, p=P.ctypes.data_as(C.c_void_p), batch=2, substeps=0,
+                rounds=0, coast_nodes=10)
+    coast, flight_like = name == "ascent_coast_batch", name in ("ascent_flight_jacobian", "ascent_trim_batch")
+
+    def opts(**kw):
+        return C.byref(_lib.AscentOptsC(**dict(dict(n_nodes=50, scheme=0, max_iter=0, warm_start=0, tol=1.0, mu_init=0.0), **kw)))
+
+    def refused(what, o=None, **changes):
+        rc = call(lib, dict(good, **changes), opts() if o is None else o)
+        msg = lib.ascent_strerror(rc)
+        assert rc == -1 and what in msg, (name, changes, rc, msg)
+
+    refused(b"null", p=None)
+    refused(b"batch <= 0", batch=0)
+    refused(b"null", blob=None)
+    refused(b"null", out=None)
+    if name == "ascent_trim_batch" or coast:
+        refused(b"null", out2=None)
+    if coast:
+        refused(b"null", out3=None)
+        refused(b"coast_nodes", coast_nodes=0)
+        refused(b"coast_nodes", coast_nodes=65536)
+    else:
+        refused(b"null", o=C.POINTER(_lib.AscentOptsC)())
+        refused(b"scheme", o=opts(scheme=7))
+        refused(b"dcost", o=opts(move_penalty=1), p=P0.ctypes.data_as(C.c_void_p))
+    if not coast and name != "ascent_param_sensitivity":
+        refused(b"substeps", substeps=-1)
+        refused(b"substeps", substeps=4097)
+    if name == "ascent_trim_batch":
+        refused(b"rounds", rounds=33)
+    if flight_like:
+        refused(b"terminal 2", o=opts(terminal=2))
+    for k, v in arrays.items():
+        assert (v == 7.25).all(), k
