@@ -4,10 +4,12 @@
 This is this repository's own counterpart of the reference script: the same problem, declared with
 the same modelling calls, solved by libascent on an MI355X instead of GEKKO/APMonitor/IPOPT.  It prints
 the quantities the reference prints (/root/reference/Launch_Optimiser.py:178-194) and writes the same
-three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim]
+three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim] [--disperse]
 --fly also integrates the ODEs under the control just found (RK4 on the device) and prints where that flight ends.
 --trim corrects (t_f, u) so that the flown control reaches the target orbit (trim_batch) and prints t_f and the flown apsides
 before and after.
+--disperse trims, then flies the trimmed control 1024 times with 50 N (1-sigma) of thrust error and 1e-3 of error on every control
+step (disperse_batch) and prints the Monte Carlo and the linear 1-sigma of the flown apsides side by side.
 """
 import argparse
 import os
@@ -122,6 +124,25 @@ def trim(m, scheme):
     return t
 
 
+def disperse(m, scheme, samples=1024):
+    """The trimmed solution under a dispersed thrust and control: Monte Carlo on the device beside the flight Jacobian's linear
+    prediction from the same draws."""
+    from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, flight_jacobian, trim_batch
+    res = m.result
+    kw = dict(scheme=scheme, formulation=m._formulation)
+    t = trim_batch(res.params, res.flight_blob(), res.nt, **kw)
+    thrust = np.zeros(16)
+    thrust[3] = 50.0
+    d = disperse_batch(res.params, t.blob, res.nt, param_sigma=thrust, control_sigma=1e-3, samples=samples, **kw)
+    lin = np.sqrt(np.diagonal(d.linear_covariance(flight_jacobian(res.params, t.blob, res.nt, **kw)), axis1=1, axis2=2))
+    print("dispersion: %d of %d samples valid; thrust 1-sigma 50 N, control 1-sigma 1e-3 per step" % (d.n_valid[0], samples))
+    print("flown altitude (m)      nominal   Monte Carlo 1-sigma   linear 1-sigma   mean shift          min          max")
+    for name, q in (("periapsis", 7), ("apoapsis", 8)):
+        print("%-18s %12.1f %21.1f %16.1f %12.1f %12.1f %12.1f"
+              % (name, d.nominal[0, q], d.std[0, q], lin[0, q], d.mean[0, q] - d.nominal[0, q], d.min[0, q], d.max[0, q]))
+    return d
+
+
 def plots(m, v, outdir):
     import matplotlib
     matplotlib.use("Agg")
@@ -157,6 +178,7 @@ if __name__ == "__main__":
     ap.add_argument("--scheme", type=int, default=0, help="0 backward Euler (the reference's NODES=2), 1 trapezoid, 2 Hermite-Simpson")
     ap.add_argument("--fly", action="store_true", help="fly the solution's control with RK4 on the device and print what it reaches")
     ap.add_argument("--trim", action="store_true", help="trim t_f and the control so that the flown trajectory reaches its orbit; prints before / after")
+    ap.add_argument("--disperse", action="store_true", help="trim, then fly the trimmed control under 50 N of thrust and 1e-3 of control error 1024 times; prints Monte Carlo and linear 1-sigma of the flown apsides")
     a = ap.parse_args()
     model, variables, v_ins = build()
     if a.no_dcost:
@@ -169,5 +191,7 @@ if __name__ == "__main__":
         fly(model, a.scheme)
     if a.trim:
         trim(model, a.scheme)
+    if a.disperse:
+        disperse(model, a.scheme)
     if not a.no_plots:
         plots(model, variables, a.outdir)

@@ -341,6 +341,51 @@ int ascent_trim_batch(const ascent_params *p, int64_t batch, const ascent_opts *
                       int32_t rounds, double tol, double *trim_blob_out, double *summary_out, int device_id,
                       void *hip_stream_or_null, int ptr_is_device);
 
+/* Monte Carlo dispersion: what a dispersed vehicle does under the nominal control, beyond the linear answer of
+ * ascent_flight_jacobian.  Every problem's blob is flown `samples` times with perturbed inputs and the nine end quantities of
+ * the flight Jacobian (rows q: the flown z_K in scaled units, the flown periapsis / apoapsis altitude in metres) are reduced on
+ * the device to their count, mean, covariance and extrema; the blob is shared by the samples, never tiled.
+ * Perturbations: sample s of problem b flies the blob's control exactly as ascent_fly_batch does, with
+ *   z_0[i] = sigma[i][b] * xi[i][s] (scaled units; i = 0..6),
+ *   field i of ascent_params (SI, declaration order) + sigma[7+i][b] * xi[7+i][s], the derived constants recomputed per sample,
+ *   the scaled t_f + sigma[23][b] * xi[23][s],
+ *   u_k + sigma_u[k-1][b] * xi[24+k-1][s], not clipped (a control execution error is physical).
+ *   The blob stays fixed in scaled units -- the convention of the flight Jacobian, so J (sigma o xi_s) is the first-order
+ *   prediction of sample s.  xi is the caller's table, normally unit normals, shared by every problem of the batch (common
+ *   random numbers: the problems of a sweep see the same draws).  A perturbation is applied only where its sigma is non-zero:
+ *   with sigma = 0 the quantity is the nominal one bit for bit, whatever xi holds.
+ * substeps: as ascent_fly_batch; the m picked at the nominal blob and the nominal T_scale is held for every sample, as the
+ *   Jacobian holds it: the work per sample is bounded by 4 * K * m right-hand sides whatever xi holds.
+ * A sample is valid if all nine rows are finite (an escaping sample has apoapsis +inf and is invalid); invalid samples are left
+ *   out of every statistic and are counted by their absence from row 0.
+ * xi [24 + K][samples], sample index fastest ([24][samples] suffices when sigma_u is null); sigma [24][batch];
+ *   sigma_u_or_null [K][batch].
+ * stats_out [ASCENT_DISPERSE_STAT_ROWS][batch]:
+ *   0        the number of valid samples n
+ *   1..9     the nominal flight's nine rows (rows 8 / 9 are summary rows 2 / 3 of ascent_fly_batch on the same blob, bit for bit)
+ *   10..18   mean                         19..63  upper triangle, row-major, of the unbiased sample covariance (NaN where n < 2)
+ *   64..72 / 73..81   minimum / maximum over the valid samples (NaN where n = 0)
+ *   Moments are accumulated on the differences from the nominal rows (centre 0 for a nominal row that is not finite), so that a
+ *   standard deviation of 1e-8 of the mean keeps its digits; with n = 1 the mean is that sample itself.  The order of the additions is fixed -- a butterfly inside a
+ *   wavefront, the four wavefronts of a workgroup (256 consecutive samples) in order, the workgroups in ascending order --: the
+ *   result depends on `samples`, not on the batch size, the problem's place in the batch, host or device pointers, or timing.
+ * samples_out_or_null [9][samples][batch], element (q, s, problem) at ((q*samples + s)*batch + problem): every sample's nine rows,
+ *   invalid ones as they came out.
+ * Options: refuses (ASCENT_E_ARG) exactly what ascent_fly_batch refuses (terminal = 2 is accepted: the terminal mode does not
+ * enter the flight), samples outside 1 .. ASCENT_DISPERSE_MAX_SAMPLES, and a null xi, sigma or stats_out.  Garbage blobs: bounded
+ * work as stated; a blob with a non-finite t_f gives n = 0 and NaN statistics.  Host or device pointers (ptr_is_device); with
+ * device pointers and a stream the call only enqueues (f_fly, f_disperse, f_disperse_stats; no host read, no synchronisation).
+ * The device workspace -- the nominal trajectory and ceil(samples / 256) partial records of 73 doubles per problem -- is the one
+ * of ascent_flight_jacobian / ascent_trim_batch. */
+#define ASCENT_DISPERSE_COLS 24     /* columns of ascent_flight_jacobian's jac_out: z_0 (7), the 16 ascent_params fields, scaled t_f */
+#define ASCENT_DISPERSE_ROWS 9      /* rows q of ascent_flight_jacobian: flown z_K (scaled), flown periapsis / apoapsis altitude (m) */
+#define ASCENT_DISPERSE_STAT_ROWS 82
+#define ASCENT_DISPERSE_MAX_SAMPLES 65536
+int ascent_disperse_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                          int32_t substeps, int32_t samples, const double *xi, const double *sigma,
+                          const double *sigma_u_or_null, double *stats_out, double *samples_out_or_null, int device_id,
+                          void *hip_stream_or_null, int ptr_is_device);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

@@ -1,0 +1,258 @@
+// Monte Carlo dispersion of flown solutions (include/ascent.h: ascent_disperse_batch): one solution blob shared by many
+// perturbed flights, reduced on the device to the moments and extrema of the nine end quantities of the flight Jacobian.
+//
+// The flight of a sample is f_fly's (ascent_flight.hip): K collocation steps of m classical RK4 substeps, the control held over
+// a step, with a perturbed initial state, perturbed ascent_params fields (derive per sample), a perturbed t_f and perturbed
+// controls.  m is the nominal flight's (flight_substeps at the blob's t_f and the nominal T_scale), held for every sample as
+// the Jacobian holds it.  The nominal flight itself is f_fly, unchanged, into the workspace trajectory: its last node and
+// its summary rows 2 / 3 are the nominal rows and the centre of the moments.
+//
+// f_disperse        one lane per (problem, sample); a workgroup of DB = 256 threads is 256 consecutive samples of one problem
+//          (workgroup g of the linear grid: problem g / nwg, chunk g % nwg, nwg = ceil(samples / 256); below 193 samples the
+//          workgroup is only the one to three wavefronts that hold samples).  The lanes of a
+//          wavefront share the problem, so the blob's u_k, sigma and the parameters are wave-uniform loads, and xi[24 + k][s]
+//          is one contiguous 512-byte run per wave and step, loaded for the next step before the current one is integrated.
+//          Latency-bound like f_fly: 4 m K dependent right-hand sides per lane.  The 73 values of a record (count, 9 sums and 45
+//          products of the differences from the centre, 9 minima, 9 maxima) are reduced one at a time -- butterfly over the
+//          wave, wave 0..3 through LDS in that order -- into one partial record per workgroup.
+// f_disperse_stats  one lane per problem, problem-fastest: the partial records added in ascending chunk order, then the 82 rows.
+// The order of every addition is fixed by `samples` alone: a problem gives the same bits alone as inside any batch.
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cmath>
+
+#include "ascent.h"
+#include "ascent_device.hpp"
+#include "ascent_disperse.hpp"
+#include "ascent_flight.hpp"
+#include "ascent_flight_dev.hpp"
+
+namespace ascent {
+namespace {
+
+constexpr int DB = 256;                    // f_disperse: threads per workgroup = samples per partial record
+constexpr int DNW = DB / 64;
+constexpr int SW = 64;                     // f_disperse_stats: threads per workgroup
+constexpr int NQ = ASCENT_DISPERSE_ROWS, NC = ASCENT_DISPERSE_COLS;
+// a partial record: rows of [nwg][NREC][batch]
+constexpr int R_N = 0, R_SUM = 1, R_PROD = R_SUM + NQ, R_MIN = R_PROD + NQ * (NQ + 1) / 2, R_MAX = R_MIN + NQ, NREC = R_MAX + NQ;
+// stats_out rows
+constexpr int O_N = 0, O_NOM = 1, O_MEAN = O_NOM + NQ, O_COV = O_MEAN + NQ, O_MIN = O_COV + NQ * (NQ + 1) / 2, O_MAX = O_MIN + NQ;
+static_assert(O_MAX + NQ == ASCENT_DISPERSE_STAT_ROWS, "stats_out layout");
+constexpr long MAX_GRID = 1L << 22;        // workgroups per launch: 2^30 threads
+
+ASC_DEV bool finite1(double a) { return fabs(a) <= 1.79769313486231570815e308; }
+
+// butterflies: every lane ends with the same bits (no lane contributes a NaN: invalid samples enter as +-inf)
+ASC_DEV double wave_min(double v) {
+  ASC_UNROLL
+  for (int off = 32; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off));
+  return v;
+}
+ASC_DEV double wave_max(double v) {
+  ASC_UNROLL
+  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  return v;
+}
+
+// the nominal flight's nine rows from f_fly's trajectory and summary
+ASC_DEV void nominal_rows(const double *__restrict__ traj, const double *__restrict__ fsum, size_t B, long p, int K, double *r) {
+  load_node(traj + p, B, K + 1, K, r);
+  r[7] = fsum[(size_t)2 * B + p];
+  r[8] = fsum[(size_t)3 * B + p];
+}
+
+// the record of one wavefront into red[]: rows r of a sample, its validity, the centre
+ASC_DEV void wave_record(const double *r, bool valid, const double *cen, int lane, double *red) {
+#pragma clang fp contract(off)      // a product fused into the first addition of its butterfly would differ between the lanes
+  double dq[NQ];
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) dq[q] = valid ? r[q] - cen[q] : 0.0;
+  double v = wave_sum(valid ? 1.0 : 0.0);
+  if (lane == 0) red[R_N] = v;
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) {
+    v = wave_sum(dq[q]);
+    if (lane == 0) red[R_SUM + q] = v;
+  }
+  int idx = R_PROD;
+  ASC_UNROLL
+  for (int i = 0; i < NQ; i++) {
+    ASC_UNROLL
+    for (int j = i; j < NQ; j++, idx++) {
+      const double pr = dq[i] * dq[j];
+      v = wave_sum(pr);
+      if (lane == 0) red[idx] = v;
+    }
+  }
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) {
+    v = wave_min(valid ? r[q] : INFINITY);
+    if (lane == 0) red[R_MIN + q] = v;
+    v = wave_max(valid ? r[q] : -INFINITY);
+    if (lane == 0) red[R_MAX + q] = v;
+  }
+}
+
+template <int FORM>
+__global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
+                                                 int nwg, long g0, const double *__restrict__ blob,
+                                                 const double *__restrict__ traj, const double *__restrict__ fsum,
+                                                 const double *__restrict__ xi, const double *__restrict__ sigma,
+                                                 const double *__restrict__ sigma_u, double *__restrict__ partial,
+                                                 double *__restrict__ samples_out) {
+  __shared__ double red[DNW][NREC];
+  const long g = g0 + blockIdx.x;
+  const long p = g / nwg;
+  const int c = (int)(g - p * nwg);
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int s = c * DB + t;
+  const size_t B = (size_t)batch, NS = (size_t)samples;
+  const double *b = blob + p;
+  const double *pf = reinterpret_cast<const double *>(P + p);      // the 16 fields in declaration order
+  const double tf0 = b[(size_t)(21 * K + S_TH) * B];
+  const int m = flight_substeps((tf0 * pf[11]) / K, substeps);      // the nominal flight's, held
+  double cen[NQ];
+  nominal_rows(traj, fsum, B, p, K, cen);
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) cen[q] = finite1(cen[q]) ? cen[q] : 0.0;
+
+  double r[NQ];
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) r[q] = NAN;
+  if (s < samples) {
+    const double *x = xi + s;
+    // the 24 sigmas (wave-uniform) and draws of this sample, loaded together; a draw counts only where its sigma is not zero
+    double sg[NC], xv[NC];
+    ASC_UNROLL
+    for (int i = 0; i < NC; i++) sg[i] = sigma[(size_t)i * B + p];
+    ASC_UNROLL
+    for (int i = 0; i < NC; i++) xv[i] = x[(size_t)i * NS];
+    double z[7], f[16];
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) z[i] = sg[i] != 0.0 ? sg[i] * xv[i] : 0.0;
+    ASC_UNROLL
+    for (int i = 0; i < 16; i++) f[i] = sg[7 + i] != 0.0 ? pf[i] + sg[7 + i] * xv[7 + i] : pf[i];
+    const double tf = sg[23] != 0.0 ? tf0 + sg[23] * xv[23] : tf0;
+    const ascent_params prm = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11], f[12], f[13], f[14], f[15]};
+    const Der d = derive(prm);
+    const double dt = (tf * d.T) / K;
+    const double hs = dt / m;
+    const double *ub = b + (size_t)(7 * K) * B, *su = sigma_u ? sigma_u + p : nullptr, *xu = x + (size_t)NC * NS;
+    double u = ub[0];
+    if (su) {
+      const double s0 = su[0];
+      if (s0 != 0.0) u += s0 * xu[0];
+    }
+    for (int k = 0; k < K; k++) {
+      const int kn = k + 1 < K ? k + 1 : k;
+      const double un = ub[(size_t)kn * B], sgn = su ? su[(size_t)kn * B] : 0.0, xn = su ? xu[(size_t)kn * NS] : 0.0;
+      fly_step<FORM>(d, z, u, hs, m);
+      u = sgn != 0.0 ? un + sgn * xn : un;
+    }
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) r[i] = z[i];
+    apsides_of(prm, z[IX], z[IY], z[IVX], z[IVY], r[7], r[8]);
+    if (samples_out) {
+      ASC_UNROLL
+      for (int q = 0; q < NQ; q++) samples_out[((size_t)q * NS + s) * B + p] = r[q];
+    }
+  }
+  bool valid = true;
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) valid = valid && finite1(r[q]);
+  wave_record(r, valid, cen, lane, red[wv]);
+  __syncthreads();
+  const int nw = (int)blockDim.x >> 6;       // 4, or fewer where samples <= 192: the waves that exist, in wave order
+  for (int i = t; i < NREC; i += (int)blockDim.x) {
+    double a = red[0][i];
+    for (int w = 1; w < nw; w++) {
+      const double o = red[w][i];
+      a = i < R_MIN ? a + o : i < R_MAX ? fmin(a, o) : fmax(a, o);
+    }
+    partial[((size_t)c * NREC + i) * B + p] = a;
+  }
+}
+
+__global__ __launch_bounds__(SW) void f_disperse_stats(long batch, int K, int nwg, const double *__restrict__ traj,
+                                                       const double *__restrict__ fsum, const double *__restrict__ partial,
+                                                       double *__restrict__ stats) {
+  const long p = (long)blockIdx.x * SW + threadIdx.x;
+  if (p >= batch) return;
+  const size_t B = (size_t)batch;
+  const double *pr = partial + p;
+  double *out = stats + p;
+  double nom[NQ], S[NQ];
+  nominal_rows(traj, fsum, B, p, K, nom);
+  double n = 0.0;
+  for (int c = 0; c < nwg; c++) n += pr[((size_t)c * NREC + R_N) * B];
+  out[(size_t)O_N * B] = n;
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) {
+    double a = 0.0, lo = INFINITY, hi = -INFINITY;
+    for (int c = 0; c < nwg; c++) {
+      a += pr[((size_t)c * NREC + R_SUM + q) * B];
+      lo = fmin(lo, pr[((size_t)c * NREC + R_MIN + q) * B]);
+      hi = fmax(hi, pr[((size_t)c * NREC + R_MAX + q) * B]);
+    }
+    S[q] = a;
+    out[(size_t)(O_NOM + q) * B] = nom[q];
+    // n = 0: NaN; n = 1: the sample itself (centre + (sample - centre) may round)
+    out[(size_t)(O_MEAN + q) * B] = n == 1.0 ? lo : (finite1(nom[q]) ? nom[q] : 0.0) + a / n;
+    out[(size_t)(O_MIN + q) * B] = n > 0.0 ? lo : NAN;
+    out[(size_t)(O_MAX + q) * B] = n > 0.0 ? hi : NAN;
+  }
+  int idx = 0;
+  ASC_UNROLL
+  for (int i = 0; i < NQ; i++) {
+    ASC_UNROLL
+    for (int j = i; j < NQ; j++, idx++) {
+      double a = 0.0;
+      for (int c = 0; c < nwg; c++) a += pr[((size_t)c * NREC + R_PROD + idx) * B];
+      out[(size_t)(O_COV + idx) * B] = n >= 2.0 ? (a - S[i] * S[j] / n) / (n - 1.0) : NAN;
+    }
+  }
+}
+
+struct DisperseWs { double *traj, *fsum, *partial; };
+DisperseWs carve(double *ws, int K, long batch) {
+  DisperseWs w;
+  const size_t B = (size_t)batch;
+  w.traj = ws;
+  w.fsum = w.traj + (size_t)ASCENT_TRAJ_FIELDS * (K + 1) * B;
+  w.partial = w.fsum + (size_t)ASCENT_FLIGHT_ROWS * B;
+  return w;
+}
+int groups_per_problem(int samples) { return (samples + DB - 1) / DB; }
+// below 193 samples a workgroup holds only the wavefronts that fly: whole wavefronts, so the butterflies see 64 lanes
+int threads_per_group(int samples) { return samples >= DB ? DB : (samples + 63) / 64 * 64; }
+
+}  // namespace
+
+size_t disperse_ws_bytes(int K, long batch, int samples) {
+  return ((size_t)ASCENT_TRAJ_FIELDS * (K + 1) + ASCENT_FLIGHT_ROWS + (size_t)groups_per_problem(samples) * NREC) * (size_t)batch * sizeof(double);
+}
+
+int disperse_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
+                 const double *dsigma_u, double *dstats, double *dsamples, double *ws) {
+  const DisperseWs w = carve(ws, c.K, c.batch);
+  if (const int rc = flight_fly_only(c, substeps, dblob, w.traj, w.fsum)) return rc;
+  const int nwg = groups_per_problem(samples);
+  const long total = c.batch * nwg;
+  for (long g0 = 0; g0 < total; g0 += MAX_GRID) {
+    const dim3 grid((unsigned)(total - g0 < MAX_GRID ? total - g0 : MAX_GRID)), block(threads_per_group(samples));
+    if (c.form == 1)
+      hipLaunchKernelGGL((f_disperse<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
+                         w.fsum, dxi, dsigma, dsigma_u, w.partial, dsamples);
+    else
+      hipLaunchKernelGGL((f_disperse<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
+                         w.fsum, dxi, dsigma, dsigma_u, w.partial, dsamples);
+    ASC_CHK(c.err, c.errlen, hipGetLastError());
+  }
+  const dim3 gst((unsigned)((c.batch + SW - 1) / SW)), bst(SW);
+  hipLaunchKernelGGL(f_disperse_stats, gst, bst, 0, c.stream, c.batch, c.K, nwg, w.traj, w.fsum, w.partial, dstats);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
+  return ASCENT_OK;
+}
+
+}  // namespace ascent

@@ -1,0 +1,21 @@
+// Host interface of the Monte Carlo dispersion (ascent_disperse.hip), used by the C ABI in ascent_solver.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include "ascent.h"
+#include "ascent_host.hpp"
+
+namespace ascent {
+
+// Device workspace (bytes) of disperse_run: the nominal trajectory and f_fly's summary rows, and ceil(samples / 256) partial
+// records of 73 doubles per problem.  Nothing of size samples * K exists.
+size_t disperse_ws_bytes(int K, long batch, int samples);
+
+// include/ascent.h: ascent_disperse_batch.  Device pointers: c.dp[batch], dblob [21K+10][batch], dxi [24 + K][samples] ([24][samples]
+// with dsigma_u null), dsigma [24][batch], dsigma_u [K][batch] or null, dstats [ASCENT_DISPERSE_STAT_ROWS][batch], dsamples
+// [9][samples][batch] or null, ws of disperse_ws_bytes.  Options already checked by the caller.  Only enqueues on c.stream: f_fly,
+// f_disperse (one launch per 2^22 workgroups) and f_disperse_stats.  Returns ASCENT_OK / ASCENT_E_HIP.
+int disperse_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
+                 const double *dsigma_u, double *dstats, double *dsamples, double *ws);
+
+}  // namespace ascent

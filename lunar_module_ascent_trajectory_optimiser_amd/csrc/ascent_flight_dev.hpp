@@ -1,5 +1,6 @@
 // Device helpers of the flight verification (ascent_flight.hip) shared with the flight Jacobian and the trim
-// (ascent_trim.hip): the substep rule, the right-hand side, one RK4 collocation step and the two-body apsides.
+// (ascent_trim.hip) and the dispersion (ascent_disperse.hip): the substep rule, the right-hand side, one RK4 collocation step,
+// the two-body apsides, a node of a flown trajectory and the wavefront sum.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -58,6 +59,24 @@ ASC_DEV void apsides_of(const ascent_params &prm, double x, double y, double vx,
   const double h = X * VY - Y * VX;
   peri = h * h / (GM * (1.0 + e)) - prm.R0;
   apo = 0.5 * v2 - GM / r >= 0.0 ? INFINITY : (1.0 + e) / (2.0 / r - v2 / GM) - prm.R0;
+}
+
+// the 7-state of node k in a trajectory of ascent_fly_batch's layout (fields x y xdot ydot ax ay angle angledot u mass)
+ASC_DEV void load_node(const double *__restrict__ tr, size_t B, int nt, int k, double *z) {
+  z[IX] = tr[((size_t)0 * nt + k) * B];
+  z[IY] = tr[((size_t)1 * nt + k) * B];
+  z[IVX] = tr[((size_t)2 * nt + k) * B];
+  z[IVY] = tr[((size_t)3 * nt + k) * B];
+  z[IA] = tr[((size_t)6 * nt + k) * B];
+  z[IW] = tr[((size_t)7 * nt + k) * B];
+  z[IM] = tr[((size_t)9 * nt + k) * B];
+}
+
+// sum over the 64 lanes of a wavefront
+ASC_DEV double wave_sum(double v) {          // butterfly: every lane ends with the same bits
+  ASC_UNROLL
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
 }
 
 }  // namespace ascent

@@ -35,6 +35,7 @@
 #include "ascent_sens.hpp"
 #include "ascent_flight.hpp"
 #include "ascent_trim.hpp"
+#include "ascent_disperse.hpp"
 
 using namespace ascent;
 
@@ -866,6 +867,32 @@ int ascent_trim_batch(const ascent_params *p, int64_t batch, const ascent_opts *
   const double *db = st.in(sol_blob, nb);
   double *dout = st.out(trim_blob_out, nb), *ds = st.out(summary_out, (size_t)ASCENT_TRIM_ROWS * batch);
   if ((rc = st.failed()) || (rc = trim_run(c, o->terminal, substeps, rounds, tol, db, dout, ds, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
+  return st.finish();
+}
+
+// Monte Carlo dispersion (ascent_disperse.hip); its workspace is the buffer of the flight Jacobian and the trim
+int ascent_disperse_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                          int32_t samples, const double *xi, const double *sigma, const double *sigma_u, double *stats_out,
+                          double *samples_out, int device_id, void *stream_, int ptr_is_device) {
+  int rc = check_options(p, batch, o);
+  if (rc) return rc;
+  if (!sol_blob || !xi || !sigma || !stats_out) { snprintf(g_err, sizeof g_err, "null solution blob, xi, sigma or stats_out"); return ASCENT_E_ARG; }
+  if (samples < 1 || samples > ASCENT_DISPERSE_MAX_SAMPLES) { snprintf(g_err, sizeof g_err, "samples out of range (1 .. %d)", ASCENT_DISPERSE_MAX_SAMPLES); return ASCENT_E_ARG; }
+  if ((rc = check_substeps(substeps)) || (rc = check_solvable(p, batch, o, ptr_is_device)) || (rc = check_device(device_id))) return rc;
+  std::lock_guard<std::mutex> lock(g_mu[device_id]);
+  HIPCHK(hipSetDevice(device_id));
+  hipStream_t stream = (hipStream_t)stream_;
+  const int K = o->n_nodes - 1;
+  double *ws = nullptr;
+  if ((rc = trim_ws_claim(device_id, disperse_ws_bytes(K, (long)batch, samples), stream, &ws))) return rc;
+  Staging st(stream, ptr_is_device);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
+  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch);
+  const double *dx = st.in(xi, (size_t)(ASCENT_DISPERSE_COLS + (sigma_u ? K : 0)) * samples);
+  const double *dsg = st.in(sigma, (size_t)ASCENT_DISPERSE_COLS * batch), *dsu = st.in(sigma_u, (size_t)K * batch);
+  double *dst = st.out(stats_out, (size_t)ASCENT_DISPERSE_STAT_ROWS * batch);
+  double *dsm = st.out(samples_out, (size_t)ASCENT_DISPERSE_ROWS * samples * batch);
+  if ((rc = st.failed()) || (rc = disperse_run(c, substeps, samples, db, dx, dsg, dsu, dst, dsm, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
   return st.finish();
 }
 

@@ -48,17 +48,6 @@ constexpr int TW = 64;                     // t_update / t_final: one wavefront 
 // per-problem state of the trim between its kernels, rows of [ST_ROWS][batch]
 constexpr int ST_FLAG = 0 /* 0 active, 1 converged, 2 non-finite or singular */, ST_ROUNDS = 1, ST_C0 = 2, ST_NFREE = 3, ST_ROWS = 4;
 
-// the 7-state of node k in a trajectory of ascent_fly_batch's layout (fields x y xdot ydot ax ay angle angledot u mass)
-ASC_DEV void load_node(const double *__restrict__ tr, size_t B, int nt, int k, double *z) {
-  z[IX] = tr[((size_t)0 * nt + k) * B];
-  z[IY] = tr[((size_t)1 * nt + k) * B];
-  z[IVX] = tr[((size_t)2 * nt + k) * B];
-  z[IVY] = tr[((size_t)3 * nt + k) * B];
-  z[IA] = tr[((size_t)6 * nt + k) * B];
-  z[IW] = tr[((size_t)7 * nt + k) * B];
-  z[IM] = tr[((size_t)9 * nt + k) * B];
-}
-
 // f(z, u) and its tangent dF = f_z dz + (the column's own forcing): (fx, fy) picked from d accel / d Der for the columns
 // C_DER .. C_DER + 4, cw on the angledot row (alpha for the control column, u for the alpha column), cm on the mass row (mrate)
 template <int FORM>
@@ -262,11 +251,6 @@ __global__ __launch_bounds__(JB) void j_jac(const ascent_params *__restrict__ P,
   }
 }
 
-ASC_DEV double wave_sum(double v) {          // butterfly: every lane ends with the same bits
-  ASC_UNROLL
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 ASC_DEV double max_nan2(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
 ASC_DEV double wave_max_nan(double v) {
   ASC_UNROLL

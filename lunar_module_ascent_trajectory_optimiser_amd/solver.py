@@ -115,6 +115,65 @@ class FlightJacobian:
         return np.sqrt(var)
 
 
+def _sigma_rows(v, n, B, what):
+    """(B, n) from None (zeros), a scalar, (n,) or (B, n)"""
+    if v is None:
+        return np.zeros((B, n))
+    a = np.asarray(v, dtype=np.float64)
+    try:
+        return np.ascontiguousarray(np.broadcast_to(a, (B, n)))
+    except ValueError:
+        raise ValueError(f"{what} must broadcast to {(B, n)}") from None
+
+
+def _cov_from_upper(rows):
+    """(batch, 9, 9) symmetric from the 45 rows of the upper triangle, row-major: (batch, 45)"""
+    B = rows.shape[0]
+    cov = np.empty((B, 9, 9))
+    iu = np.triu_indices(9)
+    cov[:, iu[0], iu[1]] = rows
+    cov[:, iu[1], iu[0]] = rows
+    return cov
+
+
+@dataclasses.dataclass
+class DispersionResult:
+    """Monte Carlo dispersion of flown solutions (disperse_batch; include/ascent.h: ascent_disperse_batch): the statistics of the
+    nine end quantities of the flight (columns JACOBIAN_ROWS: the flown z_K in scaled units, the flown periapsis / apoapsis
+    altitude in metres) over the valid samples.  Problem index first."""
+    n_valid: np.ndarray             # (batch,) samples with nine finite rows; the others are left out of every statistic
+    nominal: np.ndarray             # (batch, 9) the unperturbed flight
+    mean: np.ndarray                # (batch, 9)
+    cov: np.ndarray                 # (batch, 9, 9) unbiased sample covariance, symmetric; NaN where n_valid < 2
+    min: np.ndarray                 # (batch, 9) NaN where n_valid = 0
+    max: np.ndarray                 # (batch, 9)
+    samples: np.ndarray | None      # (batch, samples, 9) every sample's rows, invalid ones as they came out (keep_samples=True)
+    xi: np.ndarray                  # (24 + K, samples) the draws, shared by every problem
+    z0_sigma: np.ndarray            # (batch, 7) scaled units
+    param_sigma: np.ndarray         # (batch, 16) SI units
+    tf_sigma: np.ndarray            # (batch,) scaled units
+    control_sigma: np.ndarray       # (batch, K)
+
+    @property
+    def std(self) -> np.ndarray:
+        """(batch, 9)"""
+        return np.sqrt(np.diagonal(self.cov, axis1=1, axis2=2))
+
+    def linear_covariance(self, J: FlightJacobian) -> np.ndarray:
+        """(batch, 9, 9) J D C_xi D J': the first-order prediction of `cov` from a FlightJacobian of the same blob, D the sigmas of
+        this result and C_xi the unbiased sample covariance of the rows of this very `xi` -- no sampling noise between the two."""
+        A = [J.dz0 * self.z0_sigma[:, None, :], J.dparams * self.param_sigma[:, None, :], (J.dtf * self.tf_sigma[:, None])[:, :, None]]
+        n = 24
+        if self.control_sigma.any():
+            if J.dcontrols is None:
+                raise ValueError("this FlightJacobian was computed without the control columns")
+            A.append(J.dcontrols * self.control_sigma[:, None, :])
+            n += self.control_sigma.shape[1]
+        A = np.concatenate(A, axis=2)
+        C = np.atleast_2d(np.cov(self.xi[:n]))
+        return np.einsum("bqc,cd,brd->bqr", A, C, A)
+
+
 @dataclasses.dataclass
 class TrimResult:
     """A batch of trimmed solutions (trim_batch; include/ascent.h: ascent_trim_batch)."""
@@ -199,6 +258,12 @@ class BatchResult:
         if self.flight is None or self.flight.traj is None:
             raise ValueError("coast(flown=True) needs the flown trajectory: solve_batch(..., flight=True)")
         return coast_batch(self.params, np.ascontiguousarray(self.flight.traj[:, :4, -1].T), coast_nodes, device)
+
+    def disperse(self, **kw) -> "DispersionResult":
+        """Monte Carlo dispersion of these solutions' flights: disperse_batch(self.params, the blob, self.nt, **kw).  A result
+        does not keep the options it was solved with: repeat scheme, formulation, terminal and move_penalty in kw as for
+        disperse_batch -- a formulation-1 solution dispersed without formulation=1 is flown as formulation 0."""
+        return disperse_batch(self.params, self.blob if self.blob is not None else self.flight_blob(), self.nt, **kw)
 
     def flight_blob(self) -> np.ndarray:
         """The part of a solution blob that fly_batch reads -- states, control and tf -- rebuilt from the trajectory (the rest
@@ -383,6 +448,39 @@ def trim_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, t
     _lib.check(L.ascent_trim_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), int(rounds), float(tol), _ptr(out), _ptr(summ),
                                    device, None, 0))
     return TrimResult(out, np.ascontiguousarray(summ.T), nt)
+
+
+def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, control_sigma=None, tf_sigma=None, z0_sigma=None,
+                   samples: int = 256, seed: int = 0, xi=None, keep_samples: bool = False, scheme=0, formulation=0, terminal=0,
+                   move_penalty: bool = False, substeps: int = 0, device: int = 0) -> DispersionResult:
+    """Monte Carlo dispersion (include/ascent.h: ascent_disperse_batch): every blob's control flown `samples` times on the
+    device as fly_batch flies it, with the initial state, the 16 parameter fields, t_f and every control perturbed by
+    sigma * xi, and the nine end quantities reduced on the device to count, mean, covariance and extrema.  The blob is shared
+    by the samples, not tiled.  param_sigma (16,) or (batch, 16) in SI units and control_sigma a scalar, (K,) or (batch, K)
+    broadcast like FlightJacobian.sigma's; tf_sigma a scalar or (batch,) in scaled units; z0_sigma (7,) or (batch, 7) in scaled
+    units; None: not perturbed.  xi (24 + K, samples): the draws, shared by every problem of the batch (common random numbers);
+    None draws np.random.default_rng(seed).standard_normal((24 + K, samples)).  The substeps picked at the nominal blob are held
+    for every sample.  keep_samples: also return every sample's rows.  terminal 2 is accepted."""
+    L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
+    if xi is None:
+        xi = np.random.default_rng(seed).standard_normal((24 + K, int(samples)))
+    xi = np.ascontiguousarray(xi, dtype=np.float64)
+    if xi.ndim != 2 or xi.shape[0] != 24 + K:
+        raise ValueError(f"xi must have shape (24 + K, samples) = ({24 + K}, samples)")
+    S = xi.shape[1]
+    zs, ps = _sigma_rows(z0_sigma, 7, B, "z0_sigma"), _sigma_rows(param_sigma, 16, B, "param_sigma")
+    ts = _sigma_rows(None if tf_sigma is None else np.asarray(tf_sigma, dtype=np.float64)[..., None], 1, B, "tf_sigma")
+    us = _sigma_rows(control_sigma, K, B, "control_sigma")
+    sig = np.ascontiguousarray(np.concatenate([zs, ps, ts], axis=1).T)
+    sig_u = np.ascontiguousarray(us.T) if control_sigma is not None else None
+    stats = np.empty((82, B))
+    smp = np.empty((9, S, B)) if keep_samples else None
+    _lib.check(L.ascent_disperse_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
+                                       _ptr(stats), _ptr(smp), device, None, 0))
+    st = stats.T
+    return DispersionResult(st[:, 0].astype(np.int64), np.ascontiguousarray(st[:, 1:10]), np.ascontiguousarray(st[:, 10:19]),
+                            _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
+                            None if smp is None else np.ascontiguousarray(smp.transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us)
 
 
 def eval_nodes(params, iterate: np.ndarray, nt: int = 200, device: int = 0, path="auto", scheme=0, formulation=0):
