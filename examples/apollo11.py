@@ -4,12 +4,14 @@
 This is this repository's own counterpart of the reference script: the same problem, declared with
 the same modelling calls, solved by libascent on an MI355X instead of GEKKO/APMonitor/IPOPT.  It prints
 the quantities the reference prints (/root/reference/Launch_Optimiser.py:178-194) and writes the same
-three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim] [--disperse]
+three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim] [--disperse] [--guide]
 --fly also integrates the ODEs under the control just found (RK4 on the device) and prints where that flight ends.
 --trim corrects (t_f, u) so that the flown control reaches the target orbit (trim_batch) and prints t_f and the flown apsides
 before and after.
 --disperse trims, then flies the trimmed control 1024 times with 50 N (1-sigma) of thrust error and 1e-3 of error on every control
 step (disperse_batch) and prints the Monte Carlo and the linear 1-sigma of the flown apsides side by side.
+--guide trims, computes the neighbouring-optimal feedback gains (guidance_gains) and flies the same 1024 dispersed samples open loop
+and under that feedback; prints both 1-sigmas of the flown apsides and the control authority the feedback took.
 """
 import argparse
 import os
@@ -143,6 +145,32 @@ def disperse(m, scheme, samples=1024):
     return d
 
 
+def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0):
+    """The trimmed solution under the same dispersions, open loop and steering back to the nominal with a cutoff on the state.
+    The cutoff channel stretches the last step only, T / K = 2.2 s here: 50 N of 15 kN over a 435 s burn is 1.4 s (1-sigma) of burn
+    time, so the stretch is allowed +-2 steps; at stretch_max = 0.5 it sits on its bound for most samples."""
+    from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, guidance_gains, trim_batch
+    res = m.result
+    kw = dict(scheme=scheme, formulation=m._formulation)
+    t = trim_batch(res.params, res.flight_blob(), res.nt, **kw)
+    g = guidance_gains(res.params, t.blob, res.nt, cond_weights=(weight,) * 3, control_weight=1.0, cutoff_weight=1.0, stretch_max=stretch_max, **kw)
+    thrust = np.zeros(16)
+    thrust[3] = 50.0
+    dkw = dict(param_sigma=thrust, control_sigma=1e-3, samples=samples, **kw)
+    op = disperse_batch(res.params, t.blob, res.nt, **dkw)
+    cl = disperse_batch(res.params, t.blob, res.nt, guidance=g, keep_samples=True, **dkw)
+    print("guidance: status %d, %d of %d controls free, largest steering gain %.4g, largest cutoff gain %.4g (weights %g, 1, 1)"
+          % (g.status[0], g.free_controls[0], res.nt - 1, g.max_gain[0], g.max_cutoff_gain[0], weight))
+    print("closed loop: %d of %d samples valid; thrust 1-sigma 50 N, control 1-sigma 1e-3 per step" % (cl.n_valid[0], samples))
+    print("flown altitude (m)      nominal   open loop 1-sigma   closed loop 1-sigma   closed loop min / max")
+    for name, q in (("periapsis", 7), ("apoapsis", 8)):
+        print("%-18s %12.1f %19.1f %21.2f %14.1f / %.1f" % (name, cl.nominal[0, q], op.std[0, q], cl.std[0, q], cl.min[0, q], cl.max[0, q]))
+    e = cl.effort[0]
+    print("control authority: a command clipped on %.2f steps per flight, largest |K.dz| %.3g, cutoff stretch 1-sigma %.3g (largest %.3g of %g)"
+          % (e[:, 0].mean(), np.nanmax(e[:, 1]), np.nanstd(e[:, 2]), np.nanmax(np.abs(e[:, 2])), stretch_max))
+    return op, cl, g
+
+
 def plots(m, v, outdir):
     import matplotlib
     matplotlib.use("Agg")
@@ -179,6 +207,7 @@ if __name__ == "__main__":
     ap.add_argument("--fly", action="store_true", help="fly the solution's control with RK4 on the device and print what it reaches")
     ap.add_argument("--trim", action="store_true", help="trim t_f and the control so that the flown trajectory reaches its orbit; prints before / after")
     ap.add_argument("--disperse", action="store_true", help="trim, then fly the trimmed control under 50 N of thrust and 1e-3 of control error 1024 times; prints Monte Carlo and linear 1-sigma of the flown apsides")
+    ap.add_argument("--guide", action="store_true", help="trim, compute LQ feedback gains and fly 1024 dispersed samples open loop and closed loop; prints both 1-sigmas of the flown apsides")
     a = ap.parse_args()
     model, variables, v_ins = build()
     if a.no_dcost:
@@ -193,5 +222,7 @@ if __name__ == "__main__":
         trim(model, a.scheme)
     if a.disperse:
         disperse(model, a.scheme)
+    if a.guide:
+        guide(model, a.scheme)
     if not a.no_plots:
         plots(model, variables, a.outdir)

@@ -386,6 +386,60 @@ int ascent_disperse_batch(const ascent_params *p, int64_t batch, const ascent_op
                           const double *sigma_u_or_null, double *stats_out, double *samples_out_or_null, int device_id,
                           void *hip_stream_or_null, int ptr_is_device);
 
+/* Guidance gains: the neighbouring-optimal linear feedback about a flown solution -- what a dispersed vehicle needs to steer
+ * back to the nominal flight and to cut off on its state, where ascent_disperse_batch flies it open loop.
+ * Linearisation: that of ascent_flight_jacobian, about the flight ascent_fly_batch computes at the blob.  Deviations (scaled
+ * units) obey dz_k = Phi_k dz_{k-1} + g_k du_k + [k = K] gamma_K tau: Phi_k = dz_k/dz_{k-1}, g_k = dz_k/du_k, gamma_K = dt *
+ * dz_K/d dt, tau the relative stretch of the last step's duration (the cutoff channel).
+ * Cost: 1/2 sum_i q_i (c_i' dz_K)^2 + 1/2 r_u sum_k du_k^2 + 1/2 r_t tau^2, c_i the gradients of the trim's three conditions
+ *   (e3, g1, g2) at the nominal flown z_K.  The target is the nominal flown end conditions, not c = 0: pass a trimmed blob
+ *   (ascent_trim_batch) to aim at the orbit.
+ * weights [6][batch]: q_e3, q_g1, q_g2 >= 0, r_u > 0, r_t > 0, stretch_max >= 0 (the bound of |tau|; 0: no cutoff channel).
+ * Recursion, plain form, k = K .. 1 from P_K = sum_i q_i c_i c_i': B holds the column g_k if |u_k| < 0.999 (the trim's rule: a
+ *   saturated control has no authority and its gain row is exactly 0) and the column gamma_K if k = K and stretch_max > 0;
+ *   S = R + B' P_k B, G = S^-1 B' P_k Phi_k, P_{k-1} = Phi_k' P_k Phi_k - G' S G, symmetrised by averaging; without a column
+ *   P_{k-1} = Phi_k' P_k Phi_k.  In double precision the recursion loses digits as q grows (relative to an 80-bit run of itself:
+ *   about 1e-12 at q = 1e6, 5e-8 at 1e9, 3e-5 at 1e12 on the nominal problem).
+ * gain_u_out [7][K][batch], element (state i, step k-1, problem) at ((i*K + k-1)*batch + problem): K_k, so that the commanded
+ *   control of step k is u_k - K_k . (z - z_{k-1}^nominal).   gain_t_out [7][batch]: k_t, tau = -k_t . (z - z_{K-1}^nominal); zero
+ *   where stretch_max = 0.
+ * summary_out [ASCENT_GUIDE_ROWS][batch]: 0 status (0 ok, 2 frozen)   1 number of free controls (|u_k| < 0.999)
+ *   2 max_k |K_k|_inf   3 |k_t|_inf   4 the substeps m used.
+ * A non-finite S, a pivot or a determinant of S <= 0, or a weights column outside the ranges above freezes the problem: status
+ *   2, NaN gains, NaN rows 2 / 3 and a NaN closed-loop Jacobian; no fault, bounded work.
+ * jac_cl_out_or_null [9][24][batch], jac_u_cl_out_or_null [9][K][batch] (the latter only with the former): the flight Jacobian
+ *   of the closed loop under these gains, clips ignored, rows / columns / layout of ascent_flight_jacobian; the column of u_k now
+ *   means the execution error of step k.  Where every gain is zero (q = 0) it is ascent_flight_jacobian's.
+ * Options, substeps, refusals (terminal = 2 included), garbage blobs, pointers and stream as ascent_flight_jacobian; a problem
+ * gives the same bits alone as inside any batch; with device pointers and a stream the call only enqueues two kernels. */
+#define ASCENT_GUIDE_ROWS 5
+int ascent_guidance_gains(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                          const double *weights, double *gain_u_out, double *gain_t_out, double *summary_out,
+                          double *jac_cl_out_or_null, double *jac_u_cl_out_or_null, int device_id, void *hip_stream_or_null,
+                          int ptr_is_device);
+
+/* Guided Monte Carlo dispersion: ascent_disperse_batch with every sample steering by a linear state feedback.  The gains are the
+ * caller's (ascent_guidance_gains' or any other), layouts as above.  Sample s at step k, from its state z at node k-1 (perfect
+ * state knowledge; blob and nominal flight fixed in scaled units):
+ *   dz = z - z_{k-1}^nominal (the flight of ascent_fly_batch at the blob);
+ *   commanded control clip(u_k - K_k . dz, -1, 1); where the gain row of the step is all zero, u_k itself, bit for bit;
+ *   executed control: the command + sigma_u[k-1][b] * xi[24+k-1][s], not clipped;
+ *   on the last step, with gain_t and stretch_max both given and stretch_max[b] > 0: the sample's dt times
+ *   1 + clip(-k_t . dz, -stretch_max[b], +stretch_max[b]).
+ *   A K_k . dz or k_t . dz that is not finite (NaN or inf gains) makes the command NaN: the sample is invalid.
+ * m is held as in ascent_disperse_batch: 4 * K * m right-hand sides per sample whatever the gains hold.
+ * stats_out exactly as ascent_disperse_batch: same reduction, same fixed order, same validity rule.  With all-zero gains and no
+ * stretch the call gives the bits of ascent_disperse_batch.
+ * samples_out_or_null [ASCENT_GUIDED_SAMPLE_ROWS][samples][batch]: the nine rows, then the number of steps whose command was
+ *   clipped, max_k |K_k . dz|, and the stretch applied.
+ * Refuses what ascent_disperse_batch refuses, and a null gain_u. */
+#define ASCENT_GUIDED_SAMPLE_ROWS 12
+int ascent_disperse_guided_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                                 int32_t substeps, int32_t samples, const double *xi, const double *sigma,
+                                 const double *sigma_u_or_null, const double *gain_u, const double *gain_t_or_null,
+                                 const double *stretch_max_or_null, double *stats_out, double *samples_out_or_null,
+                                 int device_id, void *hip_stream_or_null, int ptr_is_device);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

@@ -16,6 +16,7 @@
 //          products of the differences from the centre, 9 minima, 9 maxima) are reduced one at a time -- butterfly over the
 //          wave, wave 0..3 through LDS in that order -- into one partial record per workgroup.
 // f_disperse_stats  one lane per problem, problem-fastest: the partial records added in ascending chunk order, then the 82 rows.
+// f_disperse_guided f_disperse under state feedback (ascent_disperse_guided_batch): same mapping, same record, same reduction.
 // The order of every addition is fixed by `samples` alone: a problem gives the same bits alone as inside any batch.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -174,6 +175,123 @@ __global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict
   }
 }
 
+// f_disperse with the feedback of include/ascent.h: ascent_disperse_guided_batch.  Per step 7 nominal-state and 7 gain doubles
+// more, wave-uniform, loaded for the next step with its u before the current one is integrated.  The command of a step whose
+// gain row is all zero is u_k itself, and without a stretch hs is f_disperse's: such a flight has f_disperse's bits.  A
+// non-finite K.dz makes the command NaN, so the sample is invalid (a clip would hide it).
+template <int FORM>
+__global__ __launch_bounds__(DB) void f_disperse_guided(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
+                                                        int nwg, long g0, const double *__restrict__ blob,
+                                                        const double *__restrict__ traj, const double *__restrict__ fsum,
+                                                        const double *__restrict__ xi, const double *__restrict__ sigma,
+                                                        const double *__restrict__ sigma_u, const double *__restrict__ gain_u,
+                                                        const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
+                                                        double *__restrict__ partial, double *__restrict__ samples_out) {
+  __shared__ double red[DNW][NREC];
+  const long g = g0 + blockIdx.x;
+  const long p = g / nwg;
+  const int c = (int)(g - p * nwg);
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int s = c * DB + t;
+  const size_t B = (size_t)batch, NS = (size_t)samples;
+  const int nt = K + 1;
+  const double *b = blob + p;
+  const double *pf = reinterpret_cast<const double *>(P + p);      // the 16 fields in declaration order
+  const double tf0 = b[(size_t)(21 * K + S_TH) * B];
+  const int m = flight_substeps((tf0 * pf[11]) / K, substeps);      // the nominal flight's, held
+  double cen[NQ];
+  nominal_rows(traj, fsum, B, p, K, cen);
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) cen[q] = finite1(cen[q]) ? cen[q] : 0.0;
+
+  double r[NQ];
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) r[q] = NAN;
+  if (s < samples) {
+    const double *x = xi + s;
+    double sg[NC], xv[NC];
+    ASC_UNROLL
+    for (int i = 0; i < NC; i++) sg[i] = sigma[(size_t)i * B + p];
+    ASC_UNROLL
+    for (int i = 0; i < NC; i++) xv[i] = x[(size_t)i * NS];
+    double z[7], f[16];
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) z[i] = sg[i] != 0.0 ? sg[i] * xv[i] : 0.0;
+    ASC_UNROLL
+    for (int i = 0; i < 16; i++) f[i] = sg[7 + i] != 0.0 ? pf[i] + sg[7 + i] * xv[7 + i] : pf[i];
+    const double tf = sg[23] != 0.0 ? tf0 + sg[23] * xv[23] : tf0;
+    const ascent_params prm = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11], f[12], f[13], f[14], f[15]};
+    const Der d = derive(prm);
+    const double dt = (tf * d.T) / K;
+    const double hs = dt / m;
+    const double smax = gain_t && stretch_max ? stretch_max[p] : 0.0;
+    const double *ub = b + (size_t)(7 * K) * B, *su = sigma_u ? sigma_u + p : nullptr, *xu = x + (size_t)NC * NS;
+    const double *tr = traj + p, *gu = gain_u + p;
+    double un = ub[0], sgn = su ? su[0] : 0.0, xn = su ? xu[0] : 0.0, zn[7], kn[7];
+    load_node(tr, B, nt, 0, zn);
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) kn[i] = gu[(size_t)i * K * B];
+    double nclip = 0.0, dmax = 0.0, stretch = 0.0;
+    for (int k = 0; k < K; k++) {
+      // the command of this step from the state it starts at
+      double dz[7], dot = 0.0;
+      bool zero = true;
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) {
+        dz[i] = z[i] - zn[i];
+        dot += kn[i] * dz[i];
+        zero = zero && kn[i] == 0.0;
+      }
+      double uc = un;
+      if (!zero) {
+        const double w = un - dot;
+        uc = finite1(dot) ? fmin(1.0, fmax(-1.0, w)) : NAN;
+        nclip += uc != w ? 1.0 : 0.0;
+        dmax = (dot != dot || dmax != dmax) ? NAN : fmax(dmax, fabs(dot));
+      }
+      const double u = sgn != 0.0 ? uc + sgn * xn : uc;
+      double h = hs;
+      if (k == K - 1 && smax > 0.0) {
+        double dtau = 0.0;
+        ASC_UNROLL
+        for (int i = 0; i < 7; i++) dtau -= gain_t[(size_t)i * B + p] * dz[i];
+        stretch = finite1(dtau) ? fmin(smax, fmax(-smax, dtau)) : NAN;
+        h = (dt * (1.0 + stretch)) / m;
+      }
+      const int kq = k + 1 < K ? k + 1 : k;
+      un = ub[(size_t)kq * B]; sgn = su ? su[(size_t)kq * B] : 0.0; xn = su ? xu[(size_t)kq * NS] : 0.0;
+      load_node(tr, B, nt, kq, zn);
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) kn[i] = gu[((size_t)i * K + kq) * B];
+      fly_step<FORM>(d, z, u, h, m);
+    }
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) r[i] = z[i];
+    apsides_of(prm, z[IX], z[IY], z[IVX], z[IVY], r[7], r[8]);
+    if (samples_out) {
+      ASC_UNROLL
+      for (int q = 0; q < NQ; q++) samples_out[((size_t)q * NS + s) * B + p] = r[q];
+      samples_out[((size_t)(NQ + 0) * NS + s) * B + p] = nclip;
+      samples_out[((size_t)(NQ + 1) * NS + s) * B + p] = dmax;
+      samples_out[((size_t)(NQ + 2) * NS + s) * B + p] = stretch;
+    }
+  }
+  bool valid = true;
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) valid = valid && finite1(r[q]);
+  wave_record(r, valid, cen, lane, red[wv]);
+  __syncthreads();
+  const int nw = (int)blockDim.x >> 6;
+  for (int i = t; i < NREC; i += (int)blockDim.x) {
+    double a = red[0][i];
+    for (int w = 1; w < nw; w++) {
+      const double o = red[w][i];
+      a = i < R_MIN ? a + o : i < R_MAX ? fmin(a, o) : fmax(a, o);
+    }
+    partial[((size_t)c * NREC + i) * B + p] = a;
+  }
+}
+
 __global__ __launch_bounds__(SW) void f_disperse_stats(long batch, int K, int nwg, const double *__restrict__ traj,
                                                        const double *__restrict__ fsum, const double *__restrict__ partial,
                                                        double *__restrict__ stats) {
@@ -247,6 +365,29 @@ int disperse_run(const Call &c, int substeps, int samples, const double *dblob, 
     else
       hipLaunchKernelGGL((f_disperse<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
                          w.fsum, dxi, dsigma, dsigma_u, w.partial, dsamples);
+    ASC_CHK(c.err, c.errlen, hipGetLastError());
+  }
+  const dim3 gst((unsigned)((c.batch + SW - 1) / SW)), bst(SW);
+  hipLaunchKernelGGL(f_disperse_stats, gst, bst, 0, c.stream, c.batch, c.K, nwg, w.traj, w.fsum, w.partial, dstats);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
+  return ASCENT_OK;
+}
+
+int disperse_guided_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
+                        const double *dsigma_u, const double *dgain_u, const double *dgain_t, const double *dsmax, double *dstats,
+                        double *dsamples, double *ws) {
+  const DisperseWs w = carve(ws, c.K, c.batch);
+  if (const int rc = flight_fly_only(c, substeps, dblob, w.traj, w.fsum)) return rc;
+  const int nwg = groups_per_problem(samples);
+  const long total = c.batch * nwg;
+  for (long g0 = 0; g0 < total; g0 += MAX_GRID) {
+    const dim3 grid((unsigned)(total - g0 < MAX_GRID ? total - g0 : MAX_GRID)), block(threads_per_group(samples));
+    if (c.form == 1)
+      hipLaunchKernelGGL((f_disperse_guided<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
+                         w.fsum, dxi, dsigma, dsigma_u, dgain_u, dgain_t, dsmax, w.partial, dsamples);
+    else
+      hipLaunchKernelGGL((f_disperse_guided<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
+                         w.fsum, dxi, dsigma, dsigma_u, dgain_u, dgain_t, dsmax, w.partial, dsamples);
     ASC_CHK(c.err, c.errlen, hipGetLastError());
   }
   const dim3 gst((unsigned)((c.batch + SW - 1) / SW)), bst(SW);

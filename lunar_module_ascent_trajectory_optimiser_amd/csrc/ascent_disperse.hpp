@@ -18,4 +18,11 @@ size_t disperse_ws_bytes(int K, long batch, int samples);
 int disperse_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
                  const double *dsigma_u, double *dstats, double *dsamples, double *ws);
 
+// include/ascent.h: ascent_disperse_guided_batch.  As disperse_run, plus dgain_u [7][K][batch], dgain_t [7][batch] or null,
+// dsmax [batch] or null; dsamples [12][samples][batch] or null.  Same workspace, same three enqueues with f_disperse_guided in
+// f_disperse's place.
+int disperse_guided_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
+                        const double *dsigma_u, const double *dgain_u, const double *dgain_t, const double *dsmax, double *dstats,
+                        double *dsamples, double *ws);
+
 }  // namespace ascent

@@ -1,0 +1,318 @@
+// Guidance gains (include/ascent.h: ascent_guidance_gains): the neighbouring-optimal feedback about a flown solution.
+//
+// The linearisation is j_jac's (ascent_trim.hip): about the states f_fly wrote into the workspace trajectory, the step records
+// [Phi_k | g_k | Gamma_k] from fly_step_tangent.  Deviations obey dz_k = Phi_k dz_{k-1} + g_k du_k + [k = K] gamma_K tau with
+// gamma_K = dt dz_K/d dt (tau: the relative stretch of the last step), and the cost is
+//   1/2 sum_i q_i (c_i' dz_K)^2 + 1/2 r_u sum_k du_k^2 + 1/2 r_t tau^2,   c_i = grad (e3, g1, g2) of terminal_eval at z_K.
+//
+// g_gains  one workgroup of JB = 256 threads per NLP, chunks of CH = 16 steps, last chunk first; evaluation and LDS staging
+//          exactly as j_jac.  Wave 0 then takes the chunk's steps in descending order, P (7 x 7), Lambda (9 x 7) and the 9 x 8
+//          accumulators in LDS between the chunks:
+//   A      lane (i, j) < 49: M = P Phi;  lanes 49..55 / 56..62: w_u = P g, w_t = P gamma
+//   B      every lane, redundantly (LDS broadcasts): S = R + B' P B (at most 2 x 2: the column g if |u_k| < 0.999, the column
+//          gamma if k = K and stretch_max > 0), G = S^-1 (w' Phi) -- a division, or the closed-form 2 x 2 inverse on the last
+//          step --; lane j < 7 stores G_j.  A non-finite S, a pivot or a determinant <= 0 freezes the problem.
+//   C      lane (i, j) < 49: P <- 1/2 (N_ij + N_ji), N = Phi' M - G' S G, both halves computed by the lane itself, so P stays
+//          exactly symmetric;  lane q < 9: row q of Lambda <- Lambda (Phi - g K' - gamma k_t'), Lambda g to jac_u, Lambda Gamma
+//          into the accumulators -- j_jac's sweep with the gain terms taken off.
+//          The phases of one wavefront are ordered by LDS's in-order execution; wave_sync keeps the compiler from reordering them.
+//   epilogue   j_jac's chain rule, restated here (j_jac itself is left as it is: the trim depends on its bits).
+// The order of every addition is fixed: a problem gives the same bits alone as inside any batch.
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cmath>
+
+#include "ascent.h"
+#include "ascent_device.hpp"
+#include "ascent_flight.hpp"
+#include "ascent_flight_dev.hpp"
+#include "ascent_guide.hpp"
+#include "ascent_tangent_dev.hpp"
+#include "ascent_trim.hpp"
+
+namespace ascent {
+namespace {
+
+constexpr int GW = 64;                     // the sweeping wavefront
+constexpr int W_QE3 = 0, W_RU = 3, W_RT = 4, W_SMAX = 5;      // rows of weights [6][batch]
+
+ASC_DEV bool finite1(double a) { return fabs(a) <= 1.79769313486231570815e308; }
+ASC_DEV double max_nan2(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
+
+// orders the LDS traffic of the phases of one wavefront (the hardware executes a wavefront's LDS instructions in order)
+ASC_DEV void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int FORM>
+__global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ P, long batch, int K, int substeps,
+                                              const double *__restrict__ blob, const double *__restrict__ traj,
+                                              const double *__restrict__ weights, double *__restrict__ gain_u,
+                                              double *__restrict__ gain_t, double *__restrict__ summary,
+                                              double *__restrict__ jac, double *__restrict__ jac_u) {
+  __shared__ double rec[CH * REC];
+  __shared__ double Ps[49], Ms[49], Ws[14], Gs[14], Ls[JROWS * 7], As[JROWS * NACC];
+  __shared__ int frozen_s;
+  const long p = blockIdx.x;
+  const size_t B = (size_t)batch;
+  const int t = threadIdx.x, g = t >> 4, col = t & (NCOL - 1);
+  const int nt = K + 1;
+  const double *b = blob + p, *tr = traj + p;
+  const ascent_params prm = P[p];
+  const Der d = derive(prm);
+  const double tf = b[(size_t)(21 * K + S_TH) * B];
+  const double dt = (tf * d.T) / K;
+  const int m = flight_substeps(dt, substeps);
+  const double hs = dt / m;
+  const double ru = weights[(size_t)W_RU * B + p], rt = weights[(size_t)W_RT * B + p], smax = weights[(size_t)W_SMAX * B + p];
+  const int pi = t < 49 ? t / 7 : 0, pj = t % 7;      // lane (pi, pj) of P; every lane: column pj of a gain row
+
+  double dirG = 0.0, dirM = 0.0, dirR0 = 0.0, dirS = 0.0, nf = 0.0, gmax = 0.0, tmax = 0.0;
+  if (t < GW) {
+    double zK[7], gp[5], ga[5], q[3];
+    load_node(tr, B, nt, K, zK);
+    ASC_UNROLL
+    for (int i = 0; i < 3; i++) q[i] = weights[(size_t)(W_QE3 + i) * B + p];
+    const bool wok = q[0] >= 0.0 && q[1] >= 0.0 && q[2] >= 0.0 && ru > 0.0 && rt > 0.0 && smax >= 0.0 && finite1(q[0]) &&
+                     finite1(q[1]) && finite1(q[2]) && finite1(ru) && finite1(rt) && finite1(smax);
+    if (t == 0) frozen_s = wok ? 0 : 1;
+    // P_K = sum_i q_i c_i c_i'
+    const Terminal tm = terminal_eval(d, zK);
+    const double cg[3][7] = {{tm.e3g[0], tm.e3g[1], tm.e3g[2], tm.e3g[3], 0.0, 0.0, 0.0},
+                             {tm.g1g[0], tm.g1g[1], 0.0, 0.0, 0.0, 0.0, 0.0},
+                             {0.0, 0.0, tm.g2g[0], tm.g2g[1], 0.0, 0.0, 0.0}};
+    if (t < 49) {
+      double a = 0.0;
+      ASC_UNROLL
+      for (int i = 0; i < 3; i++) {
+        double ci = 0.0, cj = 0.0;
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) { ci = l == pi ? cg[i][l] : ci; cj = l == pj ? cg[i][l] : cj; }
+        a += q[i] * (ci * cj);
+      }
+      Ps[t] = a;
+    }
+    // Lambda_K = I / grad apsides, as j_jac
+    if (jac) {
+      apsides_grad(prm, zK[IX], zK[IY], zK[IVX], zK[IVY], gp, ga);
+      if (t < JROWS) {
+        double L[7];
+        ASC_UNROLL
+        for (int i = 0; i < 7; i++) L[i] = t == i ? 1.0 : 0.0;
+        if (t == 7 || t == 8) {
+          const double *gq = t == 7 ? gp : ga;
+          const double S = prm.r_peri;
+          L[IX] = S * gq[0]; L[IY] = S * gq[1]; L[IVX] = S * gq[2]; L[IVY] = S * gq[3];
+          dirS = zK[IX] * gq[0] + zK[IY] * gq[1] + zK[IVX] * gq[2] + zK[IVY] * gq[3];
+          dirR0 = gq[1] - 1.0;
+          dirG = prm.M * gq[4];
+          dirM = prm.G * gq[4];
+        }
+        ASC_UNROLL
+        for (int i = 0; i < 7; i++) Ls[t * 7 + i] = L[i];
+        ASC_UNROLL
+        for (int a = 0; a < NACC; a++) As[t * NACC + a] = 0.0;
+      }
+    }
+    for (int k = t; k < K; k += GW) nf += fabs(b[(size_t)(7 * K + k) * B]) < 0.999 ? 1.0 : 0.0;
+    nf = wave_sum(nf);
+  }
+  __syncthreads();
+
+  const int nch = (K + CH - 1) / CH;
+  for (int c = nch - 1; c >= 0; c--) {
+    if (frozen_s) break;                      // uniform: read between two barriers
+    const int k = c * CH + g + 1;             // this group's step: node k-1 -> k
+    if (k <= K) {
+      double z[7], dz[7];
+      load_node(tr, B, nt, k - 1, z);
+      const double u = b[(size_t)(7 * K + k - 1) * B];
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) dz[i] = col == i ? 1.0 : 0.0;
+      fly_step_tangent<FORM>(d, z, dz, u, hs, m, col);
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) rec[g * REC + i * NCOL + col] = dz[i];
+    }
+    __syncthreads();
+    if (t < GW) {
+      const int top = K - c * CH < CH ? K - c * CH : CH;
+      bool ok = true;
+      for (int s = top - 1; s >= 0 && ok; s--) {
+        const double *R = rec + s * REC;
+        const int kk = c * CH + s;            // step kk + 1
+        const double uk = b[(size_t)(7 * K + kk) * B];
+        const bool f1 = fabs(uk) < 0.999, f2 = kk + 1 == K && smax > 0.0;
+        // A
+        if (t < 49) {
+          double a = 0.0;
+          ASC_UNROLL
+          for (int l = 0; l < 7; l++) a += Ps[pi * 7 + l] * R[l * NCOL + pj];
+          Ms[t] = a;
+        } else if (t < 63) {
+          const int cc = t < 56 ? C_U : C_DT;
+          const double sc = t < 56 ? 1.0 : dt;
+          double a = 0.0;
+          ASC_UNROLL
+          for (int l = 0; l < 7; l++) a += Ps[pj * 7 + l] * (sc * R[l * NCOL + cc]);
+          Ws[t - 49] = a;
+        }
+        wave_sync();
+        // B
+        double s11 = ru, s12 = 0.0, s22 = rt, h1 = 0.0, h2 = 0.0;
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) {
+          const double gl = R[l * NCOL + C_U], tl = dt * R[l * NCOL + C_DT];
+          s11 += gl * Ws[l];
+          s12 += gl * Ws[7 + l];
+          s22 += tl * Ws[7 + l];
+          h1 += Ws[l] * R[l * NCOL + pj];
+          h2 += Ws[7 + l] * R[l * NCOL + pj];
+        }
+        double g1 = 0.0, g2 = 0.0;
+        if (f1 && f2) {
+          const double det = s11 * s22 - s12 * s12;
+          ok = finite1(s11) && finite1(s12) && finite1(s22) && s11 > 0.0 && s22 > 0.0 && det > 0.0;
+          g1 = (s22 * h1 - s12 * h2) / det;
+          g2 = (s11 * h2 - s12 * h1) / det;
+        } else if (f1) {
+          ok = finite1(s11) && s11 > 0.0;
+          g1 = h1 / s11;
+          s12 = 0.0; s22 = 0.0;
+        } else if (f2) {
+          ok = finite1(s22) && s22 > 0.0;
+          g2 = h2 / s22;
+          s11 = 0.0; s12 = 0.0;
+        } else {
+          s11 = 0.0; s12 = 0.0; s22 = 0.0;
+        }
+        if (!ok) break;                       // uniform: every lane computed the same S
+        if (t < 7) {
+          Gs[t] = g1;
+          Gs[7 + t] = g2;
+          gain_u[((size_t)t * K + kk) * B + p] = g1;
+          if (kk + 1 == K) gain_t[(size_t)t * B + p] = g2;
+          gmax = max_nan2(gmax, fabs(g1));
+          tmax = max_nan2(tmax, fabs(g2));
+        }
+        wave_sync();
+        // C
+        if (t < 49) {
+          double nij = 0.0, nji = 0.0;
+          ASC_UNROLL
+          for (int l = 0; l < 7; l++) {
+            nij += R[l * NCOL + pi] * Ms[l * 7 + pj];
+            nji += R[l * NCOL + pj] * Ms[l * 7 + pi];
+          }
+          const double ui = Gs[pi], uj = Gs[pj], ti = Gs[7 + pi], tj = Gs[7 + pj];
+          nij -= ui * (s11 * uj + s12 * tj) + ti * (s12 * uj + s22 * tj);
+          nji -= uj * (s11 * ui + s12 * ti) + tj * (s12 * ui + s22 * ti);
+          Ps[t] = 0.5 * (nij + nji);
+        }
+        if (jac && t < JROWS) {
+          double L[7], o[NCOL];
+          ASC_UNROLL
+          for (int i = 0; i < 7; i++) L[i] = Ls[t * 7 + i];
+          ASC_UNROLL
+          for (int cc = 0; cc < NCOL; cc++) {
+            double a = 0.0;
+            ASC_UNROLL
+            for (int i = 0; i < 7; i++) a += L[i] * R[i * NCOL + cc];
+            o[cc] = a;
+          }
+          if (jac_u) jac_u[((size_t)t * K + kk) * B + p] = o[C_U];
+          ASC_UNROLL
+          for (int a = 0; a < NACC; a++) As[t * NACC + a] += o[C_DT + a];
+          const double ot = dt * o[C_DT];
+          ASC_UNROLL
+          for (int i = 0; i < 7; i++) {
+            double v = o[i];
+            if (f1) v -= o[C_U] * Gs[i];
+            if (f2) v -= ot * Gs[7 + i];
+            Ls[t * 7 + i] = v;
+          }
+        }
+        wave_sync();
+      }
+      if (!ok && t == 0) frozen_s = 1;
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  const bool frozen = frozen_s != 0;
+
+  if (t < GW) {
+    gmax = t < 7 ? gmax : 0.0;
+    tmax = t < 7 ? tmax : 0.0;
+    ASC_UNROLL
+    for (int off = 4; off >= 1; off >>= 1) { gmax = max_nan2(gmax, __shfl_xor(gmax, off)); tmax = max_nan2(tmax, __shfl_xor(tmax, off)); }
+    if (t == 0) {
+      summary[(size_t)0 * B + p] = frozen ? 2.0 : 0.0;
+      summary[(size_t)1 * B + p] = nf;
+      summary[(size_t)2 * B + p] = frozen ? NAN : gmax;
+      summary[(size_t)3 * B + p] = frozen ? NAN : tmax;
+      summary[(size_t)4 * B + p] = (double)m;
+    }
+  }
+  if (frozen) {                               // NaN gains and Jacobian; after the sweeping wavefront's own stores have landed
+    __threadfence();
+    __syncthreads();
+    for (int e = t; e < 7 * K; e += JB) gain_u[(size_t)e * B + p] = NAN;
+    if (t < 7) gain_t[(size_t)t * B + p] = NAN;
+    if (jac)
+      for (int e = t; e < JROWS * JCOLS; e += JB) jac[(size_t)e * B + p] = NAN;
+    if (jac_u)
+      for (int e = t; e < JROWS * K; e += JB) jac_u[(size_t)e * B + p] = NAN;
+    return;
+  }
+
+  if (jac && t < JROWS) {
+    const double S = prm.r_peri, R0 = prm.R0;
+    const double *A = As + t * NACC;
+    const double aDT = A[0], aRHO0 = A[1 + ACC_RHO0], aGAM = A[1 + ACC_GAM], aTHR = A[1 + ACC_THR], aM0 = A[1 + ACC_M0],
+                 aMS = A[1 + ACC_MS], aAL = A[C_ALPHA - C_DT], aMR = A[C_MRATE - C_DT];
+    double o[JCOLS];
+    ASC_UNROLL
+    for (int i = 0; i < 7; i++) o[i] = Ls[t * 7 + i];
+    const double S3 = S * S * S;
+    o[7 + 0] = aGAM * prm.M / S3 + dirG;                              // G
+    o[7 + 1] = aGAM * prm.G / S3 + dirM;                              // M
+    o[7 + 2] = aRHO0 / S + dirR0;                                     // R0
+    o[7 + 3] = aTHR / S;                                              // Ft
+    o[7 + 4] = aM0;                                                   // M0
+    o[7 + 5] = aMR / prm.fuel_mass;                                   // mdot
+    o[7 + 6] = -aMR * d.mrate / prm.fuel_mass;                        // fuel_mass
+    o[7 + 7] = aMS;                                                   // mass_scalar
+    o[7 + 8] = FORM == 1 ? 0.0 : aAL / 3.0;                           // ang_acc_max
+    o[7 + 9] = -aRHO0 * R0 / (S * S) - 3.0 * aGAM * d.gam / S - aTHR * d.thr / S + dirS;     // r_peri
+    o[7 + 10] = 0.0;                                                  // r_apo
+    o[7 + 11] = aDT * (tf / K);                                       // T_scale
+    o[7 + 12] = FORM == 1 ? aAL : 0.0;                                // angle_ub
+    o[7 + 13] = 0.0; o[7 + 14] = 0.0; o[7 + 15] = 0.0;                // tf_lb, tf_ub, dcost
+    o[23] = aDT * (d.T / K);                                          // t_f
+    ASC_UNROLL
+    for (int cc = 0; cc < JCOLS; cc++) jac[((size_t)t * JCOLS + cc) * B + p] = o[cc];
+  }
+}
+
+}  // namespace
+
+size_t gains_ws_bytes(int K, long batch) { return jac_ws_bytes(K, batch); }
+
+int gains_run(const Call &c, int substeps, const double *dblob, const double *dweights, double *dgain_u, double *dgain_t,
+              double *dsummary, double *djac, double *djac_u, double *ws) {
+  double *traj = ws, *fsum = ws + (size_t)ASCENT_TRAJ_FIELDS * (c.K + 1) * (size_t)c.batch;      // the carve of jac_run
+  if (const int rc = flight_fly_only(c, substeps, dblob, traj, fsum)) return rc;
+  const dim3 grid((unsigned)c.batch), block(JB);
+  if (c.form == 1)
+    hipLaunchKernelGGL((g_gains<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, traj, dweights, dgain_u, dgain_t,
+                       dsummary, djac, djac_u);
+  else
+    hipLaunchKernelGGL((g_gains<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, traj, dweights, dgain_u, dgain_t,
+                       dsummary, djac, djac_u);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
+  return ASCENT_OK;
+}
+
+}  // namespace ascent

@@ -32,121 +32,15 @@
 #include "ascent_device.hpp"
 #include "ascent_flight.hpp"
 #include "ascent_flight_dev.hpp"
+#include "ascent_tangent_dev.hpp"
 #include "ascent_trim.hpp"
 
 namespace ascent {
 namespace {
 
-constexpr int JB = 256;                    // j_jac: threads per workgroup
-constexpr int CH = 16;                     // steps per chunk = groups per workgroup
-constexpr int NCOL = 16;                   // tangent columns per step = lanes per group
-constexpr int REC = 7 * NCOL;              // doubles per step record
-constexpr int C_U = 7, C_DT = 8, C_DER = 9, C_ALPHA = 14, C_MRATE = 15;      // C_DER + ACC_RHO0 .. ACC_MS, then alpha | angle_ub, mrate
-constexpr int NACC = 8;                    // accumulators of the sweep: columns C_DT .. C_MRATE
-constexpr int JROWS = 9, JCOLS = 24;
 constexpr int TW = 64;                     // t_update / t_final: one wavefront per NLP
 // per-problem state of the trim between its kernels, rows of [ST_ROWS][batch]
 constexpr int ST_FLAG = 0 /* 0 active, 1 converged, 2 non-finite or singular */, ST_ROUNDS = 1, ST_C0 = 2, ST_NFREE = 3, ST_ROWS = 4;
-
-// f(z, u) and its tangent dF = f_z dz + (the column's own forcing): (fx, fy) picked from d accel / d Der for the columns
-// C_DER .. C_DER + 4, cw on the angledot row (alpha for the control column, u for the alpha column), cm on the mass row (mrate)
-template <int FORM>
-ASC_DEV void stage(const Der &d, const double *z, const double *dz, double u, int col, double cw, double cm, double *F, double *dF) {
-  double ax, ay, G[8], dax[ACC_NDER], day[ACC_NDER];
-  accel<1>(d, z[IX], z[IY], z[IA], z[IM], 0.0, 0.0, ax, ay, G, nullptr);
-  accel_dder(d, z[IX], z[IY], z[IA], z[IM], dax, day);
-  rhs_f<FORM>(d, z, u, ax, ay, F);
-  double fx = 0.0, fy = 0.0;
-  ASC_UNROLL
-  for (int j = 0; j < ACC_NDER; j++) {
-    const bool s = col == C_DER + j;
-    fx = s ? dax[j] : fx;
-    fy = s ? day[j] : fy;
-  }
-  dF[IX] = dz[IVX];
-  dF[IY] = dz[IVY];
-  dF[IVX] = G[0] * dz[IX] + G[1] * dz[IY] + G[2] * dz[IA] + G[3] * dz[IM] + fx;
-  dF[IVY] = G[4] * dz[IX] + G[5] * dz[IY] + G[6] * dz[IA] + G[7] * dz[IM] + fy;
-  dF[IA] = FORM == 1 ? 0.0 : dz[IW];
-  dF[IW] = FORM == 1 ? 0.0 : cw;
-  dF[IM] = cm;
-}
-
-// fly_step (ascent_flight_dev.hpp) with one tangent column carried along: z the same arithmetic, dz the exact derivative of it
-template <int FORM>
-ASC_DEV void fly_step_tangent(const Der &d, double *z, double *dz, double u, double hs, int m, int col) {
-  double cw = 0.0, cm = col == C_MRATE ? 1.0 : 0.0;
-  const double dhs = col == C_DT ? 1.0 / m : 0.0;      // hs = dt / m
-  if (FORM == 1) {
-    z[IA] = 0.5 * d.aub * (u + 1.0); z[IW] = 0.0;
-    dz[IA] = col == C_U ? 0.5 * d.aub : col == C_ALPHA ? 0.5 * (u + 1.0) : 0.0;
-    dz[IW] = 0.0;
-  } else {
-    cw = col == C_U ? d.alpha : col == C_ALPHA ? u : 0.0;
-  }
-  for (int j = 0; j < m; j++) {
-    double k1[7], k2[7], k3[7], k4[7], w[7], d1[7], d2[7], d3[7], d4[7], dw[7];
-    stage<FORM>(d, z, dz, u, col, cw, cm, k1, d1);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) { w[i] = z[i] + 0.5 * hs * k1[i]; dw[i] = dz[i] + 0.5 * (hs * d1[i] + dhs * k1[i]); }
-    stage<FORM>(d, w, dw, u, col, cw, cm, k2, d2);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) { w[i] = z[i] + 0.5 * hs * k2[i]; dw[i] = dz[i] + 0.5 * (hs * d2[i] + dhs * k2[i]); }
-    stage<FORM>(d, w, dw, u, col, cw, cm, k3, d3);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) { w[i] = z[i] + hs * k3[i]; dw[i] = dz[i] + (hs * d3[i] + dhs * k3[i]); }
-    stage<FORM>(d, w, dw, u, col, cw, cm, k4, d4);
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) {
-      const double ks = k1[i] + 2.0 * (k2[i] + k3[i]) + k4[i], ds = d1[i] + 2.0 * (d2[i] + d3[i]) + d4[i];
-      z[i] += hs * (1.0 / 6.0) * ks;
-      dz[i] += (1.0 / 6.0) * (hs * ds + dhs * ks);
-    }
-  }
-}
-
-// Gradients of apsides_of's periapsis / apoapsis altitude with respect to (X, Y, VX, VY, GM) in SI units at a scaled state;
-// returns false where the specific energy is >= 0 (the apoapsis gradient is then NaN).  With E = v^2/2 - GM/r, h = X VY - Y VX,
-// a = -GM / (2 E) and the eccentricity vector (ex, ey) = (v^2/GM - 1/r) r - (r.v/GM) v of apsides_of: periapsis a (1 - e),
-// apoapsis a (1 + e); E >= 0: periapsis h^2 / (GM (1 + e)).  e and its gradient come from the vector, de = (ex dex + ey dey) / e
-// (accurate to about eps / e; e^2 = 1 + 2 E h^2 / GM^2 loses eps / e^2).  At e exactly 0 the apsides have a kink (e = |(ex, ey)|)
-// and no gradient: de is set to 0, so that both rows are the gradient of a - R0, the mean of the one-sided derivatives.
-ASC_DEV bool apsides_grad(const ascent_params &prm, double x, double y, double vx, double vy, double *gp, double *ga) {
-  const double S = prm.r_peri, GM = prm.G * prm.M;
-  const double X = x * S, Y = y * S + prm.R0, VX = vx * S, VY = vy * S;
-  const double r = sqrt(X * X + Y * Y), v2 = VX * VX + VY * VY, rv = X * VX + Y * VY;
-  const double E = 0.5 * v2 - GM / r, h = X * VY - Y * VX;
-  const double ir3 = 1.0 / (r * r * r);
-  const double c = v2 / GM - 1.0 / r, d = rv / GM;      // (ex, ey) = c (X, Y) - d (VX, VY)
-  const double ex = c * X - d * VX, ey = c * Y - d * VY;
-  const double e = sqrt(ex * ex + ey * ey);
-  const double dE[5] = {GM * X * ir3, GM * Y * ir3, VX, VY, -1.0 / r};
-  const double dh[5] = {VY, -VX, -Y, X, 0.0};
-  const double dc[5] = {X * ir3, Y * ir3, 2.0 * VX / GM, 2.0 * VY / GM, -v2 / (GM * GM)};
-  const double dd[5] = {VX / GM, VY / GM, X / GM, Y / GM, -rv / (GM * GM)};
-  double de[5];
-  ASC_UNROLL
-  for (int i = 0; i < 5; i++) {
-    const double dex = dc[i] * X - dd[i] * VX + (i == 0 ? c : 0.0) - (i == 2 ? d : 0.0);
-    const double dey = dc[i] * Y - dd[i] * VY + (i == 1 ? c : 0.0) - (i == 3 ? d : 0.0);
-    de[i] = e > 0.0 ? (ex * dex + ey * dey) / e : 0.0;
-  }
-  if (E >= 0.0) {
-    const double q = 1.0 / (GM * (1.0 + e));
-    ASC_UNROLL
-    for (int i = 0; i < 5; i++) { gp[i] = 2.0 * h * q * dh[i] - h * h * q / (1.0 + e) * de[i]; ga[i] = NAN; }
-    gp[4] -= h * h * q / GM;
-    return false;
-  }
-  const double a = -GM / (2.0 * E);
-  double da[5];
-  ASC_UNROLL
-  for (int i = 0; i < 5; i++) da[i] = GM / (2.0 * E * E) * dE[i];
-  da[4] -= 1.0 / (2.0 * E);
-  ASC_UNROLL
-  for (int i = 0; i < 5; i++) { gp[i] = (1.0 - e) * da[i] - a * de[i]; ga[i] = (1.0 + e) * da[i] + a * de[i]; }
-  return true;
-}
 
 template <int FORM>
 __global__ __launch_bounds__(JB) void j_jac(const ascent_params *__restrict__ P, long batch, int K, int substeps,

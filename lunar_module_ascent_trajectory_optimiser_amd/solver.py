@@ -153,6 +153,7 @@ class DispersionResult:
     param_sigma: np.ndarray         # (batch, 16) SI units
     tf_sigma: np.ndarray            # (batch,) scaled units
     control_sigma: np.ndarray       # (batch, K)
+    effort: np.ndarray | None = None    # (batch, samples, 3) guided flights with keep_samples: EFFORT_ROWS
 
     @property
     def std(self) -> np.ndarray:
@@ -172,6 +173,27 @@ class DispersionResult:
         A = np.concatenate(A, axis=2)
         C = np.atleast_2d(np.cov(self.xi[:n]))
         return np.einsum("bqc,cd,brd->bqr", A, C, A)
+
+
+EFFORT_ROWS = ("clipped_steps", "max_feedback", "stretch")
+GUIDE_ROWS = ("status", "free_controls", "max_gain", "max_cutoff_gain", "substeps")
+GUIDE_STATUS_NAMES = {0: "ok", 2: "frozen"}
+
+
+@dataclasses.dataclass
+class GuidanceResult:
+    """Neighbouring-optimal feedback gains about a flown solution (guidance_gains; include/ascent.h: ascent_guidance_gains).
+    Step k commands u_k - gain_u[:, k-1] . (z - z_{k-1}^nominal); the last step's duration is stretched by the relative amount
+    -gain_t . (z - z_{K-1}^nominal), clipped to +-stretch_max.  Problem index first."""
+    gain_u: np.ndarray              # (batch, K, 7); the row of a saturated control is exactly zero
+    gain_t: np.ndarray              # (batch, 7) zero where stretch_max = 0
+    summary: np.ndarray             # (batch, 5) columns GUIDE_ROWS
+    stretch_max: np.ndarray         # (batch,)
+    jacobian: FlightJacobian | None     # the flight Jacobian of the closed loop, clips ignored; dcontrols: execution errors
+
+
+for _i, _n in enumerate(GUIDE_ROWS):    # the summary columns by name: .status, .free_controls, ... -> (batch,)
+    setattr(GuidanceResult, _n, property(lambda self, _i=_i: self.summary[:, _i]))
 
 
 @dataclasses.dataclass
@@ -260,7 +282,8 @@ class BatchResult:
         return coast_batch(self.params, np.ascontiguousarray(self.flight.traj[:, :4, -1].T), coast_nodes, device)
 
     def disperse(self, **kw) -> "DispersionResult":
-        """Monte Carlo dispersion of these solutions' flights: disperse_batch(self.params, the blob, self.nt, **kw).  A result
+        """Monte Carlo dispersion of these solutions' flights: disperse_batch(self.params, the blob, self.nt, **kw), with
+        guidance=<a GuidanceResult of the same blob> under that feedback.  A result
         does not keep the options it was solved with: repeat scheme, formulation, terminal and move_penalty in kw as for
         disperse_batch -- a formulation-1 solution dispersed without formulation=1 is flown as formulation 0."""
         return disperse_batch(self.params, self.blob if self.blob is not None else self.flight_blob(), self.nt, **kw)
@@ -452,7 +475,7 @@ def trim_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, t
 
 def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, control_sigma=None, tf_sigma=None, z0_sigma=None,
                    samples: int = 256, seed: int = 0, xi=None, keep_samples: bool = False, scheme=0, formulation=0, terminal=0,
-                   move_penalty: bool = False, substeps: int = 0, device: int = 0) -> DispersionResult:
+                   move_penalty: bool = False, substeps: int = 0, device: int = 0, guidance: GuidanceResult | None = None) -> DispersionResult:
     """Monte Carlo dispersion (include/ascent.h: ascent_disperse_batch): every blob's control flown `samples` times on the
     device as fly_batch flies it, with the initial state, the 16 parameter fields, t_f and every control perturbed by
     sigma * xi, and the nine end quantities reduced on the device to count, mean, covariance and extrema.  The blob is shared
@@ -460,7 +483,10 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     broadcast like FlightJacobian.sigma's; tf_sigma a scalar or (batch,) in scaled units; z0_sigma (7,) or (batch, 7) in scaled
     units; None: not perturbed.  xi (24 + K, samples): the draws, shared by every problem of the batch (common random numbers);
     None draws np.random.default_rng(seed).standard_normal((24 + K, samples)).  The substeps picked at the nominal blob are held
-    for every sample.  keep_samples: also return every sample's rows.  terminal 2 is accepted."""
+    for every sample.  keep_samples: also return every sample's rows.  terminal 2 is accepted.
+    guidance: a GuidanceResult (or anything with gain_u (batch, K, 7), gain_t (batch, 7) or None and stretch_max): every sample
+    steers by that feedback (include/ascent.h: ascent_disperse_guided_batch) and, with keep_samples, `effort` (batch, samples, 3)
+    holds EFFORT_ROWS.  None: the open-loop call."""
     L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     if xi is None:
         xi = np.random.default_rng(seed).standard_normal((24 + K, int(samples)))
@@ -474,13 +500,53 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     sig = np.ascontiguousarray(np.concatenate([zs, ps, ts], axis=1).T)
     sig_u = np.ascontiguousarray(us.T) if control_sigma is not None else None
     stats = np.empty((82, B))
-    smp = np.empty((9, S, B)) if keep_samples else None
-    _lib.check(L.ascent_disperse_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
-                                       _ptr(stats), _ptr(smp), device, None, 0))
+    smp = np.empty((9 if guidance is None else 12, S, B)) if keep_samples else None
+    if guidance is None:
+        _lib.check(L.ascent_disperse_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
+                                           _ptr(stats), _ptr(smp), device, None, 0))
+    else:
+        gu = np.ascontiguousarray(np.asarray(guidance.gain_u, dtype=np.float64).transpose(2, 1, 0))
+        if gu.shape != (7, K, B):
+            raise ValueError(f"guidance.gain_u must have shape {(B, K, 7)}")
+        gt = None if guidance.gain_t is None else np.ascontiguousarray(np.asarray(guidance.gain_t, dtype=np.float64).T)
+        if gt is not None and gt.shape != (7, B):
+            raise ValueError(f"guidance.gain_t must have shape {(B, 7)}")
+        sm = None if gt is None else _sigma_rows(np.asarray(guidance.stretch_max, dtype=np.float64)[..., None], 1, B, "stretch_max")[:, 0].copy()
+        _lib.check(L.ascent_disperse_guided_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
+                                                  _ptr(gu), _ptr(gt), _ptr(sm), _ptr(stats), _ptr(smp), device, None, 0))
     st = stats.T
     return DispersionResult(st[:, 0].astype(np.int64), np.ascontiguousarray(st[:, 1:10]), np.ascontiguousarray(st[:, 10:19]),
                             _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
-                            None if smp is None else np.ascontiguousarray(smp.transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us)
+                            None if smp is None else np.ascontiguousarray(smp[:9].transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us,
+                            None if smp is None or guidance is None else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)))
+
+
+def guidance_gains(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,
+                   substeps: int = 0, device: int = 0, cond_weights=(1e6, 1e6, 1e6), control_weight=1.0, cutoff_weight=1.0,
+                   stretch_max=0.5, want_jacobian: bool = True) -> GuidanceResult:
+    """Guidance gains (include/ascent.h: ascent_guidance_gains): the linear-quadratic feedback about the flight of a blob
+    (21K+10, batch) -- normally a trimmed one, since the target is what the nominal control reaches -- from a backward Riccati
+    sweep over the step records of the flight Jacobian.  cond_weights (3,) or (batch, 3): the weights q of the squared
+    deviations of the trim's three conditions at the last node; control_weight r_u and cutoff_weight r_t, scalars or (batch,),
+    weigh du_k^2 and the squared relative stretch tau^2 of the last step; stretch_max bounds |tau| (0: steering only).  In double
+    precision the gains lose digits as q grows (about 1e-12 at 1e6, 3e-5 at 1e12).  Returns a GuidanceResult; pass it to
+    disperse_batch(..., guidance=...).  terminal 2 is refused."""
+    L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
+    w = np.ascontiguousarray(np.concatenate([_sigma_rows(cond_weights, 3, B, "cond_weights")] + [
+        _sigma_rows(np.asarray(v, dtype=np.float64)[..., None], 1, B, n)
+        for v, n in ((control_weight, "control_weight"), (cutoff_weight, "cutoff_weight"), (stretch_max, "stretch_max"))], axis=1).T)
+    gu, gt, summ = np.empty((7, K, B)), np.empty((7, B)), np.empty((len(GUIDE_ROWS), B))
+    jac = np.empty((9, 24, B)) if want_jacobian else None
+    ju = np.empty((9, K, B)) if want_jacobian else None
+    _lib.check(L.ascent_guidance_gains(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(w), _ptr(gu), _ptr(gt), _ptr(summ),
+                                       _ptr(jac), _ptr(ju), device, None, 0))
+    J = None
+    if want_jacobian:
+        j = jac.transpose(2, 0, 1)
+        J = FlightJacobian(np.ascontiguousarray(j[:, :, :7]), np.ascontiguousarray(j[:, :, 7:23]), np.ascontiguousarray(j[:, :, 23]),
+                           np.ascontiguousarray(ju.transpose(2, 0, 1)))
+    return GuidanceResult(np.ascontiguousarray(gu.transpose(2, 1, 0)), np.ascontiguousarray(gt.T), np.ascontiguousarray(summ.T),
+                          w[5].copy(), J)
 
 
 def eval_nodes(params, iterate: np.ndarray, nt: int = 200, device: int = 0, path="auto", scheme=0, formulation=0):
