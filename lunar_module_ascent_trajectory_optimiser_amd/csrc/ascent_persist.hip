@@ -548,99 +548,107 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
     // ============================ A: trial point, merit function and KKT error ======================================
     int state = (int)sc[X_STATE];
     if (__all(state == ST_DONE)) break;
-    if (state == ST_TRIAL) {
-      const bool first = sc[X_FIRST] != 0.0;
-      const double alpha = first ? 0.0 : sc[X_ALPHA], adu = first ? 0.0 : sc[X_ADU], mu = sc[X_MU];
-      const Scal s = lds_scal(sc, X_S), ds = lds_scal(sc, X_D);
-      const Scal stt = trial_scal(d, s, ds, alpha, adu, mu, first);
-      const int cur = (int)sc[X_CUR];
-      const double *ic = w + (size_t)(cur * NIT) * Kp, *stp = w + (size_t)R_ST * Kp;
-      double *in = w + (size_t)((1 - cur) * NIT) * Kp;
-      const double dt = hT * stt.th, be = dt * d.alpha;
-      const double mlo = mu * 1e-10, mhi = mu * 1e10;
-      Part P;
-      if (sc[X_TEVAL] != 0.0) {             // evaluated by the adjoint phase of the previous round
-        P.rd = sc[X_P + 0]; P.cinf = sc[X_P + 1]; P.pmin = sc[X_P + 2]; P.pmax = sc[X_P + 3]; P.l1 = sc[X_P + 4];
-        P.zsum = sc[X_P + 5]; P.rth = sc[X_P + 6]; P.c1 = sc[X_P + 7]; P.sl = sc[X_P + 8]; P.mv = sc[X_P + 9];
-      } else {
-        TrialCtx t;
-        t.alpha = alpha; t.adu = adu; t.mlo = mlo; t.mhi = mhi; t.dt = dt; t.be = be; t.hT = hT; t.first = first; t.stt = stt; t.dcw = dcw;
-        P.clear();
-        for (int c = 0; c < nch; c++) {
-          const int k = c * CHN + nl;
-          if (k < K) {
-            NodeIn n, dn;
-            load_node<MP>(ic, Kp, K, k, n, UINIT);
-            if (first) dn = NodeIn{};             // (no step yet; the step rows are not initialised)
-            else load_node<MP>(stp, Kp, K, k, dn);
-            trial_node<SCHEME, FORM, MP, TERM>(d, K, Kp, k, n, dn, t, live, in, P);
+    // An NLP whose step the Armijo test rejects is tried again at alpha / 2 here and now, while its mates in the wavefront wait
+    // one trial pass: B and F / adjoint then find every live NLP of the wavefront in the same state, and a rejection no longer
+    // costs the wavefront a round.  Accepted NLPs have left ST_TRIAL (their X_CUR has flipped) and
+    // skip the body.  Each pass changes an NLP's state or raises its X_LS, which ends the NLP at 40; 41 passes at the most besides.
+    int pass = 0;
+    do {
+      if (state == ST_TRIAL) {
+        const bool first = sc[X_FIRST] != 0.0;
+        const double alpha = first ? 0.0 : sc[X_ALPHA], adu = first ? 0.0 : sc[X_ADU], mu = sc[X_MU];
+        const Scal s = lds_scal(sc, X_S), ds = lds_scal(sc, X_D);
+        const Scal stt = trial_scal(d, s, ds, alpha, adu, mu, first);
+        const int cur = (int)sc[X_CUR];
+        const double *ic = w + (size_t)(cur * NIT) * Kp, *stp = w + (size_t)R_ST * Kp;
+        double *in = w + (size_t)((1 - cur) * NIT) * Kp;
+        const double dt = hT * stt.th, be = dt * d.alpha;
+        const double mlo = mu * 1e-10, mhi = mu * 1e10;
+        Part P;
+        if (sc[X_TEVAL] != 0.0) {             // evaluated by the adjoint phase of the previous round
+          P.rd = sc[X_P + 0]; P.cinf = sc[X_P + 1]; P.pmin = sc[X_P + 2]; P.pmax = sc[X_P + 3]; P.l1 = sc[X_P + 4];
+          P.zsum = sc[X_P + 5]; P.rth = sc[X_P + 6]; P.c1 = sc[X_P + 7]; P.sl = sc[X_P + 8]; P.mv = sc[X_P + 9];
+        } else {
+          TrialCtx t;
+          t.alpha = alpha; t.adu = adu; t.mlo = mlo; t.mhi = mhi; t.dt = dt; t.be = be; t.hT = hT; t.first = first; t.stt = stt; t.dcw = dcw;
+          P.clear();
+          for (int c = 0; c < nch; c++) {
+            const int k = c * CHN + nl;
+            if (k < K) {
+              NodeIn n, dn;
+              load_node<MP>(ic, Kp, K, k, n, UINIT);
+              if (first) dn = NodeIn{};             // (no step yet; the step rows are not initialised)
+              else load_node<MP>(stp, Kp, K, k, dn);
+              trial_node<SCHEME, FORM, MP, TERM>(d, K, Kp, k, n, dn, t, live, in, P);
+            }
+          }
+          P.template reduceW<MP, WIDE>();
+        }
+        double rd = P.rd, cinf = P.cinf, pmin = P.pmin, pmax = P.pmax, l1 = P.l1, zsum = P.zsum;
+        const double rth = 1.0 + P.rth, c1 = P.c1, sl = P.sl;
+        // ---- decisions (all 16 lanes of the NLP alike; lane 0 writes) -------------------------------------------------
+        double nu_pen = sc[X_NUP], iters = sc[X_ITERS], mu2 = mu;
+        int nstate = ST_FACTOR;
+        bool accepted = true;
+        if (!first) {
+          const double phi0 = sc[X_PHI0], Dm = sc[X_DM];
+          const double phit = (MP ? stt.th + dcw * P.mv : stt.th) - mu * sl + nu_pen * c1;
+          if (!(isfinite(phit) && phit <= phi0 + 1e-8 * alpha * Dm + 2.220446049250313e-15 * fabs(phi0))) {
+            accepted = false;
+            const int ls = (int)sc[X_LS] + 1;
+            wsync();
+            if (role == 0) {
+              sc[X_LS] = ls; sc[X_TEVAL] = 0.0;
+              if (ls >= 40) { sc[X_STATUS] = ASCENT_LINESEARCH_FAILED; sc[X_STATE] = ST_DONE; }
+              else sc[X_ALPHA] = 0.5 * alpha;
+            }
+          } else {
+            iters += 1.0;
           }
         }
-        P.template reduceW<MP, WIDE>();
-      }
-      double rd = P.rd, cinf = P.cinf, pmin = P.pmin, pmax = P.pmax, l1 = P.l1, zsum = P.zsum;
-      const double rth = 1.0 + P.rth, c1 = P.c1, sl = P.sl;
-      // ---- decisions (all 16 lanes of the NLP alike; lane 0 writes) -------------------------------------------------
-      double nu_pen = sc[X_NUP], iters = sc[X_ITERS], mu2 = mu;
-      int nstate = ST_FACTOR;
-      bool accepted = true;
-      if (!first) {
-        const double phi0 = sc[X_PHI0], Dm = sc[X_DM];
-        const double phit = (MP ? stt.th + dcw * P.mv : stt.th) - mu * sl + nu_pen * c1;
-        if (!(isfinite(phit) && phit <= phi0 + 1e-8 * alpha * Dm + 2.220446049250313e-15 * fabs(phi0))) {
-          accepted = false;
-          const int ls = (int)sc[X_LS] + 1;
+        if (accepted) {
+          ErrParts e;
+          e.rd = fmax(rd, fabs(rth - stt.zlt + stt.zut));
+          e.rd = fmax(e.rd, fmax(fabs(-stt.nu1 - stt.zs1), fabs(-stt.nu2 - stt.zs2)));
+          e.cinf = cinf;
+          const double pr[4] = {(stt.th - d.tlb) * stt.zlt, (d.tub - stt.th) * stt.zut, stt.s1 * stt.zs1, stt.s2 * stt.zs2};
+          ASC_UNROLL
+          for (int q = 0; q < 4; q++) { pmin = fmin(pmin, pr[q]); pmax = fmax(pmax, pr[q]); }
+          e.pmin = pmin; e.pmax = pmax;
+          l1 += fabs(stt.nu3) + fabs(stt.nu1) + fabs(stt.nu2);
+          zsum += stt.zlt + stt.zut + stt.zs1 + stt.zs2;
+          e.sd = fmax(100.0, (l1 + zsum) / (double)((MP ? 16 : 13) * K + 7)) * 0.01;
+          int status = -1;
+          const bool probe = sc[X_PROBE] != 0.0;
+          if (probe) { }
+          else if (e.err(0.0) <= tol) { status = ASCENT_CONVERGED; nstate = ST_DONE; }
+          else if ((int)iters >= max_iter) { status = ASCENT_MAX_ITER; nstate = ST_DONE; }
+          else {
+            while (mu2 > tol * 0.1 && e.err(mu2) <= 10.0 * mu2) {
+              mu2 = fmax(tol * 0.1, fmin(0.2 * mu2, mu2 * sqrt(mu2)));
+              nu_pen = 1.0;
+            }
+          }
+#ifdef PERSIST_TRACE      // diagnostic build: the iteration history of one NLP (scripts/persist_trace.py)
+          if (role == 0 && p == PERSIST_TRACE && K > 100)
+            printf("[persist] K=%d iter %2d mu %.1e E0 %.2e (dual %.1e primal %.1e compl %.1e..%.1e s_d %.2g) alpha %.3g adu %.3g ls %d dw %.1e nu_pen %.2g c1 %.2e\n", K, (int)iters, mu,
+                   e.err(0.0), e.rd, e.cinf, e.pmin, e.pmax, e.sd, alpha, adu, (int)sc[X_LS], sc[X_DWL], nu_pen, c1);
+          if (role == 0 && p == PERSIST_TRACE && K > 100)
+            printf("[persist]      dual rows: nodes %.2e | th %.2e s1 %.2e s2 %.2e\n", rd, fabs(rth - stt.zlt + stt.zut), fabs(-stt.nu1 - stt.zs1), fabs(-stt.nu2 - stt.zs2));
+#endif
           wsync();
           if (role == 0) {
-            sc[X_LS] = ls; sc[X_TEVAL] = 0.0;
-            if (ls >= 40) { sc[X_STATUS] = ASCENT_LINESEARCH_FAILED; sc[X_STATE] = ST_DONE; }
-            else sc[X_ALPHA] = 0.5 * alpha;
-          }
-        } else {
-          iters += 1.0;
-        }
-      }
-      if (accepted) {
-        ErrParts e;
-        e.rd = fmax(rd, fabs(rth - stt.zlt + stt.zut));
-        e.rd = fmax(e.rd, fmax(fabs(-stt.nu1 - stt.zs1), fabs(-stt.nu2 - stt.zs2)));
-        e.cinf = cinf;
-        const double pr[4] = {(stt.th - d.tlb) * stt.zlt, (d.tub - stt.th) * stt.zut, stt.s1 * stt.zs1, stt.s2 * stt.zs2};
-        ASC_UNROLL
-        for (int q = 0; q < 4; q++) { pmin = fmin(pmin, pr[q]); pmax = fmax(pmax, pr[q]); }
-        e.pmin = pmin; e.pmax = pmax;
-        l1 += fabs(stt.nu3) + fabs(stt.nu1) + fabs(stt.nu2);
-        zsum += stt.zlt + stt.zut + stt.zs1 + stt.zs2;
-        e.sd = fmax(100.0, (l1 + zsum) / (double)((MP ? 16 : 13) * K + 7)) * 0.01;
-        int status = -1;
-        const bool probe = sc[X_PROBE] != 0.0;
-        if (probe) { }
-        else if (e.err(0.0) <= tol) { status = ASCENT_CONVERGED; nstate = ST_DONE; }
-        else if ((int)iters >= max_iter) { status = ASCENT_MAX_ITER; nstate = ST_DONE; }
-        else {
-          while (mu2 > tol * 0.1 && e.err(mu2) <= 10.0 * mu2) {
-            mu2 = fmax(tol * 0.1, fmin(0.2 * mu2, mu2 * sqrt(mu2)));
-            nu_pen = 1.0;
+            put_scal(sc, X_S, stt);
+            sc[X_CUR] = 1 - cur; sc[X_FIRST] = 0.0; sc[X_ITERS] = iters; sc[X_LS] = 0.0; sc[X_C1] = c1; sc[X_SL] = sl; sc[X_RTH] = rth;
+            sc[X_MU] = mu2; sc[X_NUP] = nu_pen; sc[X_DW] = probe ? sc[X_PDW] : 0.0; sc[X_STATE] = nstate; sc[X_TEVAL] = 0.0;
+            if (MP) sc[X_MV] = P.mv;
+            if (status >= 0) sc[X_STATUS] = status;
           }
         }
-#ifdef PERSIST_TRACE      // diagnostic build: the iteration history of one NLP (scripts/persist_trace.py)
-        if (role == 0 && p == PERSIST_TRACE && K > 100)
-          printf("[persist] K=%d iter %2d mu %.1e E0 %.2e (dual %.1e primal %.1e compl %.1e..%.1e s_d %.2g) alpha %.3g adu %.3g ls %d dw %.1e nu_pen %.2g c1 %.2e\n", K, (int)iters, mu,
-                 e.err(0.0), e.rd, e.cinf, e.pmin, e.pmax, e.sd, alpha, adu, (int)sc[X_LS], sc[X_DWL], nu_pen, c1);
-        if (role == 0 && p == PERSIST_TRACE && K > 100)
-          printf("[persist]      dual rows: nodes %.2e | th %.2e s1 %.2e s2 %.2e\n", rd, fabs(rth - stt.zlt + stt.zut), fabs(-stt.nu1 - stt.zs1), fabs(-stt.nu2 - stt.zs2));
-#endif
-        wsync();
-        if (role == 0) {
-          put_scal(sc, X_S, stt);
-          sc[X_CUR] = 1 - cur; sc[X_FIRST] = 0.0; sc[X_ITERS] = iters; sc[X_LS] = 0.0; sc[X_C1] = c1; sc[X_SL] = sl; sc[X_RTH] = rth;
-          sc[X_MU] = mu2; sc[X_NUP] = nu_pen; sc[X_DW] = probe ? sc[X_PDW] : 0.0; sc[X_STATE] = nstate; sc[X_TEVAL] = 0.0;
-          if (MP) sc[X_MV] = P.mv;
-          if (status >= 0) sc[X_STATUS] = status;
-        }
       }
-    }
-    wsync();
+      wsync();
+      state = (int)sc[X_STATE];
+    } while (__builtin_expect(__any(state == ST_TRIAL) && ++pass < 41, 0));      // (marked rare: spill weights as without the loop, section 4a-lockstep)
     PROF(0);
     // ============================ B: node blocks into LDS + backward factorisation ==================================
     state = (int)sc[X_STATE];
