@@ -4,7 +4,7 @@
 This is this repository's own counterpart of the reference script: the same problem, declared with
 the same modelling calls, solved by libascent on an MI355X instead of GEKKO/APMonitor/IPOPT.  It prints
 the quantities the reference prints (/root/reference/Launch_Optimiser.py:178-194) and writes the same
-three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim] [--disperse] [--guide]
+three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim] [--disperse] [--guide [--feedforward]]
 --fly also integrates the ODEs under the control just found (RK4 on the device) and prints where that flight ends.
 --trim corrects (t_f, u) so that the flown control reaches the target orbit (trim_batch) and prints t_f and the flown apsides
 before and after.
@@ -12,6 +12,8 @@ before and after.
 step (disperse_batch) and prints the Monte Carlo and the linear 1-sigma of the flown apsides side by side.
 --guide trims, computes the neighbouring-optimal feedback gains (guidance_gains) and flies the same 1024 dispersed samples open loop
 and under that feedback; prints both 1-sigmas of the flown apsides and the control authority the feedback took.
+--guide --feedforward adds, from the same draws, the thrust feed-forward (guidance_gains(feedforward="Ft")) with the thrust known
+exactly, and with the thrust known to 10 N (1-sigma) under a navigation bias of NAV_BIAS (1-sigma, scaled units).
 """
 import argparse
 import os
@@ -29,6 +31,9 @@ VEHICLE = dict(Ft=15346.0, M0=4821.0, M_dot=5.053, fuel=2376.0, ang_acc_max=5e-4
 ORBIT = dict(periapsis=17703.0, apoapsis=88615.0)
 BURN_LIMIT = 470.0          # s, fuel-limited maximum burn: time scale of the free final time
 NT = 200
+# --guide --feedforward: 1-sigma bias of each sample's state knowledge, scaled units (x, y, vx, vy, angle, angle rate, mass);
+# a position unit is the insertion altitude, 17703 m, a velocity unit 17703 m/s: 17.7 m and 1.8 cm/s
+NAV_BIAS = (1e-3, 1e-3, 1e-6, 1e-6, 0.0, 0.0, 0.0)
 
 
 def build(nt=NT, solver=None):
@@ -145,7 +150,7 @@ def disperse(m, scheme, samples=1024):
     return d
 
 
-def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0):
+def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=False):
     """The trimmed solution under the same dispersions, open loop and steering back to the nominal with a cutoff on the state.
     The cutoff channel stretches the last step only, T / K = 2.2 s here: 50 N of 15 kN over a 435 s burn is 1.4 s (1-sigma) of burn
     time, so the stretch is allowed +-2 steps; at stretch_max = 0.5 it sits on its bound for most samples."""
@@ -168,6 +173,19 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0):
     e = cl.effort[0]
     print("control authority: a command clipped on %.2f steps per flight, largest |K.dz| %.3g, cutoff stretch 1-sigma %.3g (largest %.3g of %g)"
           % (e[:, 0].mean(), np.nanmax(e[:, 1]), np.nanstd(e[:, 2]), np.nanmax(np.abs(e[:, 2])), stretch_max))
+    if feedforward:
+        # the same draws with the feed-forward: the feedback gains are the same bits, the samples now plan with their own thrust
+        gf = guidance_gains(res.params, t.blob, res.nt, cond_weights=(weight,) * 3, control_weight=1.0, cutoff_weight=1.0, stretch_max=stretch_max,
+                            feedforward="Ft", **kw)
+        known = disperse_batch(res.params, t.blob, res.nt, guidance=gf, keep_samples=True, **dkw)
+        nav = disperse_batch(res.params, t.blob, res.nt, guidance=gf, keep_samples=True, knowledge_sigma=10.0, nav_sigma=NAV_BIAS, **dkw)
+        lin = np.sqrt(np.diagonal(nav.linear_covariance(gf.jacobian, gf.jacobian_nav)[0]))
+        print("feed-forward: largest |f_k| %.4g per N, |f_t| %.4g per N" % (gf.max_feedforward[0], gf.max_cutoff_feedforward[0]))
+        print("flown altitude 1-sigma (m)   open loop   feedback only   + feed-forward, thrust known   + known to 10 N, navigation bias (linear)")
+        for name, q in (("periapsis", 7), ("apoapsis", 8)):
+            print("%-24s %13.1f %15.2f %30.2f %25.2f (%.2f)" % (name, op.std[0, q], cl.std[0, q], known.std[0, q], nav.std[0, q], lin[q]))
+        print("commands clipped per flight: feedback only %.2f, thrust known %.2f, 10 N and navigation bias %.2f"
+              % (e[:, 0].mean(), known.effort[0, :, 0].mean(), nav.effort[0, :, 0].mean()))
     return op, cl, g
 
 
@@ -208,6 +226,7 @@ if __name__ == "__main__":
     ap.add_argument("--trim", action="store_true", help="trim t_f and the control so that the flown trajectory reaches its orbit; prints before / after")
     ap.add_argument("--disperse", action="store_true", help="trim, then fly the trimmed control under 50 N of thrust and 1e-3 of control error 1024 times; prints Monte Carlo and linear 1-sigma of the flown apsides")
     ap.add_argument("--guide", action="store_true", help="trim, compute LQ feedback gains and fly 1024 dispersed samples open loop and closed loop; prints both 1-sigmas of the flown apsides")
+    ap.add_argument("--feedforward", action="store_true", help="with --guide: also fly the same draws with the thrust feed-forward, once with the thrust known exactly and once known to 10 N (1-sigma) under a navigation bias of 1-sigma %g (scaled; %.1f m) on both positions and %g (scaled; %.1f cm/s) on both velocities" % (NAV_BIAS[0], NAV_BIAS[0] * ORBIT["periapsis"], NAV_BIAS[2], NAV_BIAS[2] * ORBIT["periapsis"] * 100))
     a = ap.parse_args()
     model, variables, v_ins = build()
     if a.no_dcost:
@@ -223,6 +242,6 @@ if __name__ == "__main__":
     if a.disperse:
         disperse(model, a.scheme)
     if a.guide:
-        guide(model, a.scheme)
+        guide(model, a.scheme, feedforward=a.feedforward)
     if not a.no_plots:
         plots(model, variables, a.outdir)

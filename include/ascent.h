@@ -440,6 +440,67 @@ int ascent_disperse_guided_batch(const ascent_params *p, int64_t batch, const as
                                  const double *stretch_max_or_null, double *stats_out, double *samples_out_or_null,
                                  int device_id, void *hip_stream_or_null, int ptr_is_device);
 
+/* Guidance gains with a parameter feed-forward: ascent_guidance_gains for a vehicle that knows (an estimate of) one of its own
+ * parameter deviations -- its thrust, from an accelerometer -- and plans the rest of the burn with it.
+ * ff_dir [16][batch]: a direction d in the space of the 16 ascent_params fields (SI, declaration order), per problem.  The
+ *   parameter deviation is theta * d with a constant scalar theta in the units d implies (d = e_Ft: newtons of thrust).
+ * Dynamics: dz_k = Phi_k dz_{k-1} + g_k du_k + pi_k theta + [k = K] gamma_K tau, pi_k = Gamma_k d: the step's derivative with
+ *   respect to the fields (blob fixed in scaled units, as ascent_flight_jacobian) along d.  The "direct" dependence of the
+ *   apsides on G, M, R0 and r_peri is not part of pi_k.  Cost, weights, columns and the 0.999 / stretch_max rules: unchanged.  The
+ *   target stays the nominal flown end conditions linearised in z; a direction that moves the conditions themselves (G, M, R0,
+ *   r_peri, r_apo) is accepted and treated the same way, and is then not the neighbouring optimum of the orbit target.
+ * Recursion: the value function 1/2 [dz; theta]' [[P, p], [p', pi0]] [dz; theta], p_K = 0.  P, S and G are ascent_guidance_gains'
+ *   (certainty equivalence).  Per step, a = P_k pi_k + p_k: f = S^-1 B' a, p_{k-1} = Phi_k' a - G' S f; without a column f = 0 and
+ *   p_{k-1} = Phi_k' a.  pi0 is not computed.
+ * Law: du_k = -K_k . dz - f_k theta-hat, tau = -k_t . dz - f_t theta-hat, theta-hat what the vehicle believes theta is.
+ * gain_u_out, gain_t_out and summary rows 0..4 are the bits of ascent_guidance_gains for the same inputs, whatever ff_dir holds.
+ * ff_u_out [K][batch]: f_k (exactly 0 for a saturated control);  ff_t_out [batch]: f_t (0 where stretch_max = 0).
+ * summary_out [ASCENT_GUIDE_FF_ROWS][batch]: rows 0..4 as ascent_guidance_gains, 5 max_k |f_k|, 6 |f_t|.
+ * ff_know_or_null [16][batch]: a row w with theta-hat = w . dp, dp the vehicle's 16 SI parameter deviations (for d = e_Ft and a
+ *   thrust known exactly, w = e_Ft).  Needed by the closed-loop Jacobian only.
+ * jac_cl_out_or_null, jac_u_cl_out_or_null: as ascent_guidance_gains, of the closed loop under the law above with theta-hat =
+ *   w . dp: every parameter column c is ascent_guidance_gains' minus E w_c, E = sum_k (Lambda_k g_k) f_k + (Lambda_K gamma_K) f_t.
+ * jac_nav_out_or_null [9][ASCENT_NAV_ROWS][batch] (only with jac_cl_out): the derivative of the nine rows with respect to
+ *   columns 0..6, a bias nu of the vehicle's state knowledge (it steers on dz + nu; scaled units):
+ *   -sum_k (Lambda_k g_k) K_k' - (Lambda_K gamma_K) k_t';  column 7, an error of theta-hat: -E.
+ *   Row 8 is NaN where the flown energy is >= 0, as everywhere.
+ * With ff_dir = 0: ff_u, ff_t and column 7 of jac_nav are zero and jac_cl, jac_u_cl are ascent_guidance_gains' bits.
+ * A non-finite entry of ff_dir or ff_know freezes the problem like a bad weight: status 2, NaN gains, feed-forward and Jacobians.
+ * Refuses what ascent_guidance_gains refuses, a null ff_dir, ff_u_out or ff_t_out, jac_nav_out without jac_cl_out, and jac_cl_out
+ * without ff_know.  Everything else as ascent_guidance_gains; with device pointers and a stream the call only enqueues two
+ * kernels (f_fly, g_gains_ff). */
+#define ASCENT_NAV_ROWS 8            /* 7 state-knowledge biases (scaled units), 1 error of theta-hat */
+#define ASCENT_GUIDE_FF_ROWS 7       /* ASCENT_GUIDE_ROWS, then 5 max_k |f_k|, 6 |f_t| */
+int ascent_guidance_feedforward(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                                int32_t substeps, const double *weights, const double *ff_dir, const double *ff_know_or_null,
+                                double *gain_u_out, double *gain_t_out, double *ff_u_out, double *ff_t_out, double *summary_out,
+                                double *jac_cl_out_or_null, double *jac_u_cl_out_or_null, double *jac_nav_out_or_null,
+                                int device_id, void *hip_stream_or_null, int ptr_is_device);
+
+/* Guided Monte Carlo dispersion with a feed-forward and navigation errors: ascent_disperse_guided_batch where no sample knows
+ * its state perfectly and every sample has a belief theta-hat about its parameter deviation.  Sample s of problem b:
+ *   nu_i = sigma_nav[i][b] * xi_nav[i][s] where that sigma is non-zero, else 0 (i = 0..6; scaled units);
+ *   theta-hat = sum_i ff_know[i][b] * (the applied deviation of field i: sigma[7+i][b] * xi[7+i][s] where that sigma is non-zero,
+ *   else 0; formed as (ff_know * sigma) * xi) + sigma_nav[7][b] * xi_nav[7][s] where that sigma is non-zero; 0 where ff_know is
+ *   null and sigma_nav[7][b] = 0.
+ * At step k: dz_i = z_i - z_i^nominal as ascent_disperse_guided_batch, then dz_i += nu_i only where nu_i is applied.  Where the
+ *   gain row of the step is all zero and f_k = 0 the command is u_k itself, bit for bit; otherwise w = u_k - K_k . dz, then
+ *   w -= f_k * theta-hat only where f_k != 0, and the command is clip(w, -1, 1), NaN where K_k . dz + f_k theta-hat is not finite.
+ *   Execution error and stretch as ascent_disperse_guided_batch with dtau = -k_t . dz, then - f_t * theta-hat where f_t != 0.
+ * samples_out row 10 is max_k |K_k . dz + f_k theta-hat|.  The 12 sample rows, the held m, the validity rule, the 82-row
+ *   reduction and its fixed order: ascent_disperse_guided_batch's.
+ * ff_u_or_null [K][batch], ff_t_or_null [batch], ff_know_or_null [16][batch] (only with ff_u), xi_nav_or_null
+ *   [ASCENT_NAV_ROWS][samples], sample fastest, and sigma_nav_or_null [ASCENT_NAV_ROWS][batch] (both or neither).
+ * With the five all null, or all given and zero, the call gives ascent_disperse_guided_batch's bits.
+ * Refuses what ascent_disperse_guided_batch refuses, xi_nav without sigma_nav or the reverse, and ff_know without ff_u. */
+int ascent_disperse_navigated_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                                    int32_t substeps, int32_t samples, const double *xi, const double *sigma,
+                                    const double *sigma_u_or_null, const double *gain_u, const double *gain_t_or_null,
+                                    const double *stretch_max_or_null, const double *ff_u_or_null, const double *ff_t_or_null,
+                                    const double *ff_know_or_null, const double *xi_nav_or_null, const double *sigma_nav_or_null,
+                                    double *stats_out, double *samples_out_or_null, int device_id, void *hip_stream_or_null,
+                                    int ptr_is_device);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

@@ -34,7 +34,8 @@ SYMBOLS = ("ascent_version", "ascent_device_count", "ascent_strerror", "ascent_s
            "ascent_eval_nodes", "ascent_kkt_step", "ascent_eval_nodes_path", "ascent_kkt_step_path",
            "ascent_dense_records", "ascent_coast_batch", "ascent_kkt_solve", "ascent_last_kernel_ms", "ascent_default_path",
            "ascent_workspace_layout", "ascent_param_sensitivity", "ascent_fly_batch", "ascent_flight_jacobian",
-           "ascent_trim_batch", "ascent_disperse_batch", "ascent_guidance_gains", "ascent_disperse_guided_batch")
+           "ascent_trim_batch", "ascent_disperse_batch", "ascent_guidance_gains", "ascent_disperse_guided_batch",
+           "ascent_guidance_feedforward", "ascent_disperse_navigated_batch")
 PATHS = {"auto": 0, "fused": 1, "split_lane": 2, "split_wide": 3, "dense": 4, "persist": 5}     # enum ascent_path
 
 _lib = None
@@ -159,6 +160,12 @@ def load():
     L.ascent_disperse_guided_batch.restype = C.c_int
     L.ascent_disperse_guided_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(AscentOptsC), C.c_void_p, C.c_int32, C.c_int32] + [
         C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_int]
+    L.ascent_guidance_feedforward.restype = C.c_int
+    L.ascent_guidance_feedforward.argtypes = [C.c_void_p, C.c_int64, C.POINTER(AscentOptsC), C.c_void_p, C.c_int32] + [C.c_void_p] * 11 + [
+        C.c_int, C.c_void_p, C.c_int]
+    L.ascent_disperse_navigated_batch.restype = C.c_int
+    L.ascent_disperse_navigated_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(AscentOptsC), C.c_void_p, C.c_int32, C.c_int32] + [
+        C.c_void_p] * 13 + [C.c_int, C.c_void_p, C.c_int]
     _lib = L
     return L
 

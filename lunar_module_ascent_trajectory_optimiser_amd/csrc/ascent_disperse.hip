@@ -17,6 +17,8 @@
 //          wave, wave 0..3 through LDS in that order -- into one partial record per workgroup.
 // f_disperse_stats  one lane per problem, problem-fastest: the partial records added in ascending chunk order, then the 82 rows.
 // f_disperse_guided f_disperse under state feedback (ascent_disperse_guided_batch): same mapping, same record, same reduction.
+// f_disperse_navigated  f_disperse_guided with the feed-forward f_k theta-hat and the navigation errors of
+//          ascent_disperse_navigated_batch: one body with f_disperse_guided (guided_body<FORM, NAV>).
 // The order of every addition is fixed by `samples` alone: a problem gives the same bits alone as inside any batch.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -179,14 +181,21 @@ __global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict
 // more, wave-uniform, loaded for the next step with its u before the current one is integrated.  The command of a step whose
 // gain row is all zero is u_k itself, and without a stretch hs is f_disperse's: such a flight has f_disperse's bits.  A
 // non-finite K.dz makes the command NaN, so the sample is invalid (a clip would hide it).
-template <int FORM>
-__global__ __launch_bounds__(DB) void f_disperse_guided(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
-                                                        int nwg, long g0, const double *__restrict__ blob,
-                                                        const double *__restrict__ traj, const double *__restrict__ fsum,
-                                                        const double *__restrict__ xi, const double *__restrict__ sigma,
-                                                        const double *__restrict__ sigma_u, const double *__restrict__ gain_u,
-                                                        const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
-                                                        double *__restrict__ partial, double *__restrict__ samples_out) {
+// NAV (f_disperse_navigated; include/ascent.h: ascent_disperse_navigated_batch): per step one more wave-uniform double, f_k, loaded
+// with the next step's gains, and per sample eight more draws loaded once: the navigation bias nu added to dz where its sigma is
+// not zero, and theta-hat, what the sample believes its parameter deviation is.  Each addition is skipped where its factor is
+// zero, so with nothing new given, or all of it zero, a flight has f_disperse_guided's bits.  NAV = false: f_disperse_guided, the
+// new arguments all null and no trace of them in the code.
+template <int FORM, bool NAV>
+ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
+                         int nwg, long g0, const double *__restrict__ blob,
+                         const double *__restrict__ traj, const double *__restrict__ fsum,
+                         const double *__restrict__ xi, const double *__restrict__ sigma,
+                         const double *__restrict__ sigma_u, const double *__restrict__ gain_u,
+                         const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
+                         const double *__restrict__ ff_u, const double *__restrict__ ff_t, const double *__restrict__ ff_know,
+                         const double *__restrict__ xi_nav, const double *__restrict__ sigma_nav,
+                         double *__restrict__ partial, double *__restrict__ samples_out) {
   __shared__ double red[DNW][NREC];
   const long g = g0 + blockIdx.x;
   const long p = g / nwg;
@@ -231,6 +240,29 @@ __global__ __launch_bounds__(DB) void f_disperse_guided(const ascent_params *__r
     load_node(tr, B, nt, 0, zn);
     ASC_UNROLL
     for (int i = 0; i < 7; i++) kn[i] = gu[(size_t)i * K * B];
+    // the navigation bias (applied where its sigma is not zero) and theta-hat = w . (applied field deviations) + the knowledge error
+    double nu[7], th = 0.0, fn = 0.0;
+    bool nav[7];
+    if constexpr (NAV) {
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) {
+        const double sn = sigma_nav ? sigma_nav[(size_t)i * B + p] : 0.0;
+        nav[i] = sn != 0.0;
+        nu[i] = nav[i] ? sn * xi_nav[(size_t)i * NS + s] : 0.0;
+      }
+      if (ff_know) {
+        // (w sigma) xi, not w (sigma xi): a product sigma xi shared with the field's own perturbation above would keep that one
+        // from being fused into its addition, and the sample's parameters would lose f_disperse_guided's bits
+        ASC_UNROLL
+        for (int i = 0; i < 16; i++) {
+          const double ws = ff_know[(size_t)i * B + p] * sg[7 + i];
+          th += sg[7 + i] != 0.0 ? ws * xv[7 + i] : 0.0;
+        }
+      }
+      const double s7 = sigma_nav ? sigma_nav[(size_t)7 * B + p] : 0.0;
+      if (s7 != 0.0) th += s7 * xi_nav[(size_t)7 * NS + s];
+      fn = ff_u ? ff_u[p] : 0.0;
+    }
     double nclip = 0.0, dmax = 0.0, stretch = 0.0;
     for (int k = 0; k < K; k++) {
       // the command of this step from the state it starts at
@@ -239,12 +271,21 @@ __global__ __launch_bounds__(DB) void f_disperse_guided(const ascent_params *__r
       ASC_UNROLL
       for (int i = 0; i < 7; i++) {
         dz[i] = z[i] - zn[i];
+        if constexpr (NAV) dz[i] = nav[i] ? dz[i] + nu[i] : dz[i];
         dot += kn[i] * dz[i];
         zero = zero && kn[i] == 0.0;
       }
       double uc = un;
+      if constexpr (NAV) zero = zero && fn == 0.0;
       if (!zero) {
-        const double w = un - dot;
+        double w = un - dot;
+        if constexpr (NAV) {
+          if (fn != 0.0) {
+            const double ft = fn * th;
+            w -= ft;
+            dot += ft;                        // the whole correction K.dz + f theta-hat
+          }
+        }
         uc = finite1(dot) ? fmin(1.0, fmax(-1.0, w)) : NAN;
         nclip += uc != w ? 1.0 : 0.0;
         dmax = (dot != dot || dmax != dmax) ? NAN : fmax(dmax, fabs(dot));
@@ -255,6 +296,10 @@ __global__ __launch_bounds__(DB) void f_disperse_guided(const ascent_params *__r
         double dtau = 0.0;
         ASC_UNROLL
         for (int i = 0; i < 7; i++) dtau -= gain_t[(size_t)i * B + p] * dz[i];
+        if constexpr (NAV) {
+          const double f2 = ff_t ? ff_t[p] : 0.0;
+          if (f2 != 0.0) dtau -= f2 * th;
+        }
         stretch = finite1(dtau) ? fmin(smax, fmax(-smax, dtau)) : NAN;
         h = (dt * (1.0 + stretch)) / m;
       }
@@ -263,6 +308,7 @@ __global__ __launch_bounds__(DB) void f_disperse_guided(const ascent_params *__r
       load_node(tr, B, nt, kq, zn);
       ASC_UNROLL
       for (int i = 0; i < 7; i++) kn[i] = gu[((size_t)i * K + kq) * B];
+      if constexpr (NAV) fn = ff_u ? ff_u[(size_t)kq * B + p] : 0.0;
       fly_step<FORM>(d, z, u, h, m);
     }
     ASC_UNROLL
@@ -290,6 +336,32 @@ __global__ __launch_bounds__(DB) void f_disperse_guided(const ascent_params *__r
     }
     partial[((size_t)c * NREC + i) * B + p] = a;
   }
+}
+
+template <int FORM>
+__global__ __launch_bounds__(DB) void f_disperse_guided(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
+                                                        int nwg, long g0, const double *__restrict__ blob,
+                                                        const double *__restrict__ traj, const double *__restrict__ fsum,
+                                                        const double *__restrict__ xi, const double *__restrict__ sigma,
+                                                        const double *__restrict__ sigma_u, const double *__restrict__ gain_u,
+                                                        const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
+                                                        double *__restrict__ partial, double *__restrict__ samples_out) {
+  guided_body<FORM, false>(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, xi, sigma, sigma_u, gain_u, gain_t, stretch_max,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, partial, samples_out);
+}
+
+struct NavArgs { const double *ff_u, *ff_t, *ff_know, *xi_nav, *sigma_nav; };
+
+template <int FORM>
+__global__ __launch_bounds__(DB) void f_disperse_navigated(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
+                                                           int nwg, long g0, const double *__restrict__ blob,
+                                                           const double *__restrict__ traj, const double *__restrict__ fsum,
+                                                           const double *__restrict__ xi, const double *__restrict__ sigma,
+                                                           const double *__restrict__ sigma_u, const double *__restrict__ gain_u,
+                                                           const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
+                                                           NavArgs nav, double *__restrict__ partial, double *__restrict__ samples_out) {
+  guided_body<FORM, true>(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, xi, sigma, sigma_u, gain_u, gain_t, stretch_max,
+                          nav.ff_u, nav.ff_t, nav.ff_know, nav.xi_nav, nav.sigma_nav, partial, samples_out);
 }
 
 __global__ __launch_bounds__(SW) void f_disperse_stats(long batch, int K, int nwg, const double *__restrict__ traj,
@@ -388,6 +460,31 @@ int disperse_guided_run(const Call &c, int substeps, int samples, const double *
     else
       hipLaunchKernelGGL((f_disperse_guided<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
                          w.fsum, dxi, dsigma, dsigma_u, dgain_u, dgain_t, dsmax, w.partial, dsamples);
+    ASC_CHK(c.err, c.errlen, hipGetLastError());
+  }
+  const dim3 gst((unsigned)((c.batch + SW - 1) / SW)), bst(SW);
+  hipLaunchKernelGGL(f_disperse_stats, gst, bst, 0, c.stream, c.batch, c.K, nwg, w.traj, w.fsum, w.partial, dstats);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
+  return ASCENT_OK;
+}
+
+int disperse_navigated_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
+                           const double *dsigma_u, const double *dgain_u, const double *dgain_t, const double *dsmax,
+                           const double *dff_u, const double *dff_t, const double *dff_know, const double *dxi_nav,
+                           const double *dsigma_nav, double *dstats, double *dsamples, double *ws) {
+  const DisperseWs w = carve(ws, c.K, c.batch);
+  if (const int rc = flight_fly_only(c, substeps, dblob, w.traj, w.fsum)) return rc;
+  const int nwg = groups_per_problem(samples);
+  const long total = c.batch * nwg;
+  const NavArgs nav = {dff_u, dff_t, dff_know, dxi_nav, dsigma_nav};
+  for (long g0 = 0; g0 < total; g0 += MAX_GRID) {
+    const dim3 grid((unsigned)(total - g0 < MAX_GRID ? total - g0 : MAX_GRID)), block(threads_per_group(samples));
+    if (c.form == 1)
+      hipLaunchKernelGGL((f_disperse_navigated<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
+                         w.fsum, dxi, dsigma, dsigma_u, dgain_u, dgain_t, dsmax, nav, w.partial, dsamples);
+    else
+      hipLaunchKernelGGL((f_disperse_navigated<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
+                         w.fsum, dxi, dsigma, dsigma_u, dgain_u, dgain_t, dsmax, nav, w.partial, dsamples);
     ASC_CHK(c.err, c.errlen, hipGetLastError());
   }
   const dim3 gst((unsigned)((c.batch + SW - 1) / SW)), bst(SW);

@@ -25,4 +25,12 @@ int disperse_guided_run(const Call &c, int substeps, int samples, const double *
                         const double *dsigma_u, const double *dgain_u, const double *dgain_t, const double *dsmax, double *dstats,
                         double *dsamples, double *ws);
 
+// include/ascent.h: ascent_disperse_navigated_batch.  As disperse_guided_run, plus dff_u [K][batch], dff_t [batch], dff_know
+// [16][batch], dxi_nav [ASCENT_NAV_ROWS][samples], dsigma_nav [ASCENT_NAV_ROWS][batch], each or null.  Same workspace, same three
+// enqueues with f_disperse_navigated in f_disperse_guided's place.
+int disperse_navigated_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
+                           const double *dsigma_u, const double *dgain_u, const double *dgain_t, const double *dsmax,
+                           const double *dff_u, const double *dff_t, const double *dff_know, const double *dxi_nav,
+                           const double *dsigma_nav, double *dstats, double *dsamples, double *ws);
+
 }  // namespace ascent

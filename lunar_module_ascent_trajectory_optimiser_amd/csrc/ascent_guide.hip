@@ -18,6 +18,20 @@
 //          The phases of one wavefront are ordered by LDS's in-order execution; wave_sync keeps the compiler from reordering them.
 //   epilogue   j_jac's chain rule, restated here (j_jac itself is left as it is: the trim depends on its bits).
 // The order of every addition is fixed: a problem gives the same bits alone as inside any batch.
+//
+// g_gains_ff  the same sweep with a thrust (parameter) feed-forward (include/ascent.h: ascent_guidance_feedforward): one body,
+//          gains_body<FORM, FF>, so the P-part above is one source text and its gains are g_gains' bits.  The deviation state is
+//          augmented by one constant scalar theta along the caller's direction d of the 16 fields: step forcing pi_k = Gamma_k d
+//          through the epilogue's chain rule (eight wave-uniform coefficients), formed by every group from its own tangent
+//          columns when the records are staged -- a butterfly over the 16 lanes of the group --, 7 doubles per step in LDS.
+//          The value function gains the column p (7 doubles in LDS); per step, beside the phases above:
+//   A      lanes 49..55 also: a = P pi + p, a second chain inside the loop that forms P g
+//   B      every lane: hf = B' a, column pj of a' Phi -- three more chains in the loop that forms S -- and f = S^-1 hf by the
+//          same closed forms as G; lane 0 stores f_k (f_t on the last step); lanes 49..55 store p <- Phi' a - G' S f
+//   C      lane q < 9: E_q += (Lambda g) f_k + (Lambda gamma) f_t and the seven navigation columns += (Lambda g) K_k +
+//          (Lambda gamma) k_t, eight more accumulators per row
+//   epilogue   parameter column c -= E_q w_c (w: the knowledge row), jac_nav = -[navigation columns | E_q].
+//          pi0 (the scalar of the value function) is not carried: no output depends on it.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cmath>
@@ -46,14 +60,20 @@ ASC_DEV void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int FORM>
-__global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ P, long batch, int K, int substeps,
-                                              const double *__restrict__ blob, const double *__restrict__ traj,
-                                              const double *__restrict__ weights, double *__restrict__ gain_u,
-                                              double *__restrict__ gain_t, double *__restrict__ summary,
-                                              double *__restrict__ jac, double *__restrict__ jac_u) {
+constexpr int NNAV = ASCENT_NAV_ROWS;
+
+// FF = false: g_gains, and no trace of the feed-forward arguments (all null) in the code
+template <int FORM, bool FF>
+ASC_DEV void gains_body(const ascent_params *__restrict__ P, long batch, int K, int substeps,
+                        const double *__restrict__ blob, const double *__restrict__ traj,
+                        const double *__restrict__ weights, double *__restrict__ gain_u,
+                        double *__restrict__ gain_t, double *__restrict__ summary,
+                        double *__restrict__ jac, double *__restrict__ jac_u, const double *__restrict__ ff_dir,
+                        const double *__restrict__ ff_know, double *__restrict__ ff_u, double *__restrict__ ff_t,
+                        double *__restrict__ jac_nav) {
   __shared__ double rec[CH * REC];
   __shared__ double Ps[49], Ms[49], Ws[14], Gs[14], Ls[JROWS * 7], As[JROWS * NACC];
+  __shared__ double pis[FF ? CH * 7 : 1], pv[FF ? 7 : 1], av[FF ? 7 : 1], Ns[FF ? JROWS * NNAV : 1];      // pi_k, p, a, nav accumulators
   __shared__ int frozen_s;
   const long p = blockIdx.x;
   const size_t B = (size_t)batch;
@@ -69,7 +89,31 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
   const double ru = weights[(size_t)W_RU * B + p], rt = weights[(size_t)W_RT * B + p], smax = weights[(size_t)W_SMAX * B + p];
   const int pi = t < 49 ? t / 7 : 0, pj = t % 7;      // lane (pi, pj) of P; every lane: column pj of a gain row
 
-  double dirG = 0.0, dirM = 0.0, dirR0 = 0.0, dirS = 0.0, nf = 0.0, gmax = 0.0, tmax = 0.0;
+  // pi_k = R[:, C_DT .. C_MRATE] . coef: the epilogue's chain rule applied to the direction; this lane's coefficient
+  double cf = 0.0;
+  bool dok = true;
+  if constexpr (FF) {
+    double dd[16], coef[NACC];
+    ASC_UNROLL
+    for (int i = 0; i < 16; i++) { dd[i] = ff_dir[(size_t)i * B + p]; dok = dok && finite1(dd[i]); }
+    if (ff_know) {
+      ASC_UNROLL
+      for (int i = 0; i < 16; i++) dok = dok && finite1(ff_know[(size_t)i * B + p]);
+    }
+    const double S = prm.r_peri, S3 = S * S * S;
+    coef[0] = dd[11] * (tf / K);
+    coef[1 + ACC_RHO0] = dd[2] / S - dd[9] * prm.R0 / (S * S);
+    coef[1 + ACC_GAM] = dd[0] * prm.M / S3 + dd[1] * prm.G / S3 - dd[9] * 3.0 * d.gam / S;
+    coef[1 + ACC_THR] = dd[3] / S - dd[9] * d.thr / S;
+    coef[1 + ACC_M0] = dd[4];
+    coef[1 + ACC_MS] = dd[7];
+    coef[C_ALPHA - C_DT] = FORM == 1 ? dd[12] : dd[8] / 3.0;
+    coef[C_MRATE - C_DT] = dd[5] / prm.fuel_mass - dd[6] * d.mrate / prm.fuel_mass;
+    ASC_UNROLL
+    for (int a = 0; a < NACC; a++) cf = col == C_DT + a ? coef[a] : cf;
+  }
+
+  double dirG = 0.0, dirM = 0.0, dirR0 = 0.0, dirS = 0.0, nf = 0.0, gmax = 0.0, tmax = 0.0, fmax_u = 0.0, fmax_t = 0.0;
   if (t < GW) {
     double zK[7], gp[5], ga[5], q[3];
     load_node(tr, B, nt, K, zK);
@@ -77,7 +121,7 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
     for (int i = 0; i < 3; i++) q[i] = weights[(size_t)(W_QE3 + i) * B + p];
     const bool wok = q[0] >= 0.0 && q[1] >= 0.0 && q[2] >= 0.0 && ru > 0.0 && rt > 0.0 && smax >= 0.0 && finite1(q[0]) &&
                      finite1(q[1]) && finite1(q[2]) && finite1(ru) && finite1(rt) && finite1(smax);
-    if (t == 0) frozen_s = wok ? 0 : 1;
+    if (t == 0) frozen_s = wok && dok ? 0 : 1;
     // P_K = sum_i q_i c_i c_i'
     const Terminal tm = terminal_eval(d, zK);
     const double cg[3][7] = {{tm.e3g[0], tm.e3g[1], tm.e3g[2], tm.e3g[3], 0.0, 0.0, 0.0},
@@ -93,6 +137,9 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
         a += q[i] * (ci * cj);
       }
       Ps[t] = a;
+    }
+    if constexpr (FF) {
+      if (t < 7) pv[t] = 0.0;
     }
     // Lambda_K = I / grad apsides, as j_jac
     if (jac) {
@@ -114,6 +161,10 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
         for (int i = 0; i < 7; i++) Ls[t * 7 + i] = L[i];
         ASC_UNROLL
         for (int a = 0; a < NACC; a++) As[t * NACC + a] = 0.0;
+        if constexpr (FF) {
+          ASC_UNROLL
+          for (int a = 0; a < NNAV; a++) Ns[t * NNAV + a] = 0.0;
+        }
       }
     }
     for (int k = t; k < K; k += GW) nf += fabs(b[(size_t)(7 * K + k) * B]) < 0.999 ? 1.0 : 0.0;
@@ -134,6 +185,15 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
       fly_step_tangent<FORM>(d, z, dz, u, hs, m, col);
       ASC_UNROLL
       for (int i = 0; i < 7; i++) rec[g * REC + i * NCOL + col] = dz[i];
+      if constexpr (FF) {                     // pi of this step: the group's parameter columns times their coefficients, summed over the group
+        ASC_UNROLL
+        for (int i = 0; i < 7; i++) {
+          double v = col >= C_DT ? dz[i] * cf : 0.0;
+          ASC_UNROLL
+          for (int off = 8; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+          if (col == 0) pis[g * 7 + i] = v;
+        }
+      }
     }
     __syncthreads();
     if (t < GW) {
@@ -153,10 +213,17 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
         } else if (t < 63) {
           const int cc = t < 56 ? C_U : C_DT;
           const double sc = t < 56 ? 1.0 : dt;
-          double a = 0.0;
+          double a = 0.0, e = 0.0;
+          if constexpr (FF) e = pv[pj];
           ASC_UNROLL
-          for (int l = 0; l < 7; l++) a += Ps[pj * 7 + l] * (sc * R[l * NCOL + cc]);
+          for (int l = 0; l < 7; l++) {
+            a += Ps[pj * 7 + l] * (sc * R[l * NCOL + cc]);
+            if constexpr (FF) e += Ps[pj * 7 + l] * pis[s * 7 + l];      // a second chain beside the first, in all 14 lanes: no branch of its own
+          }
           Ws[t - 49] = a;
+          if constexpr (FF) {
+            if (t < 56) av[pj] = e;
+          }
         }
         wave_sync();
         // B
@@ -170,24 +237,49 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
           h1 += Ws[l] * R[l * NCOL + pj];
           h2 += Ws[7 + l] * R[l * NCOL + pj];
         }
-        double g1 = 0.0, g2 = 0.0;
+        double e1 = 0.0, e2 = 0.0, ep = 0.0;  // B' a, and column pj of a' Phi
+        if constexpr (FF) {
+          ASC_UNROLL
+          for (int l = 0; l < 7; l++) {
+            e1 += R[l * NCOL + C_U] * av[l];
+            e2 += (dt * R[l * NCOL + C_DT]) * av[l];
+            ep += R[l * NCOL + pj] * av[l];
+          }
+        }
+        double g1 = 0.0, g2 = 0.0, fu = 0.0, ft = 0.0;
         if (f1 && f2) {
           const double det = s11 * s22 - s12 * s12;
           ok = finite1(s11) && finite1(s12) && finite1(s22) && s11 > 0.0 && s22 > 0.0 && det > 0.0;
           g1 = (s22 * h1 - s12 * h2) / det;
           g2 = (s11 * h2 - s12 * h1) / det;
+          if constexpr (FF) {
+            fu = (s22 * e1 - s12 * e2) / det;
+            ft = (s11 * e2 - s12 * e1) / det;
+          }
         } else if (f1) {
           ok = finite1(s11) && s11 > 0.0;
           g1 = h1 / s11;
+          if constexpr (FF) fu = e1 / s11;
           s12 = 0.0; s22 = 0.0;
         } else if (f2) {
           ok = finite1(s22) && s22 > 0.0;
           g2 = h2 / s22;
+          if constexpr (FF) ft = e2 / s22;
           s11 = 0.0; s12 = 0.0;
         } else {
           s11 = 0.0; s12 = 0.0; s22 = 0.0;
         }
         if (!ok) break;                       // uniform: every lane computed the same S
+        if constexpr (FF) {
+          if (t == 0) {
+            ff_u[(size_t)kk * B + p] = fu;
+            if (kk + 1 == K) ff_t[p] = ft;
+          }
+          fmax_u = max_nan2(fmax_u, fabs(fu));
+          fmax_t = max_nan2(fmax_t, fabs(ft));
+          // p <- Phi' a - G' S f: every lane holds column pj of G and of a' Phi; lanes 49..55 store theirs (p is read in A only)
+          if (t >= 49 && t < 56) pv[pj] = ep - (g1 * (s11 * fu + s12 * ft) + g2 * (s12 * fu + s22 * ft));
+        }
         if (t < 7) {
           Gs[t] = g1;
           Gs[7 + t] = g2;
@@ -225,6 +317,20 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
           ASC_UNROLL
           for (int a = 0; a < NACC; a++) As[t * NACC + a] += o[C_DT + a];
           const double ot = dt * o[C_DT];
+          if constexpr (FF) {
+            double *N = Ns + t * NNAV;
+            ASC_UNROLL
+            for (int i = 0; i < 7; i++) {
+              double v = N[i];
+              if (f1) v += o[C_U] * Gs[i];
+              if (f2) v += ot * Gs[7 + i];
+              N[i] = v;
+            }
+            double v = N[7];
+            if (f1) v += o[C_U] * fu;
+            if (f2) v += ot * ft;
+            N[7] = v;
+          }
           ASC_UNROLL
           for (int i = 0; i < 7; i++) {
             double v = o[i];
@@ -253,6 +359,10 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
       summary[(size_t)2 * B + p] = frozen ? NAN : gmax;
       summary[(size_t)3 * B + p] = frozen ? NAN : tmax;
       summary[(size_t)4 * B + p] = (double)m;
+      if constexpr (FF) {                     // wave-uniform: every lane formed the same f
+        summary[(size_t)5 * B + p] = frozen ? NAN : fmax_u;
+        summary[(size_t)6 * B + p] = frozen ? NAN : fmax_t;
+      }
     }
   }
   if (frozen) {                               // NaN gains and Jacobian; after the sweeping wavefront's own stores have landed
@@ -264,6 +374,12 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
       for (int e = t; e < JROWS * JCOLS; e += JB) jac[(size_t)e * B + p] = NAN;
     if (jac_u)
       for (int e = t; e < JROWS * K; e += JB) jac_u[(size_t)e * B + p] = NAN;
+    if constexpr (FF) {
+      for (int e = t; e < K; e += JB) ff_u[(size_t)e * B + p] = NAN;
+      if (t == 0) ff_t[p] = NAN;
+      if (jac_nav)
+        for (int e = t; e < JROWS * NNAV; e += JB) jac_nav[(size_t)e * B + p] = NAN;
+    }
     return;
   }
 
@@ -291,9 +407,41 @@ __global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ 
     o[7 + 12] = FORM == 1 ? aAL : 0.0;                                // angle_ub
     o[7 + 13] = 0.0; o[7 + 14] = 0.0; o[7 + 15] = 0.0;                // tf_lb, tf_ub, dcost
     o[23] = aDT * (d.T / K);                                          // t_f
+    if constexpr (FF) {                                               // theta-hat = w . dp steers against E_q
+      const double *N = Ns + t * NNAV;
+      const double eq = N[7];
+      ASC_UNROLL
+      for (int cc = 0; cc < 16; cc++) o[7 + cc] -= eq * ff_know[(size_t)cc * B + p];
+      if (jac_nav) {
+        ASC_UNROLL
+        for (int a = 0; a < NNAV; a++) jac_nav[((size_t)t * NNAV + a) * B + p] = -N[a];
+      }
+    }
     ASC_UNROLL
     for (int cc = 0; cc < JCOLS; cc++) jac[((size_t)t * JCOLS + cc) * B + p] = o[cc];
   }
+}
+
+template <int FORM>
+__global__ __launch_bounds__(JB) void g_gains(const ascent_params *__restrict__ P, long batch, int K, int substeps,
+                                              const double *__restrict__ blob, const double *__restrict__ traj,
+                                              const double *__restrict__ weights, double *__restrict__ gain_u,
+                                              double *__restrict__ gain_t, double *__restrict__ summary,
+                                              double *__restrict__ jac, double *__restrict__ jac_u) {
+  gains_body<FORM, false>(P, batch, K, substeps, blob, traj, weights, gain_u, gain_t, summary, jac, jac_u, nullptr, nullptr, nullptr,
+                          nullptr, nullptr);
+}
+
+template <int FORM>
+__global__ __launch_bounds__(JB) void g_gains_ff(const ascent_params *__restrict__ P, long batch, int K, int substeps,
+                                                 const double *__restrict__ blob, const double *__restrict__ traj,
+                                                 const double *__restrict__ weights, double *__restrict__ gain_u,
+                                                 double *__restrict__ gain_t, double *__restrict__ summary,
+                                                 double *__restrict__ jac, double *__restrict__ jac_u,
+                                                 const double *__restrict__ ff_dir, const double *__restrict__ ff_know,
+                                                 double *__restrict__ ff_u, double *__restrict__ ff_t, double *__restrict__ jac_nav) {
+  gains_body<FORM, true>(P, batch, K, substeps, blob, traj, weights, gain_u, gain_t, summary, jac, jac_u, ff_dir, ff_know, ff_u, ff_t,
+                         jac_nav);
 }
 
 }  // namespace
@@ -311,6 +459,22 @@ int gains_run(const Call &c, int substeps, const double *dblob, const double *dw
   else
     hipLaunchKernelGGL((g_gains<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, traj, dweights, dgain_u, dgain_t,
                        dsummary, djac, djac_u);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
+  return ASCENT_OK;
+}
+
+int gains_ff_run(const Call &c, int substeps, const double *dblob, const double *dweights, const double *dff_dir,
+                 const double *dff_know, double *dgain_u, double *dgain_t, double *dff_u, double *dff_t, double *dsummary,
+                 double *djac, double *djac_u, double *djac_nav, double *ws) {
+  double *traj = ws, *fsum = ws + (size_t)ASCENT_TRAJ_FIELDS * (c.K + 1) * (size_t)c.batch;
+  if (const int rc = flight_fly_only(c, substeps, dblob, traj, fsum)) return rc;
+  const dim3 grid((unsigned)c.batch), block(JB);
+  if (c.form == 1)
+    hipLaunchKernelGGL((g_gains_ff<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, traj, dweights, dgain_u, dgain_t,
+                       dsummary, djac, djac_u, dff_dir, dff_know, dff_u, dff_t, djac_nav);
+  else
+    hipLaunchKernelGGL((g_gains_ff<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, traj, dweights, dgain_u, dgain_t,
+                       dsummary, djac, djac_u, dff_dir, dff_know, dff_u, dff_t, djac_nav);
   ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }

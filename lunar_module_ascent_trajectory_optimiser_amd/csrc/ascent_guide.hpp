@@ -18,4 +18,11 @@ size_t gains_ws_bytes(int K, long batch);
 int gains_run(const Call &c, int substeps, const double *dblob, const double *dweights, double *dgain_u, double *dgain_t,
               double *dsummary, double *djac, double *djac_u, double *ws);
 
+// include/ascent.h: ascent_guidance_feedforward.  As gains_run, plus dff_dir [16][batch], dff_know [16][batch] or null (needed
+// with djac), dff_u [K][batch], dff_t [batch], dsummary [ASCENT_GUIDE_FF_ROWS][batch], djac_nav [9][ASCENT_NAV_ROWS][batch] or null
+// (only with djac).  Same workspace; enqueues f_fly and g_gains_ff.
+int gains_ff_run(const Call &c, int substeps, const double *dblob, const double *dweights, const double *dff_dir,
+                 const double *dff_know, double *dgain_u, double *dgain_t, double *dff_u, double *dff_t, double *dsummary,
+                 double *djac, double *djac_u, double *djac_nav, double *ws);
+
 }  // namespace ascent

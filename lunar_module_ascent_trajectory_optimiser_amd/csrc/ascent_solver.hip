@@ -949,6 +949,70 @@ int ascent_disperse_guided_batch(const ascent_params *p, int64_t batch, const as
   return st.finish();
 }
 
+// The feed-forward siblings of the two calls above: same checks, same workspace, same staging
+int ascent_guidance_feedforward(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                                const double *weights, const double *ff_dir, const double *ff_know, double *gain_u_out,
+                                double *gain_t_out, double *ff_u_out, double *ff_t_out, double *summary_out, double *jac_cl_out,
+                                double *jac_u_cl_out, double *jac_nav_out, int device_id, void *stream_, int ptr_is_device) {
+  int rc = check_flight_like(p, batch, o, sol_blob, substeps, ptr_is_device);
+  if (rc) return rc;
+  if (!weights || !gain_u_out || !gain_t_out || !summary_out) { snprintf(g_err, sizeof g_err, "null weights, gain_u_out, gain_t_out or summary_out"); return ASCENT_E_ARG; }
+  if (!ff_dir || !ff_u_out || !ff_t_out) { snprintf(g_err, sizeof g_err, "null ff_dir, ff_u_out or ff_t_out"); return ASCENT_E_ARG; }
+  if (jac_u_cl_out && !jac_cl_out) { snprintf(g_err, sizeof g_err, "jac_u_cl_out needs jac_cl_out"); return ASCENT_E_ARG; }
+  if (jac_nav_out && !jac_cl_out) { snprintf(g_err, sizeof g_err, "jac_nav_out needs jac_cl_out"); return ASCENT_E_ARG; }
+  if (jac_cl_out && !ff_know) { snprintf(g_err, sizeof g_err, "jac_cl_out needs ff_know"); return ASCENT_E_ARG; }
+  if ((rc = check_device(device_id))) return rc;
+  std::lock_guard<std::mutex> lock(g_mu[device_id]);
+  HIPCHK(hipSetDevice(device_id));
+  hipStream_t stream = (hipStream_t)stream_;
+  const int K = o->n_nodes - 1;
+  double *ws = nullptr;
+  if ((rc = trim_ws_claim(device_id, gains_ws_bytes(K, (long)batch), stream, &ws))) return rc;
+  Staging st(stream, ptr_is_device);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
+  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch), *dw = st.in(weights, (size_t)6 * batch);
+  const double *dd = st.in(ff_dir, (size_t)16 * batch), *dk = st.in(ff_know, (size_t)16 * batch);
+  double *dgu = st.out(gain_u_out, (size_t)7 * K * batch), *dgt = st.out(gain_t_out, (size_t)7 * batch);
+  double *dfu = st.out(ff_u_out, (size_t)K * batch), *dft = st.out(ff_t_out, (size_t)batch);
+  double *ds = st.out(summary_out, (size_t)ASCENT_GUIDE_FF_ROWS * batch);
+  double *dj = st.out(jac_cl_out, (size_t)9 * 24 * batch), *du = st.out(jac_u_cl_out, (size_t)9 * K * batch);
+  double *dn = st.out(jac_nav_out, (size_t)9 * ASCENT_NAV_ROWS * batch);
+  if ((rc = st.failed()) || (rc = gains_ff_run(c, substeps, db, dw, dd, dk, dgu, dgt, dfu, dft, ds, dj, du, dn, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
+  return st.finish();
+}
+
+int ascent_disperse_navigated_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                                    int32_t samples, const double *xi, const double *sigma, const double *sigma_u, const double *gain_u,
+                                    const double *gain_t, const double *stretch_max, const double *ff_u, const double *ff_t,
+                                    const double *ff_know, const double *xi_nav, const double *sigma_nav, double *stats_out,
+                                    double *samples_out, int device_id, void *stream_, int ptr_is_device) {
+  int rc = check_options(p, batch, o);
+  if (rc) return rc;
+  if (!sol_blob || !xi || !sigma || !gain_u || !stats_out) { snprintf(g_err, sizeof g_err, "null solution blob, xi, sigma, gain_u or stats_out"); return ASCENT_E_ARG; }
+  if (samples < 1 || samples > ASCENT_DISPERSE_MAX_SAMPLES) { snprintf(g_err, sizeof g_err, "samples out of range (1 .. %d)", ASCENT_DISPERSE_MAX_SAMPLES); return ASCENT_E_ARG; }
+  if ((xi_nav != nullptr) != (sigma_nav != nullptr)) { snprintf(g_err, sizeof g_err, "xi_nav and sigma_nav come together"); return ASCENT_E_ARG; }
+  if (ff_know && !ff_u) { snprintf(g_err, sizeof g_err, "ff_know needs ff_u"); return ASCENT_E_ARG; }
+  if ((rc = check_substeps(substeps)) || (rc = check_solvable(p, batch, o, ptr_is_device)) || (rc = check_device(device_id))) return rc;
+  std::lock_guard<std::mutex> lock(g_mu[device_id]);
+  HIPCHK(hipSetDevice(device_id));
+  hipStream_t stream = (hipStream_t)stream_;
+  const int K = o->n_nodes - 1;
+  double *ws = nullptr;
+  if ((rc = trim_ws_claim(device_id, disperse_ws_bytes(K, (long)batch, samples), stream, &ws))) return rc;
+  Staging st(stream, ptr_is_device);
+  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
+  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch);
+  const double *dx = st.in(xi, (size_t)(ASCENT_DISPERSE_COLS + (sigma_u ? K : 0)) * samples);
+  const double *dsg = st.in(sigma, (size_t)ASCENT_DISPERSE_COLS * batch), *dsu = st.in(sigma_u, (size_t)K * batch);
+  const double *dgu = st.in(gain_u, (size_t)7 * K * batch), *dgt = st.in(gain_t, (size_t)7 * batch), *dsx = st.in(stretch_max, (size_t)batch);
+  const double *dfu = st.in(ff_u, (size_t)K * batch), *dft = st.in(ff_t, (size_t)batch), *dfk = st.in(ff_know, (size_t)16 * batch);
+  const double *dxn = st.in(xi_nav, (size_t)ASCENT_NAV_ROWS * samples), *dsn = st.in(sigma_nav, (size_t)ASCENT_NAV_ROWS * batch);
+  double *dst = st.out(stats_out, (size_t)ASCENT_DISPERSE_STAT_ROWS * batch);
+  double *dsm = st.out(samples_out, (size_t)ASCENT_GUIDED_SAMPLE_ROWS * samples * batch);
+  if ((rc = st.failed()) || (rc = disperse_navigated_run(c, substeps, samples, db, dx, dsg, dsu, dgu, dgt, dsx, dfu, dft, dfk, dxn, dsn, dst, dsm, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
+  return st.finish();
+}
+
 int ascent_kkt_step(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,
                     const double *mu, const double *delta_w, double *step, int32_t *inertia_out, int device_id) {
   return ascent_kkt_step_path(p, batch, o, iterate, mu, delta_w, step, inertia_out, device_id, ASCENT_PATH_AUTO);

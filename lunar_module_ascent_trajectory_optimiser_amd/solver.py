@@ -8,7 +8,7 @@ import dataclasses
 import numpy as np
 
 from . import _lib
-from .params import AscentParams, pack
+from .params import PARAM_FIELDS, AscentParams, pack
 
 TRAJ_FIELDS = ("x", "y", "xdot", "ydot", "xdoubledot", "ydoubledot", "angle", "angledot",
                "angledoubledot", "mass")
@@ -154,15 +154,19 @@ class DispersionResult:
     tf_sigma: np.ndarray            # (batch,) scaled units
     control_sigma: np.ndarray       # (batch, K)
     effort: np.ndarray | None = None    # (batch, samples, 3) guided flights with keep_samples: EFFORT_ROWS
+    xi_nav: np.ndarray | None = None    # (8, samples) the navigation draws (ascent_disperse_navigated_batch), shared by every problem
+    nav_sigma: np.ndarray | None = None     # (batch, 8): 7 state-knowledge biases (scaled units), the error of theta-hat
 
     @property
     def std(self) -> np.ndarray:
         """(batch, 9)"""
         return np.sqrt(np.diagonal(self.cov, axis1=1, axis2=2))
 
-    def linear_covariance(self, J: FlightJacobian) -> np.ndarray:
+    def linear_covariance(self, J: FlightJacobian, J_nav: np.ndarray | None = None) -> np.ndarray:
         """(batch, 9, 9) J D C_xi D J': the first-order prediction of `cov` from a FlightJacobian of the same blob, D the sigmas of
-        this result and C_xi the unbiased sample covariance of the rows of this very `xi` -- no sampling noise between the two."""
+        this result and C_xi the unbiased sample covariance of the rows of this very `xi` -- no sampling noise between the two.
+        J_nav (batch, 9, 8), GuidanceResult.jacobian_nav: the navigation block, with this result's nav_sigma and xi_nav, is added
+        (the two tables of draws are taken as one sample)."""
         A = [J.dz0 * self.z0_sigma[:, None, :], J.dparams * self.param_sigma[:, None, :], (J.dtf * self.tf_sigma[:, None])[:, :, None]]
         n = 24
         if self.control_sigma.any():
@@ -170,13 +174,20 @@ class DispersionResult:
                 raise ValueError("this FlightJacobian was computed without the control columns")
             A.append(J.dcontrols * self.control_sigma[:, None, :])
             n += self.control_sigma.shape[1]
+        draws = self.xi[:n]
+        if J_nav is not None:
+            if self.nav_sigma is None or self.xi_nav is None:
+                raise ValueError("this dispersion was flown without navigation errors")
+            A.append(np.asarray(J_nav, dtype=np.float64) * self.nav_sigma[:, None, :])
+            draws = np.concatenate([draws, self.xi_nav], axis=0)
         A = np.concatenate(A, axis=2)
-        C = np.atleast_2d(np.cov(self.xi[:n]))
+        C = np.atleast_2d(np.cov(draws))
         return np.einsum("bqc,cd,brd->bqr", A, C, A)
 
 
 EFFORT_ROWS = ("clipped_steps", "max_feedback", "stretch")
 GUIDE_ROWS = ("status", "free_controls", "max_gain", "max_cutoff_gain", "substeps")
+GUIDE_FF_ROWS = GUIDE_ROWS + ("max_feedforward", "max_cutoff_feedforward")
 GUIDE_STATUS_NAMES = {0: "ok", 2: "frozen"}
 
 
@@ -187,12 +198,19 @@ class GuidanceResult:
     -gain_t . (z - z_{K-1}^nominal), clipped to +-stretch_max.  Problem index first."""
     gain_u: np.ndarray              # (batch, K, 7); the row of a saturated control is exactly zero
     gain_t: np.ndarray              # (batch, 7) zero where stretch_max = 0
-    summary: np.ndarray             # (batch, 5) columns GUIDE_ROWS
+    summary: np.ndarray             # (batch, 5) columns GUIDE_ROWS; (batch, 7), columns GUIDE_FF_ROWS, with a feed-forward
     stretch_max: np.ndarray         # (batch,)
     jacobian: FlightJacobian | None     # the flight Jacobian of the closed loop, clips ignored; dcontrols: execution errors
+    # with a feed-forward (guidance_gains(feedforward=...); include/ascent.h: ascent_guidance_feedforward): step k commands, beyond
+    # the feedback, -ff_u[:, k-1] * theta-hat and the stretch -ff_t * theta-hat; summary is then (batch, 7), columns GUIDE_FF_ROWS
+    ff_u: np.ndarray | None = None      # (batch, K); exactly zero for a saturated control
+    ff_t: np.ndarray | None = None      # (batch,)
+    ff_dir: np.ndarray | None = None    # (batch, 16) the direction d of the parameter deviation theta * d, SI units
+    ff_know: np.ndarray | None = None   # (batch, 16) the row w of theta-hat = w . (the vehicle's 16 parameter deviations)
+    jacobian_nav: np.ndarray | None = None      # (batch, 9, 8): 7 state-knowledge biases (scaled units), the error of theta-hat
 
 
-for _i, _n in enumerate(GUIDE_ROWS):    # the summary columns by name: .status, .free_controls, ... -> (batch,)
+for _i, _n in enumerate(GUIDE_FF_ROWS):    # the summary columns by name: .status, .free_controls, ... -> (batch,)
     setattr(GuidanceResult, _n, property(lambda self, _i=_i: self.summary[:, _i]))
 
 
@@ -475,7 +493,8 @@ def trim_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, t
 
 def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, control_sigma=None, tf_sigma=None, z0_sigma=None,
                    samples: int = 256, seed: int = 0, xi=None, keep_samples: bool = False, scheme=0, formulation=0, terminal=0,
-                   move_penalty: bool = False, substeps: int = 0, device: int = 0, guidance: GuidanceResult | None = None) -> DispersionResult:
+                   move_penalty: bool = False, substeps: int = 0, device: int = 0, guidance: GuidanceResult | None = None,
+                   nav_sigma=None, knowledge_sigma=None, xi_nav=None, nav_seed: int = 1) -> DispersionResult:
     """Monte Carlo dispersion (include/ascent.h: ascent_disperse_batch): every blob's control flown `samples` times on the
     device as fly_batch flies it, with the initial state, the 16 parameter fields, t_f and every control perturbed by
     sigma * xi, and the nine end quantities reduced on the device to count, mean, covariance and extrema.  The blob is shared
@@ -486,7 +505,11 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     for every sample.  keep_samples: also return every sample's rows.  terminal 2 is accepted.
     guidance: a GuidanceResult (or anything with gain_u (batch, K, 7), gain_t (batch, 7) or None and stretch_max): every sample
     steers by that feedback (include/ascent.h: ascent_disperse_guided_batch) and, with keep_samples, `effort` (batch, samples, 3)
-    holds EFFORT_ROWS.  None: the open-loop call."""
+    holds EFFORT_ROWS.  None: the open-loop call.
+    Where `guidance` carries a feed-forward (ff_u, ff_t, ff_know; guidance_gains(feedforward=...)) or a navigation error is given,
+    the call is ascent_disperse_navigated_batch: nav_sigma (7,) or (batch, 7), scaled units, the 1-sigma bias of each sample's state
+    knowledge; knowledge_sigma a scalar or (batch,), the 1-sigma error of theta-hat in the units of theta; xi_nav (8, samples) their
+    draws, None draws np.random.default_rng(nav_seed).standard_normal((8, samples))."""
     L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     if xi is None:
         xi = np.random.default_rng(seed).standard_normal((24 + K, int(samples)))
@@ -501,6 +524,11 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     sig_u = np.ascontiguousarray(us.T) if control_sigma is not None else None
     stats = np.empty((82, B))
     smp = np.empty((9 if guidance is None else 12, S, B)) if keep_samples else None
+    ffu = getattr(guidance, "ff_u", None)
+    navigated = ffu is not None or nav_sigma is not None or knowledge_sigma is not None
+    if navigated and guidance is None:
+        raise ValueError("nav_sigma and knowledge_sigma need guidance")
+    nav_s = None
     if guidance is None:
         _lib.check(L.ascent_disperse_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
                                            _ptr(stats), _ptr(smp), device, None, 0))
@@ -512,25 +540,64 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
         if gt is not None and gt.shape != (7, B):
             raise ValueError(f"guidance.gain_t must have shape {(B, 7)}")
         sm = None if gt is None else _sigma_rows(np.asarray(guidance.stretch_max, dtype=np.float64)[..., None], 1, B, "stretch_max")[:, 0].copy()
-        _lib.check(L.ascent_disperse_guided_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
-                                                  _ptr(gu), _ptr(gt), _ptr(sm), _ptr(stats), _ptr(smp), device, None, 0))
+        if not navigated:
+            _lib.check(L.ascent_disperse_guided_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
+                                                      _ptr(gu), _ptr(gt), _ptr(sm), _ptr(stats), _ptr(smp), device, None, 0))
+        else:
+            fu = ft = fk = None
+            if ffu is not None:
+                fu = np.ascontiguousarray(np.asarray(ffu, dtype=np.float64).T)
+                if fu.shape != (K, B):
+                    raise ValueError(f"guidance.ff_u must have shape {(B, K)}")
+                ft, fk = getattr(guidance, "ff_t", None), getattr(guidance, "ff_know", None)
+                if ft is not None:
+                    ft = np.ascontiguousarray(np.asarray(ft, dtype=np.float64))
+                    if ft.shape != (B,):
+                        raise ValueError(f"guidance.ff_t must have shape {(B,)}")
+                if fk is not None:
+                    fk = np.ascontiguousarray(np.asarray(fk, dtype=np.float64).T)
+                    if fk.shape != (16, B):
+                        raise ValueError(f"guidance.ff_know must have shape {(B, 16)}")
+            sn = None
+            if nav_sigma is not None or knowledge_sigma is not None:
+                ks = _sigma_rows(None if knowledge_sigma is None else np.asarray(knowledge_sigma, dtype=np.float64)[..., None], 1, B,
+                                 "knowledge_sigma")
+                nav_s = np.concatenate([_sigma_rows(nav_sigma, 7, B, "nav_sigma"), ks], axis=1)
+                sn = np.ascontiguousarray(nav_s.T)
+                if xi_nav is None:
+                    xi_nav = np.random.default_rng(nav_seed).standard_normal((8, S))
+                xi_nav = np.ascontiguousarray(xi_nav, dtype=np.float64)
+                if xi_nav.shape != (8, S):
+                    raise ValueError(f"xi_nav must have shape (8, samples) = {(8, S)}")
+            else:
+                xi_nav = None
+            _lib.check(L.ascent_disperse_navigated_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
+                                                         _ptr(gu), _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(xi_nav), _ptr(sn),
+                                                         _ptr(stats), _ptr(smp), device, None, 0))
     st = stats.T
     return DispersionResult(st[:, 0].astype(np.int64), np.ascontiguousarray(st[:, 1:10]), np.ascontiguousarray(st[:, 10:19]),
                             _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
                             None if smp is None else np.ascontiguousarray(smp[:9].transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us,
-                            None if smp is None or guidance is None else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)))
+                            None if smp is None or guidance is None else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)),
+                            xi_nav if nav_s is not None else None, nav_s)
 
 
 def guidance_gains(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,
                    substeps: int = 0, device: int = 0, cond_weights=(1e6, 1e6, 1e6), control_weight=1.0, cutoff_weight=1.0,
-                   stretch_max=0.5, want_jacobian: bool = True) -> GuidanceResult:
+                   stretch_max=0.5, want_jacobian: bool = True, feedforward=None, knowledge=None) -> GuidanceResult:
     """Guidance gains (include/ascent.h: ascent_guidance_gains): the linear-quadratic feedback about the flight of a blob
     (21K+10, batch) -- normally a trimmed one, since the target is what the nominal control reaches -- from a backward Riccati
     sweep over the step records of the flight Jacobian.  cond_weights (3,) or (batch, 3): the weights q of the squared
     deviations of the trim's three conditions at the last node; control_weight r_u and cutoff_weight r_t, scalars or (batch,),
     weigh du_k^2 and the squared relative stretch tau^2 of the last step; stretch_max bounds |tau| (0: steering only).  In double
     precision the gains lose digits as q grows (about 1e-12 at 1e6, 3e-5 at 1e12).  Returns a GuidanceResult; pass it to
-    disperse_batch(..., guidance=...).  terminal 2 is refused."""
+    disperse_batch(..., guidance=...).  terminal 2 is refused.
+    feedforward: a PARAM_FIELDS name (the unit direction in that field: "Ft" is newtons of thrust), (16,) or (batch, 16): the
+    direction d of a constant parameter deviation theta * d the vehicle has an estimate theta-hat of; the result then carries the
+    feed-forward gains ff_u, ff_t (include/ascent.h: ascent_guidance_feedforward; the feedback gains are unchanged bit for bit),
+    a (batch, 7) summary and, with want_jacobian, jacobian_nav and a closed-loop Jacobian whose parameter columns account for
+    theta-hat = knowledge . (the 16 parameter deviations); knowledge (16,) or (batch, 16), None: d / (d . d), the vehicle knows
+    theta exactly."""
     L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     w = np.ascontiguousarray(np.concatenate([_sigma_rows(cond_weights, 3, B, "cond_weights")] + [
         _sigma_rows(np.asarray(v, dtype=np.float64)[..., None], 1, B, n)
@@ -538,15 +605,39 @@ def guidance_gains(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=
     gu, gt, summ = np.empty((7, K, B)), np.empty((7, B)), np.empty((len(GUIDE_ROWS), B))
     jac = np.empty((9, 24, B)) if want_jacobian else None
     ju = np.empty((9, K, B)) if want_jacobian else None
-    _lib.check(L.ascent_guidance_gains(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(w), _ptr(gu), _ptr(gt), _ptr(summ),
-                                       _ptr(jac), _ptr(ju), device, None, 0))
+    ff = {}
+    if feedforward is None:
+        if knowledge is not None:
+            raise ValueError("knowledge needs feedforward")
+        _lib.check(L.ascent_guidance_gains(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(w), _ptr(gu), _ptr(gt), _ptr(summ),
+                                           _ptr(jac), _ptr(ju), device, None, 0))
+    else:
+        if isinstance(feedforward, str):
+            if feedforward not in PARAM_FIELDS:
+                raise ValueError(f"feedforward must be one of {PARAM_FIELDS} or a direction of 16 fields")
+            feedforward = np.eye(16)[PARAM_FIELDS.index(feedforward)]
+        dirs = _sigma_rows(feedforward, 16, B, "feedforward")
+        if knowledge is None:
+            dd = np.einsum("bi,bi->b", dirs, dirs)[:, None]
+            with np.errstate(all="ignore"):
+                know = np.where(dd > 0, dirs / np.where(dd > 0, dd, 1.0), dirs * 0.0)
+        else:
+            know = _sigma_rows(knowledge, 16, B, "knowledge")
+        dT, kT = np.ascontiguousarray(dirs.T), np.ascontiguousarray(know.T)
+        summ = np.empty((len(GUIDE_FF_ROWS), B))
+        fu, ft = np.empty((K, B)), np.empty(B)
+        jn = np.empty((9, 8, B)) if want_jacobian else None
+        _lib.check(L.ascent_guidance_feedforward(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(w), _ptr(dT), _ptr(kT), _ptr(gu),
+                                                 _ptr(gt), _ptr(fu), _ptr(ft), _ptr(summ), _ptr(jac), _ptr(ju), _ptr(jn), device, None, 0))
+        ff = dict(ff_u=np.ascontiguousarray(fu.T), ff_t=ft, ff_dir=dirs, ff_know=know,
+                  jacobian_nav=None if jn is None else np.ascontiguousarray(jn.transpose(2, 0, 1)))
     J = None
     if want_jacobian:
         j = jac.transpose(2, 0, 1)
         J = FlightJacobian(np.ascontiguousarray(j[:, :, :7]), np.ascontiguousarray(j[:, :, 7:23]), np.ascontiguousarray(j[:, :, 23]),
                            np.ascontiguousarray(ju.transpose(2, 0, 1)))
     return GuidanceResult(np.ascontiguousarray(gu.transpose(2, 1, 0)), np.ascontiguousarray(gt.T), np.ascontiguousarray(summ.T),
-                          w[5].copy(), J)
+                          w[5].copy(), J, **ff)
 
 
 def eval_nodes(params, iterate: np.ndarray, nt: int = 200, device: int = 0, path="auto", scheme=0, formulation=0):
