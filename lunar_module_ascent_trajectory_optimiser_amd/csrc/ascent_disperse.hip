@@ -19,6 +19,8 @@
 // f_disperse_guided f_disperse under state feedback (ascent_disperse_guided_batch): same mapping, same record, same reduction.
 // f_disperse_navigated  f_disperse_guided with the feed-forward f_k theta-hat and the navigation errors of
 //          ascent_disperse_navigated_batch: one body with f_disperse_guided (guided_body<FORM, NAV>).
+// The kernels share their head (sample_lane, perturbed_sample) and their tail (end_rows, reduce_partial); only the step loops
+// differ.  One host function, disperse_run, launches whichever kernel the call's kind names.
 // The order of every addition is fixed by `samples` alone: a problem gives the same bits alone as inside any batch.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -43,8 +45,6 @@ constexpr int R_N = 0, R_SUM = 1, R_PROD = R_SUM + NQ, R_MIN = R_PROD + NQ * (NQ
 constexpr int O_N = 0, O_NOM = 1, O_MEAN = O_NOM + NQ, O_COV = O_MEAN + NQ, O_MIN = O_COV + NQ * (NQ + 1) / 2, O_MAX = O_MIN + NQ;
 static_assert(O_MAX + NQ == ASCENT_DISPERSE_STAT_ROWS, "stats_out layout");
 constexpr long MAX_GRID = 1L << 22;        // workgroups per launch: 2^30 threads
-
-ASC_DEV bool finite1(double a) { return fabs(a) <= 1.79769313486231570815e308; }
 
 // butterflies: every lane ends with the same bits (no lane contributes a NaN: invalid samples enter as +-inf)
 ASC_DEV double wave_min(double v) {
@@ -97,6 +97,88 @@ ASC_DEV void wave_record(const double *r, bool valid, const double *cen, int lan
   }
 }
 
+// Where a lane of the dispersion kernels stands: its problem p, chunk c, sample s, and what every sample of the problem shares --
+// the blob column b, the 16 fields pf in declaration order, the blob's t_f and the nominal flight's substeps m, held.
+struct Lane {
+  long p;
+  int c, t, s, m;
+  size_t B, NS;
+  const double *b, *pf;
+  double tf0;
+};
+
+// the head of a dispersion kernel, every lane: indexing, the centre of the moments, and the rows of a lane without a sample
+ASC_DEV void sample_lane(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples, int nwg, long g0,
+                         const double *__restrict__ blob, const double *__restrict__ traj, const double *__restrict__ fsum,
+                         Lane &l, double *cen, double *r) {
+  const long g = g0 + blockIdx.x;
+  l.p = g / nwg;
+  l.c = (int)(g - l.p * nwg);
+  l.t = threadIdx.x;
+  l.s = l.c * DB + l.t;
+  l.B = (size_t)batch; l.NS = (size_t)samples;
+  l.b = blob + l.p;
+  l.pf = reinterpret_cast<const double *>(P + l.p);      // the 16 fields in declaration order
+  l.tf0 = l.b[(size_t)(21 * K + S_TH) * l.B];
+  l.m = flight_substeps((l.tf0 * l.pf[11]) / K, substeps);      // the nominal flight's, held
+  nominal_rows(traj, fsum, l.B, l.p, K, cen);
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) cen[q] = finite1(cen[q]) ? cen[q] : 0.0;
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) r[q] = NAN;
+}
+
+// the head of a lane that has a sample: the 24 sigmas (wave-uniform) and draws, loaded together -- a draw counts only where its
+// sigma is not zero --, the perturbed initial state, parameters (derive per sample) and t_f, the step dt and the substep hs
+ASC_DEV void perturbed_sample(const Lane &l, int K, const double *__restrict__ xi, const double *__restrict__ sigma, double *sg,
+                              double *xv, double *z, ascent_params &prm, Der &d, double &dt, double &hs) {
+  const double *x = xi + l.s;
+  ASC_UNROLL
+  for (int i = 0; i < NC; i++) sg[i] = sigma[(size_t)i * l.B + l.p];
+  ASC_UNROLL
+  for (int i = 0; i < NC; i++) xv[i] = x[(size_t)i * l.NS];
+  double f[16];
+  ASC_UNROLL
+  for (int i = 0; i < 7; i++) z[i] = sg[i] != 0.0 ? sg[i] * xv[i] : 0.0;
+  ASC_UNROLL
+  for (int i = 0; i < 16; i++) f[i] = sg[7 + i] != 0.0 ? l.pf[i] + sg[7 + i] * xv[7 + i] : l.pf[i];
+  const double tf = sg[23] != 0.0 ? l.tf0 + sg[23] * xv[23] : l.tf0;
+  prm = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11], f[12], f[13], f[14], f[15]};
+  d = derive(prm);
+  dt = (tf * d.T) / K;
+  hs = dt / l.m;
+}
+
+// the tail of a lane that has a sample: the nine end rows from the flown state, and the caller's copy of them
+ASC_DEV void end_rows(const Lane &l, const ascent_params &prm, const double *z, double *r, double *__restrict__ samples_out) {
+  ASC_UNROLL
+  for (int i = 0; i < 7; i++) r[i] = z[i];
+  apsides_of(prm, z[IX], z[IY], z[IVX], z[IVY], r[7], r[8]);
+  if (samples_out) {
+    ASC_UNROLL
+    for (int q = 0; q < NQ; q++) samples_out[((size_t)q * l.NS + l.s) * l.B + l.p] = r[q];
+  }
+}
+
+// the tail of a dispersion kernel, every lane: validity, the wavefront's record, and the waves that exist (4, or fewer where
+// samples <= 192) reduced in wave order into the workgroup's partial record
+ASC_DEV void reduce_partial(const Lane &l, const double *r, const double *cen, double (*red)[NREC], double *__restrict__ partial) {
+  bool valid = true;
+  ASC_UNROLL
+  for (int q = 0; q < NQ; q++) valid = valid && finite1(r[q]);
+  wave_record(r, valid, cen, l.t & 63, red[l.t >> 6]);
+  __syncthreads();
+  const int nw = (int)blockDim.x >> 6;
+  for (int i = l.t; i < NREC; i += (int)blockDim.x) {
+    double a = red[0][i];
+    for (int w = 1; w < nw; w++) {
+      const double o = red[w][i];
+      a = i < R_MIN ? a + o : i < R_MAX ? fmin(a, o) : fmax(a, o);
+    }
+    partial[((size_t)l.c * NREC + i) * l.B + l.p] = a;
+  }
+}
+
 template <int FORM>
 __global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
                                                  int nwg, long g0, const double *__restrict__ blob,
@@ -105,43 +187,17 @@ __global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict
                                                  const double *__restrict__ sigma_u, double *__restrict__ partial,
                                                  double *__restrict__ samples_out) {
   __shared__ double red[DNW][NREC];
-  const long g = g0 + blockIdx.x;
-  const long p = g / nwg;
-  const int c = (int)(g - p * nwg);
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int s = c * DB + t;
-  const size_t B = (size_t)batch, NS = (size_t)samples;
-  const double *b = blob + p;
-  const double *pf = reinterpret_cast<const double *>(P + p);      // the 16 fields in declaration order
-  const double tf0 = b[(size_t)(21 * K + S_TH) * B];
-  const int m = flight_substeps((tf0 * pf[11]) / K, substeps);      // the nominal flight's, held
-  double cen[NQ];
-  nominal_rows(traj, fsum, B, p, K, cen);
-  ASC_UNROLL
-  for (int q = 0; q < NQ; q++) cen[q] = finite1(cen[q]) ? cen[q] : 0.0;
-
-  double r[NQ];
-  ASC_UNROLL
-  for (int q = 0; q < NQ; q++) r[q] = NAN;
-  if (s < samples) {
-    const double *x = xi + s;
-    // the 24 sigmas (wave-uniform) and draws of this sample, loaded together; a draw counts only where its sigma is not zero
-    double sg[NC], xv[NC];
-    ASC_UNROLL
-    for (int i = 0; i < NC; i++) sg[i] = sigma[(size_t)i * B + p];
-    ASC_UNROLL
-    for (int i = 0; i < NC; i++) xv[i] = x[(size_t)i * NS];
-    double z[7], f[16];
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) z[i] = sg[i] != 0.0 ? sg[i] * xv[i] : 0.0;
-    ASC_UNROLL
-    for (int i = 0; i < 16; i++) f[i] = sg[7 + i] != 0.0 ? pf[i] + sg[7 + i] * xv[7 + i] : pf[i];
-    const double tf = sg[23] != 0.0 ? tf0 + sg[23] * xv[23] : tf0;
-    const ascent_params prm = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11], f[12], f[13], f[14], f[15]};
-    const Der d = derive(prm);
-    const double dt = (tf * d.T) / K;
-    const double hs = dt / m;
-    const double *ub = b + (size_t)(7 * K) * B, *su = sigma_u ? sigma_u + p : nullptr, *xu = x + (size_t)NC * NS;
+  Lane l;
+  double cen[NQ], r[NQ];
+  sample_lane(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, l, cen, r);
+  if (l.s < samples) {
+    const size_t B = l.B, NS = l.NS;
+    const int m = l.m;
+    double sg[NC], xv[NC], z[7], dt, hs;
+    ascent_params prm;
+    Der d;
+    perturbed_sample(l, K, xi, sigma, sg, xv, z, prm, d, dt, hs);
+    const double *ub = l.b + (size_t)(7 * K) * B, *su = sigma_u ? sigma_u + l.p : nullptr, *xu = xi + l.s + (size_t)NC * NS;
     double u = ub[0];
     if (su) {
       const double s0 = su[0];
@@ -153,28 +209,9 @@ __global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict
       fly_step<FORM>(d, z, u, hs, m);
       u = sgn != 0.0 ? un + sgn * xn : un;
     }
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) r[i] = z[i];
-    apsides_of(prm, z[IX], z[IY], z[IVX], z[IVY], r[7], r[8]);
-    if (samples_out) {
-      ASC_UNROLL
-      for (int q = 0; q < NQ; q++) samples_out[((size_t)q * NS + s) * B + p] = r[q];
-    }
+    end_rows(l, prm, z, r, samples_out);
   }
-  bool valid = true;
-  ASC_UNROLL
-  for (int q = 0; q < NQ; q++) valid = valid && finite1(r[q]);
-  wave_record(r, valid, cen, lane, red[wv]);
-  __syncthreads();
-  const int nw = (int)blockDim.x >> 6;       // 4, or fewer where samples <= 192: the waves that exist, in wave order
-  for (int i = t; i < NREC; i += (int)blockDim.x) {
-    double a = red[0][i];
-    for (int w = 1; w < nw; w++) {
-      const double o = red[w][i];
-      a = i < R_MIN ? a + o : i < R_MAX ? fmin(a, o) : fmax(a, o);
-    }
-    partial[((size_t)c * NREC + i) * B + p] = a;
-  }
+  reduce_partial(l, r, cen, red, partial);
 }
 
 // f_disperse with the feedback of include/ascent.h: ascent_disperse_guided_batch.  Per step 7 nominal-state and 7 gain doubles
@@ -197,44 +234,19 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
                          const double *__restrict__ xi_nav, const double *__restrict__ sigma_nav,
                          double *__restrict__ partial, double *__restrict__ samples_out) {
   __shared__ double red[DNW][NREC];
-  const long g = g0 + blockIdx.x;
-  const long p = g / nwg;
-  const int c = (int)(g - p * nwg);
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int s = c * DB + t;
-  const size_t B = (size_t)batch, NS = (size_t)samples;
-  const int nt = K + 1;
-  const double *b = blob + p;
-  const double *pf = reinterpret_cast<const double *>(P + p);      // the 16 fields in declaration order
-  const double tf0 = b[(size_t)(21 * K + S_TH) * B];
-  const int m = flight_substeps((tf0 * pf[11]) / K, substeps);      // the nominal flight's, held
-  double cen[NQ];
-  nominal_rows(traj, fsum, B, p, K, cen);
-  ASC_UNROLL
-  for (int q = 0; q < NQ; q++) cen[q] = finite1(cen[q]) ? cen[q] : 0.0;
-
-  double r[NQ];
-  ASC_UNROLL
-  for (int q = 0; q < NQ; q++) r[q] = NAN;
-  if (s < samples) {
-    const double *x = xi + s;
-    double sg[NC], xv[NC];
-    ASC_UNROLL
-    for (int i = 0; i < NC; i++) sg[i] = sigma[(size_t)i * B + p];
-    ASC_UNROLL
-    for (int i = 0; i < NC; i++) xv[i] = x[(size_t)i * NS];
-    double z[7], f[16];
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) z[i] = sg[i] != 0.0 ? sg[i] * xv[i] : 0.0;
-    ASC_UNROLL
-    for (int i = 0; i < 16; i++) f[i] = sg[7 + i] != 0.0 ? pf[i] + sg[7 + i] * xv[7 + i] : pf[i];
-    const double tf = sg[23] != 0.0 ? tf0 + sg[23] * xv[23] : tf0;
-    const ascent_params prm = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11], f[12], f[13], f[14], f[15]};
-    const Der d = derive(prm);
-    const double dt = (tf * d.T) / K;
-    const double hs = dt / m;
+  Lane l;
+  double cen[NQ], r[NQ];
+  sample_lane(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, l, cen, r);
+  if (l.s < samples) {
+    const size_t B = l.B, NS = l.NS;
+    const long p = l.p;
+    const int s = l.s, m = l.m, nt = K + 1;
+    double sg[NC], xv[NC], z[7], dt, hs;
+    ascent_params prm;
+    Der d;
+    perturbed_sample(l, K, xi, sigma, sg, xv, z, prm, d, dt, hs);
     const double smax = gain_t && stretch_max ? stretch_max[p] : 0.0;
-    const double *ub = b + (size_t)(7 * K) * B, *su = sigma_u ? sigma_u + p : nullptr, *xu = x + (size_t)NC * NS;
+    const double *ub = l.b + (size_t)(7 * K) * B, *su = sigma_u ? sigma_u + p : nullptr, *xu = xi + s + (size_t)NC * NS;
     const double *tr = traj + p, *gu = gain_u + p;
     double un = ub[0], sgn = su ? su[0] : 0.0, xn = su ? xu[0] : 0.0, zn[7], kn[7];
     load_node(tr, B, nt, 0, zn);
@@ -311,31 +323,14 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
       if constexpr (NAV) fn = ff_u ? ff_u[(size_t)kq * B + p] : 0.0;
       fly_step<FORM>(d, z, u, h, m);
     }
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) r[i] = z[i];
-    apsides_of(prm, z[IX], z[IY], z[IVX], z[IVY], r[7], r[8]);
+    end_rows(l, prm, z, r, samples_out);
     if (samples_out) {
-      ASC_UNROLL
-      for (int q = 0; q < NQ; q++) samples_out[((size_t)q * NS + s) * B + p] = r[q];
       samples_out[((size_t)(NQ + 0) * NS + s) * B + p] = nclip;
       samples_out[((size_t)(NQ + 1) * NS + s) * B + p] = dmax;
       samples_out[((size_t)(NQ + 2) * NS + s) * B + p] = stretch;
     }
   }
-  bool valid = true;
-  ASC_UNROLL
-  for (int q = 0; q < NQ; q++) valid = valid && finite1(r[q]);
-  wave_record(r, valid, cen, lane, red[wv]);
-  __syncthreads();
-  const int nw = (int)blockDim.x >> 6;
-  for (int i = t; i < NREC; i += (int)blockDim.x) {
-    double a = red[0][i];
-    for (int w = 1; w < nw; w++) {
-      const double o = red[w][i];
-      a = i < R_MIN ? a + o : i < R_MAX ? fmin(a, o) : fmax(a, o);
-    }
-    partial[((size_t)c * NREC + i) * B + p] = a;
-  }
+  reduce_partial(l, r, cen, red, partial);
 }
 
 template <int FORM>
@@ -404,15 +399,6 @@ __global__ __launch_bounds__(SW) void f_disperse_stats(long batch, int K, int nw
   }
 }
 
-struct DisperseWs { double *traj, *fsum, *partial; };
-DisperseWs carve(double *ws, int K, long batch) {
-  DisperseWs w;
-  const size_t B = (size_t)batch;
-  w.traj = ws;
-  w.fsum = w.traj + (size_t)ASCENT_TRAJ_FIELDS * (K + 1) * B;
-  w.partial = w.fsum + (size_t)ASCENT_FLIGHT_ROWS * B;
-  return w;
-}
 int groups_per_problem(int samples) { return (samples + DB - 1) / DB; }
 // below 193 samples a workgroup holds only the wavefronts that fly: whole wavefronts, so the butterflies see 64 lanes
 int threads_per_group(int samples) { return samples >= DB ? DB : (samples + 63) / 64 * 64; }
@@ -420,75 +406,38 @@ int threads_per_group(int samples) { return samples >= DB ? DB : (samples + 63) 
 }  // namespace
 
 size_t disperse_ws_bytes(int K, long batch, int samples) {
-  return ((size_t)ASCENT_TRAJ_FIELDS * (K + 1) + ASCENT_FLIGHT_ROWS + (size_t)groups_per_problem(samples) * NREC) * (size_t)batch * sizeof(double);
+  return flight_ws_bytes(K, batch) + (size_t)groups_per_problem(samples) * NREC * (size_t)batch * sizeof(double);
 }
 
-int disperse_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
-                 const double *dsigma_u, double *dstats, double *dsamples, double *ws) {
-  const DisperseWs w = carve(ws, c.K, c.batch);
-  if (const int rc = flight_fly_only(c, substeps, dblob, w.traj, w.fsum)) return rc;
+template <int FORM>
+static void disperse_launch(const Call &c, DisperseKind kind, dim3 grid, dim3 block, int substeps, int samples, int nwg, long g0,
+                            const DisperseIO &io, const FlightWs &w) {
+  double *partial = w.rest;
+  if (kind == DISPERSE_OPEN)
+    hipLaunchKernelGGL((f_disperse<FORM>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob, w.traj,
+                       w.fsum, io.xi, io.sigma, io.sigma_u, partial, io.samples_out);
+  else if (kind == DISPERSE_GUIDED)
+    hipLaunchKernelGGL((f_disperse_guided<FORM>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob,
+                       w.traj, w.fsum, io.xi, io.sigma, io.sigma_u, io.gain_u, io.gain_t, io.stretch_max, partial, io.samples_out);
+  else
+    hipLaunchKernelGGL((f_disperse_navigated<FORM>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob,
+                       w.traj, w.fsum, io.xi, io.sigma, io.sigma_u, io.gain_u, io.gain_t, io.stretch_max,
+                       NavArgs{io.ff_u, io.ff_t, io.ff_know, io.xi_nav, io.sigma_nav}, partial, io.samples_out);
+}
+
+int disperse_run(const Call &c, DisperseKind kind, int substeps, int samples, const DisperseIO &io, double *ws) {
+  const FlightWs w = flight_ws(ws, c.K, c.batch);      // rest: the partial records
+  if (const int rc = flight_fly_only(c, substeps, io.blob, w.traj, w.fsum)) return rc;
   const int nwg = groups_per_problem(samples);
   const long total = c.batch * nwg;
   for (long g0 = 0; g0 < total; g0 += MAX_GRID) {
     const dim3 grid((unsigned)(total - g0 < MAX_GRID ? total - g0 : MAX_GRID)), block(threads_per_group(samples));
-    if (c.form == 1)
-      hipLaunchKernelGGL((f_disperse<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
-                         w.fsum, dxi, dsigma, dsigma_u, w.partial, dsamples);
-    else
-      hipLaunchKernelGGL((f_disperse<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
-                         w.fsum, dxi, dsigma, dsigma_u, w.partial, dsamples);
+    if (c.form == 1) disperse_launch<1>(c, kind, grid, block, substeps, samples, nwg, g0, io, w);
+    else disperse_launch<0>(c, kind, grid, block, substeps, samples, nwg, g0, io, w);
     ASC_CHK(c.err, c.errlen, hipGetLastError());
   }
   const dim3 gst((unsigned)((c.batch + SW - 1) / SW)), bst(SW);
-  hipLaunchKernelGGL(f_disperse_stats, gst, bst, 0, c.stream, c.batch, c.K, nwg, w.traj, w.fsum, w.partial, dstats);
-  ASC_CHK(c.err, c.errlen, hipGetLastError());
-  return ASCENT_OK;
-}
-
-int disperse_guided_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
-                        const double *dsigma_u, const double *dgain_u, const double *dgain_t, const double *dsmax, double *dstats,
-                        double *dsamples, double *ws) {
-  const DisperseWs w = carve(ws, c.K, c.batch);
-  if (const int rc = flight_fly_only(c, substeps, dblob, w.traj, w.fsum)) return rc;
-  const int nwg = groups_per_problem(samples);
-  const long total = c.batch * nwg;
-  for (long g0 = 0; g0 < total; g0 += MAX_GRID) {
-    const dim3 grid((unsigned)(total - g0 < MAX_GRID ? total - g0 : MAX_GRID)), block(threads_per_group(samples));
-    if (c.form == 1)
-      hipLaunchKernelGGL((f_disperse_guided<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
-                         w.fsum, dxi, dsigma, dsigma_u, dgain_u, dgain_t, dsmax, w.partial, dsamples);
-    else
-      hipLaunchKernelGGL((f_disperse_guided<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
-                         w.fsum, dxi, dsigma, dsigma_u, dgain_u, dgain_t, dsmax, w.partial, dsamples);
-    ASC_CHK(c.err, c.errlen, hipGetLastError());
-  }
-  const dim3 gst((unsigned)((c.batch + SW - 1) / SW)), bst(SW);
-  hipLaunchKernelGGL(f_disperse_stats, gst, bst, 0, c.stream, c.batch, c.K, nwg, w.traj, w.fsum, w.partial, dstats);
-  ASC_CHK(c.err, c.errlen, hipGetLastError());
-  return ASCENT_OK;
-}
-
-int disperse_navigated_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
-                           const double *dsigma_u, const double *dgain_u, const double *dgain_t, const double *dsmax,
-                           const double *dff_u, const double *dff_t, const double *dff_know, const double *dxi_nav,
-                           const double *dsigma_nav, double *dstats, double *dsamples, double *ws) {
-  const DisperseWs w = carve(ws, c.K, c.batch);
-  if (const int rc = flight_fly_only(c, substeps, dblob, w.traj, w.fsum)) return rc;
-  const int nwg = groups_per_problem(samples);
-  const long total = c.batch * nwg;
-  const NavArgs nav = {dff_u, dff_t, dff_know, dxi_nav, dsigma_nav};
-  for (long g0 = 0; g0 < total; g0 += MAX_GRID) {
-    const dim3 grid((unsigned)(total - g0 < MAX_GRID ? total - g0 : MAX_GRID)), block(threads_per_group(samples));
-    if (c.form == 1)
-      hipLaunchKernelGGL((f_disperse_navigated<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
-                         w.fsum, dxi, dsigma, dsigma_u, dgain_u, dgain_t, dsmax, nav, w.partial, dsamples);
-    else
-      hipLaunchKernelGGL((f_disperse_navigated<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, dblob, w.traj,
-                         w.fsum, dxi, dsigma, dsigma_u, dgain_u, dgain_t, dsmax, nav, w.partial, dsamples);
-    ASC_CHK(c.err, c.errlen, hipGetLastError());
-  }
-  const dim3 gst((unsigned)((c.batch + SW - 1) / SW)), bst(SW);
-  hipLaunchKernelGGL(f_disperse_stats, gst, bst, 0, c.stream, c.batch, c.K, nwg, w.traj, w.fsum, w.partial, dstats);
+  hipLaunchKernelGGL(f_disperse_stats, gst, bst, 0, c.stream, c.batch, c.K, nwg, w.traj, w.fsum, w.rest, io.stats);
   ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }

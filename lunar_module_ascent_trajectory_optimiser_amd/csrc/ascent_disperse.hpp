@@ -11,26 +11,24 @@ namespace ascent {
 // records of 73 doubles per problem.  Nothing of size samples * K exists.
 size_t disperse_ws_bytes(int K, long batch, int samples);
 
-// include/ascent.h: ascent_disperse_batch.  Device pointers: c.dp[batch], dblob [21K+10][batch], dxi [24 + K][samples] ([24][samples]
-// with dsigma_u null), dsigma [24][batch], dsigma_u [K][batch] or null, dstats [ASCENT_DISPERSE_STAT_ROWS][batch], dsamples
-// [9][samples][batch] or null, ws of disperse_ws_bytes.  Options already checked by the caller.  Only enqueues on c.stream: f_fly,
-// f_disperse (one launch per 2^22 workgroups) and f_disperse_stats.  Returns ASCENT_OK / ASCENT_E_HIP.
-int disperse_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
-                 const double *dsigma_u, double *dstats, double *dsamples, double *ws);
+// The three dispersion calls of include/ascent.h differ in what they are given, not in what is done with it
+enum DisperseKind { DISPERSE_OPEN = 0 /* ascent_disperse_batch */, DISPERSE_GUIDED /* .._guided_batch */, DISPERSE_NAVIGATED /* .._navigated_batch */ };
 
-// include/ascent.h: ascent_disperse_guided_batch.  As disperse_run, plus dgain_u [7][K][batch], dgain_t [7][batch] or null,
-// dsmax [batch] or null; dsamples [12][samples][batch] or null.  Same workspace, same three enqueues with f_disperse_guided in
-// f_disperse's place.
-int disperse_guided_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
-                        const double *dsigma_u, const double *dgain_u, const double *dgain_t, const double *dsmax, double *dstats,
-                        double *dsamples, double *ws);
+// The arrays of a dispersion call, host or device pointers alike; null where the caller gave none or the kind has none.
+// blob [21K+10][batch], xi [24 + K][samples] ([24][samples] with sigma_u null), sigma [24][batch], sigma_u [K][batch];
+// guided and navigated: gain_u [7][K][batch], gain_t [7][batch], stretch_max [batch];
+// navigated: ff_u [K][batch], ff_t [batch], ff_know [16][batch], xi_nav [ASCENT_NAV_ROWS][samples], sigma_nav [ASCENT_NAV_ROWS][batch];
+// stats [ASCENT_DISPERSE_STAT_ROWS][batch], samples_out [9 (open) | ASCENT_GUIDED_SAMPLE_ROWS][samples][batch].
+struct DisperseIO {
+  const double *blob, *xi, *sigma, *sigma_u;
+  const double *gain_u, *gain_t, *stretch_max;
+  const double *ff_u, *ff_t, *ff_know, *xi_nav, *sigma_nav;
+  double *stats, *samples_out;
+};
 
-// include/ascent.h: ascent_disperse_navigated_batch.  As disperse_guided_run, plus dff_u [K][batch], dff_t [batch], dff_know
-// [16][batch], dxi_nav [ASCENT_NAV_ROWS][samples], dsigma_nav [ASCENT_NAV_ROWS][batch], each or null.  Same workspace, same three
-// enqueues with f_disperse_navigated in f_disperse_guided's place.
-int disperse_navigated_run(const Call &c, int substeps, int samples, const double *dblob, const double *dxi, const double *dsigma,
-                           const double *dsigma_u, const double *dgain_u, const double *dgain_t, const double *dsmax,
-                           const double *dff_u, const double *dff_t, const double *dff_know, const double *dxi_nav,
-                           const double *dsigma_nav, double *dstats, double *dsamples, double *ws);
+// io: device pointers, ws of disperse_ws_bytes.  Options already checked by the caller.  Only enqueues on c.stream: f_fly, the
+// kind's kernel -- f_disperse, f_disperse_guided or f_disperse_navigated, one launch per 2^22 workgroups -- and f_disperse_stats.
+// Returns ASCENT_OK / ASCENT_E_HIP.
+int disperse_run(const Call &c, DisperseKind kind, int substeps, int samples, const DisperseIO &io, double *ws);
 
 }  // namespace ascent

@@ -16,6 +16,8 @@
 //          takes NLP t % PB and the steps k = t / PB + 1, + LB/PB, ...  Owns summary rows 6..8: the maxima over the steps are
 //          reduced over the lanes of one NLP with cross-lane shuffles, then over the waves in LDS, in a fixed order (results
 //          depend on the batch size only through PB, never on timing).
+// flight_ws (ascent_flight.hpp) is the head of every workspace that starts with a fly-out; finite1 and max_nan, the family's two
+// NaN rules, are in ascent_flight_dev.hpp.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cmath>
@@ -98,7 +100,6 @@ ASC_DEV void max_at(double &v, int &k, double w, int l) {         // (v, k) <- t
   }
   if (take) { v = w; k = l; }
 }
-ASC_DEV double max_nan(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
 
 template <int FORM>
 __global__ __launch_bounds__(LB) void f_local(const ascent_params *__restrict__ P, long batch, int K, int pb, int substeps,

@@ -17,4 +17,18 @@ int flight_run(const Call &c, int substeps, const double *dblob, double *dtraj, 
 // round of the trim (ascent_trim.hip).
 int flight_fly_only(const Call &c, int substeps, const double *dblob, double *dtraj, double *dsummary);
 
+// The head of every workspace that starts with a fly-out (the flight Jacobian, the trim, the guidance gains, the dispersion):
+// flight_fly_only's trajectory [ASCENT_TRAJ_FIELDS (K + 1)][batch], its summary [ASCENT_FLIGHT_ROWS][batch], then the caller's own.
+struct FlightWs { double *traj, *fsum, *rest; };
+inline FlightWs flight_ws(double *ws, int K, long batch) {
+  FlightWs w;
+  w.traj = ws;
+  w.fsum = w.traj + (size_t)ASCENT_TRAJ_FIELDS * (K + 1) * (size_t)batch;
+  w.rest = w.fsum + (size_t)ASCENT_FLIGHT_ROWS * (size_t)batch;
+  return w;
+}
+inline size_t flight_ws_bytes(int K, long batch) {
+  return ((size_t)ASCENT_TRAJ_FIELDS * (K + 1) + ASCENT_FLIGHT_ROWS) * (size_t)batch * sizeof(double);
+}
+
 }  // namespace ascent

@@ -1,6 +1,7 @@
 // Device helpers of the flight verification (ascent_flight.hip) shared with the flight Jacobian and the trim
 // (ascent_trim.hip) and the dispersion (ascent_disperse.hip): the substep rule, the right-hand side, one RK4 collocation step,
-// the two-body apsides, a node of a flown trajectory and the wavefront sum.
+// the two-body apsides, a node of a flown trajectory, the wavefront sum, and the two NaN rules every family member follows:
+// finite1 and the NaN-propagating maximum.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -9,11 +10,15 @@
 
 namespace ascent {
 
+ASC_DEV bool finite1(double a) { return fabs(a) <= 1.79769313486231570815e308; }      // false for NaN, +-inf
+// the maximum that a NaN wins (fmax drops it): an unconverged blob shows as NaN, not as its largest finite value
+ASC_DEV double max_nan(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
+
 // substeps per collocation step: the caller's, or (0) dt / 0.5 s rounded up, 1 .. ASCENT_FLIGHT_MAX_SUBSTEPS; whatever the
 // blob holds, the loops below are bounded by it
 ASC_DEV int flight_substeps(double dt, int substeps) {
   if (substeps > 0) return substeps;
-  if (!(fabs(dt) <= 1.79769313486231570815e308)) return 1;      // NaN, +-inf
+  if (!finite1(dt)) return 1;
   const double q = ceil(dt / 0.5);
   return q >= (double)ASCENT_FLIGHT_MAX_SUBSTEPS ? ASCENT_FLIGHT_MAX_SUBSTEPS : q >= 1.0 ? (int)q : 1;
 }

@@ -16,13 +16,15 @@
 //          exactly symmetric;  lane q < 9: row q of Lambda <- Lambda (Phi - g K' - gamma k_t'), Lambda g to jac_u, Lambda Gamma
 //          into the accumulators -- j_jac's sweep with the gain terms taken off.
 //          The phases of one wavefront are ordered by LDS's in-order execution; wave_sync keeps the compiler from reordering them.
-//   epilogue   j_jac's chain rule, restated here (j_jac itself is left as it is: the trim depends on its bits).
+//   The two ends of the Jacobian part are j_jac's own functions (ascent_tangent_dev.hpp): lambda_apsis_rows starts Lambda_K,
+//   jac_columns is the epilogue's chain rule; the trim depends on j_jac's bits, and both kernels keep the parent text's.
 // The order of every addition is fixed: a problem gives the same bits alone as inside any batch.
 //
 // g_gains_ff  the same sweep with a thrust (parameter) feed-forward (include/ascent.h: ascent_guidance_feedforward): one body,
 //          gains_body<FORM, FF>, so the P-part above is one source text and its gains are g_gains' bits.  The deviation state is
 //          augmented by one constant scalar theta along the caller's direction d of the 16 fields: step forcing pi_k = Gamma_k d
-//          through the epilogue's chain rule (eight wave-uniform coefficients), formed by every group from its own tangent
+//          through the transpose of the epilogue's chain rule (tangent_coefficients, beside jac_columns: eight wave-uniform
+//          coefficients), formed by every group from its own tangent
 //          columns when the records are staged -- a butterfly over the 16 lanes of the group --, 7 doubles per step in LDS.
 //          The value function gains the column p (7 doubles in LDS); per step, beside the phases above:
 //   A      lanes 49..55 also: a = P pi + p, a second chain inside the loop that forms P g
@@ -49,9 +51,6 @@ namespace {
 
 constexpr int GW = 64;                     // the sweeping wavefront
 constexpr int W_QE3 = 0, W_RU = 3, W_RT = 4, W_SMAX = 5;      // rows of weights [6][batch]
-
-ASC_DEV bool finite1(double a) { return fabs(a) <= 1.79769313486231570815e308; }
-ASC_DEV double max_nan2(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
 
 // orders the LDS traffic of the phases of one wavefront (the hardware executes a wavefront's LDS instructions in order)
 ASC_DEV void wave_sync() {
@@ -89,7 +88,7 @@ ASC_DEV void gains_body(const ascent_params *__restrict__ P, long batch, int K, 
   const double ru = weights[(size_t)W_RU * B + p], rt = weights[(size_t)W_RT * B + p], smax = weights[(size_t)W_SMAX * B + p];
   const int pi = t < 49 ? t / 7 : 0, pj = t % 7;      // lane (pi, pj) of P; every lane: column pj of a gain row
 
-  // pi_k = R[:, C_DT .. C_MRATE] . coef: the epilogue's chain rule applied to the direction; this lane's coefficient
+  // pi_k = R[:, C_DT .. C_MRATE] . coef: the epilogue's chain rule transposed onto the direction; this lane's coefficient
   double cf = 0.0;
   bool dok = true;
   if constexpr (FF) {
@@ -100,22 +99,15 @@ ASC_DEV void gains_body(const ascent_params *__restrict__ P, long batch, int K, 
       ASC_UNROLL
       for (int i = 0; i < 16; i++) dok = dok && finite1(ff_know[(size_t)i * B + p]);
     }
-    const double S = prm.r_peri, S3 = S * S * S;
-    coef[0] = dd[11] * (tf / K);
-    coef[1 + ACC_RHO0] = dd[2] / S - dd[9] * prm.R0 / (S * S);
-    coef[1 + ACC_GAM] = dd[0] * prm.M / S3 + dd[1] * prm.G / S3 - dd[9] * 3.0 * d.gam / S;
-    coef[1 + ACC_THR] = dd[3] / S - dd[9] * d.thr / S;
-    coef[1 + ACC_M0] = dd[4];
-    coef[1 + ACC_MS] = dd[7];
-    coef[C_ALPHA - C_DT] = FORM == 1 ? dd[12] : dd[8] / 3.0;
-    coef[C_MRATE - C_DT] = dd[5] / prm.fuel_mass - dd[6] * d.mrate / prm.fuel_mass;
+    tangent_coefficients<FORM>(prm, d, tf, K, dd, coef);
     ASC_UNROLL
     for (int a = 0; a < NACC; a++) cf = col == C_DT + a ? coef[a] : cf;
   }
 
-  double dirG = 0.0, dirM = 0.0, dirR0 = 0.0, dirS = 0.0, nf = 0.0, gmax = 0.0, tmax = 0.0, fmax_u = 0.0, fmax_t = 0.0;
+  ApsisDirect dir = {0.0, 0.0, 0.0, 0.0};
+  double nf = 0.0, gmax = 0.0, tmax = 0.0, fmax_u = 0.0, fmax_t = 0.0;
   if (t < GW) {
-    double zK[7], gp[5], ga[5], q[3];
+    double zK[7], q[3];
     load_node(tr, B, nt, K, zK);
     ASC_UNROLL
     for (int i = 0; i < 3; i++) q[i] = weights[(size_t)(W_QE3 + i) * B + p];
@@ -143,20 +135,11 @@ ASC_DEV void gains_body(const ascent_params *__restrict__ P, long batch, int K, 
     }
     // Lambda_K = I / grad apsides, as j_jac
     if (jac) {
-      apsides_grad(prm, zK[IX], zK[IY], zK[IVX], zK[IVY], gp, ga);
+      double L[7];
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) L[i] = t == i ? 1.0 : 0.0;
+      lambda_apsis_rows(prm, zK, t, L, dir);
       if (t < JROWS) {
-        double L[7];
-        ASC_UNROLL
-        for (int i = 0; i < 7; i++) L[i] = t == i ? 1.0 : 0.0;
-        if (t == 7 || t == 8) {
-          const double *gq = t == 7 ? gp : ga;
-          const double S = prm.r_peri;
-          L[IX] = S * gq[0]; L[IY] = S * gq[1]; L[IVX] = S * gq[2]; L[IVY] = S * gq[3];
-          dirS = zK[IX] * gq[0] + zK[IY] * gq[1] + zK[IVX] * gq[2] + zK[IVY] * gq[3];
-          dirR0 = gq[1] - 1.0;
-          dirG = prm.M * gq[4];
-          dirM = prm.G * gq[4];
-        }
         ASC_UNROLL
         for (int i = 0; i < 7; i++) Ls[t * 7 + i] = L[i];
         ASC_UNROLL
@@ -275,8 +258,8 @@ ASC_DEV void gains_body(const ascent_params *__restrict__ P, long batch, int K, 
             ff_u[(size_t)kk * B + p] = fu;
             if (kk + 1 == K) ff_t[p] = ft;
           }
-          fmax_u = max_nan2(fmax_u, fabs(fu));
-          fmax_t = max_nan2(fmax_t, fabs(ft));
+          fmax_u = max_nan(fmax_u, fabs(fu));
+          fmax_t = max_nan(fmax_t, fabs(ft));
           // p <- Phi' a - G' S f: every lane holds column pj of G and of a' Phi; lanes 49..55 store theirs (p is read in A only)
           if (t >= 49 && t < 56) pv[pj] = ep - (g1 * (s11 * fu + s12 * ft) + g2 * (s12 * fu + s22 * ft));
         }
@@ -285,8 +268,8 @@ ASC_DEV void gains_body(const ascent_params *__restrict__ P, long batch, int K, 
           Gs[7 + t] = g2;
           gain_u[((size_t)t * K + kk) * B + p] = g1;
           if (kk + 1 == K) gain_t[(size_t)t * B + p] = g2;
-          gmax = max_nan2(gmax, fabs(g1));
-          tmax = max_nan2(tmax, fabs(g2));
+          gmax = max_nan(gmax, fabs(g1));
+          tmax = max_nan(tmax, fabs(g2));
         }
         wave_sync();
         // C
@@ -352,7 +335,7 @@ ASC_DEV void gains_body(const ascent_params *__restrict__ P, long batch, int K, 
     gmax = t < 7 ? gmax : 0.0;
     tmax = t < 7 ? tmax : 0.0;
     ASC_UNROLL
-    for (int off = 4; off >= 1; off >>= 1) { gmax = max_nan2(gmax, __shfl_xor(gmax, off)); tmax = max_nan2(tmax, __shfl_xor(tmax, off)); }
+    for (int off = 4; off >= 1; off >>= 1) { gmax = max_nan(gmax, __shfl_xor(gmax, off)); tmax = max_nan(tmax, __shfl_xor(tmax, off)); }
     if (t == 0) {
       summary[(size_t)0 * B + p] = frozen ? 2.0 : 0.0;
       summary[(size_t)1 * B + p] = nf;
@@ -384,29 +367,8 @@ ASC_DEV void gains_body(const ascent_params *__restrict__ P, long batch, int K, 
   }
 
   if (jac && t < JROWS) {
-    const double S = prm.r_peri, R0 = prm.R0;
-    const double *A = As + t * NACC;
-    const double aDT = A[0], aRHO0 = A[1 + ACC_RHO0], aGAM = A[1 + ACC_GAM], aTHR = A[1 + ACC_THR], aM0 = A[1 + ACC_M0],
-                 aMS = A[1 + ACC_MS], aAL = A[C_ALPHA - C_DT], aMR = A[C_MRATE - C_DT];
     double o[JCOLS];
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) o[i] = Ls[t * 7 + i];
-    const double S3 = S * S * S;
-    o[7 + 0] = aGAM * prm.M / S3 + dirG;                              // G
-    o[7 + 1] = aGAM * prm.G / S3 + dirM;                              // M
-    o[7 + 2] = aRHO0 / S + dirR0;                                     // R0
-    o[7 + 3] = aTHR / S;                                              // Ft
-    o[7 + 4] = aM0;                                                   // M0
-    o[7 + 5] = aMR / prm.fuel_mass;                                   // mdot
-    o[7 + 6] = -aMR * d.mrate / prm.fuel_mass;                        // fuel_mass
-    o[7 + 7] = aMS;                                                   // mass_scalar
-    o[7 + 8] = FORM == 1 ? 0.0 : aAL / 3.0;                           // ang_acc_max
-    o[7 + 9] = -aRHO0 * R0 / (S * S) - 3.0 * aGAM * d.gam / S - aTHR * d.thr / S + dirS;     // r_peri
-    o[7 + 10] = 0.0;                                                  // r_apo
-    o[7 + 11] = aDT * (tf / K);                                       // T_scale
-    o[7 + 12] = FORM == 1 ? aAL : 0.0;                                // angle_ub
-    o[7 + 13] = 0.0; o[7 + 14] = 0.0; o[7 + 15] = 0.0;                // tf_lb, tf_ub, dcost
-    o[23] = aDT * (d.T / K);                                          // t_f
+    jac_columns<FORM>(prm, d, tf, K, Ls + t * 7, As + t * NACC, dir, o);
     if constexpr (FF) {                                               // theta-hat = w . dp steers against E_q
       const double *N = Ns + t * NNAV;
       const double eq = N[7];
@@ -448,33 +410,22 @@ __global__ __launch_bounds__(JB) void g_gains_ff(const ascent_params *__restrict
 
 size_t gains_ws_bytes(int K, long batch) { return jac_ws_bytes(K, batch); }
 
-int gains_run(const Call &c, int substeps, const double *dblob, const double *dweights, double *dgain_u, double *dgain_t,
-              double *dsummary, double *djac, double *djac_u, double *ws) {
-  double *traj = ws, *fsum = ws + (size_t)ASCENT_TRAJ_FIELDS * (c.K + 1) * (size_t)c.batch;      // the carve of jac_run
-  if (const int rc = flight_fly_only(c, substeps, dblob, traj, fsum)) return rc;
+template <int FORM>
+static void gains_launch(const Call &c, int substeps, const GainsIO &io, const double *traj) {
   const dim3 grid((unsigned)c.batch), block(JB);
-  if (c.form == 1)
-    hipLaunchKernelGGL((g_gains<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, traj, dweights, dgain_u, dgain_t,
-                       dsummary, djac, djac_u);
+  if (io.ff_dir)
+    hipLaunchKernelGGL((g_gains_ff<FORM>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, io.blob, traj, io.weights, io.gain_u,
+                       io.gain_t, io.summary, io.jac, io.jac_u, io.ff_dir, io.ff_know, io.ff_u, io.ff_t, io.jac_nav);
   else
-    hipLaunchKernelGGL((g_gains<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, traj, dweights, dgain_u, dgain_t,
-                       dsummary, djac, djac_u);
-  ASC_CHK(c.err, c.errlen, hipGetLastError());
-  return ASCENT_OK;
+    hipLaunchKernelGGL((g_gains<FORM>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, io.blob, traj, io.weights, io.gain_u,
+                       io.gain_t, io.summary, io.jac, io.jac_u);
 }
 
-int gains_ff_run(const Call &c, int substeps, const double *dblob, const double *dweights, const double *dff_dir,
-                 const double *dff_know, double *dgain_u, double *dgain_t, double *dff_u, double *dff_t, double *dsummary,
-                 double *djac, double *djac_u, double *djac_nav, double *ws) {
-  double *traj = ws, *fsum = ws + (size_t)ASCENT_TRAJ_FIELDS * (c.K + 1) * (size_t)c.batch;
-  if (const int rc = flight_fly_only(c, substeps, dblob, traj, fsum)) return rc;
-  const dim3 grid((unsigned)c.batch), block(JB);
-  if (c.form == 1)
-    hipLaunchKernelGGL((g_gains_ff<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, traj, dweights, dgain_u, dgain_t,
-                       dsummary, djac, djac_u, dff_dir, dff_know, dff_u, dff_t, djac_nav);
-  else
-    hipLaunchKernelGGL((g_gains_ff<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, dblob, traj, dweights, dgain_u, dgain_t,
-                       dsummary, djac, djac_u, dff_dir, dff_know, dff_u, dff_t, djac_nav);
+int gains_run(const Call &c, int substeps, const GainsIO &io, double *ws) {
+  const FlightWs w = flight_ws(ws, c.K, c.batch);
+  if (const int rc = flight_fly_only(c, substeps, io.blob, w.traj, w.fsum)) return rc;
+  if (c.form == 1) gains_launch<1>(c, substeps, io, w.traj);
+  else gains_launch<0>(c, substeps, io, w.traj);
   ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }

@@ -11,18 +11,18 @@ namespace ascent {
 // step records, P and Lambda live in LDS only.
 size_t gains_ws_bytes(int K, long batch);
 
-// include/ascent.h: ascent_guidance_gains.  Device pointers: c.dp[batch], dblob [21K+10][batch], dweights [6][batch], dgain_u
-// [7][K][batch], dgain_t [7][batch], dsummary [ASCENT_GUIDE_ROWS][batch], djac [9][24][batch] and djac_u [9][K][batch] both or
-// neither, ws of gains_ws_bytes.  Options already checked by the caller.  Only enqueues two kernels on c.stream (f_fly, g_gains).
-// Returns ASCENT_OK / ASCENT_E_HIP.
-int gains_run(const Call &c, int substeps, const double *dblob, const double *dweights, double *dgain_u, double *dgain_t,
-              double *dsummary, double *djac, double *djac_u, double *ws);
+// The arrays of ascent_guidance_gains and ascent_guidance_feedforward (include/ascent.h), host or device pointers alike.
+// blob [21K+10][batch], weights [6][batch], gain_u [7][K][batch], gain_t [7][batch], summary [ASCENT_GUIDE_ROWS |
+// ASCENT_GUIDE_FF_ROWS][batch], jac [9][24][batch] or null, jac_u [9][K][batch] or null (only with jac).  The feed-forward call
+// (ff_dir not null) adds ff_dir [16][batch], ff_know [16][batch] or null (needed with jac), ff_u [K][batch], ff_t [batch],
+// jac_nav [9][ASCENT_NAV_ROWS][batch] or null (only with jac); all five are null in a gains call.
+struct GainsIO {
+  const double *blob, *weights, *ff_dir, *ff_know;
+  double *gain_u, *gain_t, *ff_u, *ff_t, *summary, *jac, *jac_u, *jac_nav;
+};
 
-// include/ascent.h: ascent_guidance_feedforward.  As gains_run, plus dff_dir [16][batch], dff_know [16][batch] or null (needed
-// with djac), dff_u [K][batch], dff_t [batch], dsummary [ASCENT_GUIDE_FF_ROWS][batch], djac_nav [9][ASCENT_NAV_ROWS][batch] or null
-// (only with djac).  Same workspace; enqueues f_fly and g_gains_ff.
-int gains_ff_run(const Call &c, int substeps, const double *dblob, const double *dweights, const double *dff_dir,
-                 const double *dff_know, double *dgain_u, double *dgain_t, double *dff_u, double *dff_t, double *dsummary,
-                 double *djac, double *djac_u, double *djac_nav, double *ws);
+// io: device pointers, ws of gains_ws_bytes.  Options already checked by the caller.  Only enqueues two kernels on c.stream:
+// f_fly, then g_gains, or g_gains_ff where io.ff_dir is given.  Returns ASCENT_OK / ASCENT_E_HIP.
+int gains_run(const Call &c, int substeps, const GainsIO &io, double *ws);
 
 }  // namespace ascent

@@ -11,9 +11,13 @@
 //   dense blocks d_* / pc_*         ascent_dense.hpp (ascent_dense.hip, ascent_blocktri.hip)
 //   split pipeline q_*              ascent_pipeline.hpp (ascent_pipeline.hip)
 //   fused k_solve                   ascent_fused.hpp (ascent_fused.hip)
-// the post-optimal sensitivity s_sens, ascent_sens.hpp (ascent_sens.hip), and the flight verification f_fly / f_local,
-// ascent_flight.hpp (ascent_flight.hip), and the flight Jacobian and trim j_jac / t_update / t_final, ascent_trim.hpp
-// (ascent_trim.hip).
+// The calls on a solution blob after the solve share one host path, BlobCall below (checks, device lock, the analysis workspace
+// of the device, staging, the Call and the staged blob); each states only its own checks, its buffers and its run function:
+//   post-optimal sensitivity s_sens                       ascent_sens.hpp (ascent_sens.hip)
+//   flight verification f_fly / f_local                   ascent_flight.hpp (ascent_flight.hip)
+//   flight Jacobian and trim j_jac / t_update / t_final   ascent_trim.hpp (ascent_trim.hip)
+//   guidance gains g_gains / g_gains_ff                   ascent_guide.hpp (ascent_guide.hip), one GainsIO for both calls
+//   dispersion f_disperse / _guided / _navigated          ascent_disperse.hpp (ascent_disperse.hip), one DisperseIO for all three
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -741,59 +745,19 @@ int ascent_coast_batch(const ascent_params *p, int64_t batch, const double *fina
   return st.finish();
 }
 
-int ascent_param_sensitivity(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
-                             double *grad_out, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_options(p, batch, o);
-  if (rc) return rc;
-  if (!sol_blob || !grad_out) { snprintf(g_err, sizeof g_err, "null solution blob or output pointer"); return ASCENT_E_ARG; }
-  if ((rc = check_solvable(p, batch, o, ptr_is_device)) || (rc = check_device(device_id))) return rc;
-  std::lock_guard<std::mutex> lock(g_mu[device_id]);
-  HIPCHK(hipSetDevice(device_id));
-  hipStream_t stream = (hipStream_t)stream_;
-  Staging st(stream, ptr_is_device);
-  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
-  const double *db = st.in(sol_blob, (21 * (size_t)c.K + NSC) * batch);
-  double *dg = st.out(grad_out, (size_t)16 * batch);
-  if ((rc = st.failed()) || (rc = sens_run(c, o->terminal, db, dg))) return rc;
-  return st.finish();
-}
-
-namespace {
-int check_substeps(int32_t substeps) {
-  if (substeps < 0 || substeps > ASCENT_FLIGHT_MAX_SUBSTEPS) { snprintf(g_err, sizeof g_err, "substeps out of range (0 = automatic, 1 .. %d)", ASCENT_FLIGHT_MAX_SUBSTEPS); return ASCENT_E_ARG; }
-  return 0;
-}
-}  // namespace
-
-int ascent_fly_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
-                     double *flown_traj, double *local_err, double *summary, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_options(p, batch, o);
-  if (rc) return rc;
-  if (!sol_blob || !summary) { snprintf(g_err, sizeof g_err, "null solution blob or summary pointer"); return ASCENT_E_ARG; }
-  if ((rc = check_substeps(substeps)) || (rc = check_solvable(p, batch, o, ptr_is_device)) || (rc = check_device(device_id))) return rc;
-  std::lock_guard<std::mutex> lock(g_mu[device_id]);
-  HIPCHK(hipSetDevice(device_id));
-  hipStream_t stream = (hipStream_t)stream_;
-  Staging st(stream, ptr_is_device);
-  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
-  const double *db = st.in(sol_blob, (21 * (size_t)c.K + NSC) * batch);
-  double *dt = st.out(flown_traj, (size_t)ASCENT_TRAJ_FIELDS * o->n_nodes * batch), *dl = st.out(local_err, (size_t)7 * c.K * batch);
-  double *ds = st.out(summary, (size_t)ASCENT_FLIGHT_ROWS * batch);
-  if ((rc = st.failed()) || (rc = flight_run(c, substeps, db, dt, dl, ds))) return rc;
-  return st.finish();
-}
-
 // ---------------------------------------------------------------------------------------------
-// Flight Jacobian and trim (ascent_trim.hip).  Their device workspace is one buffer per device, apart from the solver's: a
-// call on another stream than its predecessor waits for the predecessor's last kernel (an event) before it reuses the buffer;
-// growing it frees the old one, which waits for the device.
+// The calls on a solution blob after the solve: sensitivity, flight, flight Jacobian, trim, dispersion, guidance gains.
+//
+// All but the first two work in the analysis workspace of the device: one buffer per device, apart from the solver's.  A call on
+// another stream than its predecessor waits for the predecessor's last kernel (an event) before it reuses the buffer; growing it
+// frees the old one, which waits for the device.
 // ---------------------------------------------------------------------------------------------
 namespace {
-struct TrimDeviceWs { double *ws = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool used = false; };
-TrimDeviceWs g_trim_ws[MAX_DEV];
+struct AnalysisWs { double *ws = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool used = false; };
+AnalysisWs g_analysis_ws[MAX_DEV];
 
-int trim_ws_claim(int dev, size_t bytes, hipStream_t stream, double **out) {      // (under g_mu[dev])
-  TrimDeviceWs &w = g_trim_ws[dev];
+int analysis_ws_claim(int dev, size_t bytes, hipStream_t stream, double **out) {      // (under g_mu[dev])
+  AnalysisWs &w = g_analysis_ws[dev];
   if (!w.ev) HIPCHK(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
   if (w.bytes < bytes) {
     if (w.ws) HIPCHK(hipFree(w.ws));
@@ -807,178 +771,233 @@ int trim_ws_claim(int dev, size_t bytes, hipStream_t stream, double **out) {    
   *out = w.ws;
   return 0;
 }
-int trim_ws_release(int dev, hipStream_t stream) {
-  TrimDeviceWs &w = g_trim_ws[dev];
+int analysis_ws_release(int dev, hipStream_t stream) {
+  AnalysisWs &w = g_analysis_ws[dev];
   HIPCHK(hipEventRecord(w.ev, stream));
   w.used = true;
   return 0;
 }
 
-// what ascent_fly_batch refuses, plus terminal = 2
-int check_flight_like(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
-                      int ptr_is_device) {
-  int rc = check_options(p, batch, o);
+int check_substeps(int32_t substeps) {
+  if (substeps < 0 || substeps > ASCENT_FLIGHT_MAX_SUBSTEPS) { snprintf(g_err, sizeof g_err, "substeps out of range (0 = automatic, 1 .. %d)", ASCENT_FLIGHT_MAX_SUBSTEPS); return ASCENT_E_ARG; }
+  return 0;
+}
+int check_samples(int32_t samples) {
+  if (samples < 1 || samples > ASCENT_DISPERSE_MAX_SAMPLES) { snprintf(g_err, sizeof g_err, "samples out of range (1 .. %d)", ASCENT_DISPERSE_MAX_SAMPLES); return ASCENT_E_ARG; }
+  return 0;
+}
+
+// What the nine entry points below share, in the order their defects have always been reported.  An entry point puts its own
+// null and range checks between the steps, then names its buffers (st.in / st.out) and its run function:
+//   options()               check_options
+//   solvable()              check_solvable
+//   flight_like(substeps)   both, and between them: the blob, the substep range, terminal 2 refused
+//   open(device_id, bytes)  the device, its lock, the analysis workspace (bytes > 0), the Call and the staged blob
+//   close()                 after the run function: the workspace released and the staging finished
+class BlobCall {
+ public:
+  BlobCall(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, void *stream, int ptr_is_device)
+      : p_(p), batch_(batch), o_(o), blob_(sol_blob), device_(ptr_is_device), stream_((hipStream_t)stream), st(stream_, ptr_is_device) {}
+  int options() { return check_options(p_, batch_, o_); }
+  int solvable() { return check_solvable(p_, batch_, o_, device_); }
+  int flight_like(int32_t substeps) {      // what ascent_fly_batch refuses, plus terminal = 2
+    int rc = options();
+    if (rc) return rc;
+    if (!blob_) { snprintf(g_err, sizeof g_err, "null solution blob"); return ASCENT_E_ARG; }
+    if ((rc = check_substeps(substeps))) return rc;
+    if (o_->terminal == 2) { snprintf(g_err, sizeof g_err, "terminal 2 is not supported by the flight Jacobian and the trim (its two conditions are nearly dependent where burnout sits at an apsis)"); return ASCENT_E_ARG; }
+    return solvable();
+  }
+  int open(int device_id, size_t ws_bytes) {
+    int rc = check_device(device_id);
+    if (rc) return rc;
+    dev_ = device_id;
+    lock_ = std::unique_lock<std::mutex>(g_mu[dev_]);
+    HIPCHK(hipSetDevice(dev_));
+    K = o_->n_nodes - 1;
+    if (ws_bytes && (rc = analysis_ws_claim(dev_, ws_bytes, stream_, &ws))) return rc;
+    c = call_of(st.in(p_, (size_t)batch_), batch_, o_, stream_);
+    blob = st.in(blob_, (21 * (size_t)K + NSC) * batch_);
+    return 0;
+  }
+  int close() {
+    if (ws)
+      if (const int rc = analysis_ws_release(dev_, stream_)) return rc;
+    return st.finish();
+  }
+
+ private:
+  const ascent_params *p_;
+  int64_t batch_;
+  const ascent_opts *o_;
+  const double *blob_;
+  int device_, dev_ = -1;
+  hipStream_t stream_;
+  std::unique_lock<std::mutex> lock_;      // declared before st: the staging frees its copies while the device is still locked
+
+ public:
+  Staging st;
+  Call c{};
+  int K = 0;
+  const double *blob = nullptr;      // the staged solution blob
+  double *ws = nullptr;              // the analysis workspace, where the call claimed one
+};
+
+// ascent_disperse_batch, ascent_disperse_guided_batch and ascent_disperse_navigated_batch: io holds the caller's pointers
+int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, int32_t samples, DisperseKind kind,
+                  DisperseIO io, int device_id, void *stream_, int ptr_is_device) {
+  BlobCall b(p, batch, o, io.blob, stream_, ptr_is_device);
+  int rc = b.options();
   if (rc) return rc;
-  if (!sol_blob) { snprintf(g_err, sizeof g_err, "null solution blob"); return ASCENT_E_ARG; }
-  if ((rc = check_substeps(substeps))) return rc;
-  if (o->terminal == 2) { snprintf(g_err, sizeof g_err, "terminal 2 is not supported by the flight Jacobian and the trim (its two conditions are nearly dependent where burnout sits at an apsis)"); return ASCENT_E_ARG; }
-  return check_solvable(p, batch, o, ptr_is_device);
+  if (kind == DISPERSE_OPEN) {
+    if (!io.blob || !io.xi || !io.sigma || !io.stats) { snprintf(g_err, sizeof g_err, "null solution blob, xi, sigma or stats_out"); return ASCENT_E_ARG; }
+  } else if (!io.blob || !io.xi || !io.sigma || !io.gain_u || !io.stats) { snprintf(g_err, sizeof g_err, "null solution blob, xi, sigma, gain_u or stats_out"); return ASCENT_E_ARG; }
+  if ((rc = check_samples(samples))) return rc;
+  if ((io.xi_nav != nullptr) != (io.sigma_nav != nullptr)) { snprintf(g_err, sizeof g_err, "xi_nav and sigma_nav come together"); return ASCENT_E_ARG; }
+  if (io.ff_know && !io.ff_u) { snprintf(g_err, sizeof g_err, "ff_know needs ff_u"); return ASCENT_E_ARG; }
+  if ((rc = check_substeps(substeps)) || (rc = b.solvable()) || (rc = b.open(device_id, disperse_ws_bytes(o->n_nodes - 1, (long)batch, samples)))) return rc;
+  Staging &st = b.st;
+  const size_t K = (size_t)b.K, B = (size_t)batch, S = (size_t)samples;
+  io.blob = b.blob;
+  io.xi = st.in(io.xi, (ASCENT_DISPERSE_COLS + (io.sigma_u ? K : 0)) * S);
+  io.sigma = st.in(io.sigma, ASCENT_DISPERSE_COLS * B);
+  io.sigma_u = st.in(io.sigma_u, K * B);
+  io.gain_u = st.in(io.gain_u, 7 * K * B);
+  io.gain_t = st.in(io.gain_t, 7 * B);
+  io.stretch_max = st.in(io.stretch_max, B);
+  io.ff_u = st.in(io.ff_u, K * B);
+  io.ff_t = st.in(io.ff_t, B);
+  io.ff_know = st.in(io.ff_know, 16 * B);
+  io.xi_nav = st.in(io.xi_nav, ASCENT_NAV_ROWS * S);
+  io.sigma_nav = st.in(io.sigma_nav, ASCENT_NAV_ROWS * B);
+  io.stats = st.out(io.stats, ASCENT_DISPERSE_STAT_ROWS * B);
+  io.samples_out = st.out(io.samples_out, (kind == DISPERSE_OPEN ? ASCENT_DISPERSE_ROWS : ASCENT_GUIDED_SAMPLE_ROWS) * S * B);
+  if ((rc = b.st.failed()) || (rc = disperse_run(b.c, kind, substeps, samples, io, b.ws))) return rc;
+  return b.close();
+}
+
+// ascent_guidance_gains and ascent_guidance_feedforward (ff): io holds the caller's pointers
+int gains_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, bool ff, GainsIO io, int device_id,
+               void *stream_, int ptr_is_device) {
+  BlobCall b(p, batch, o, io.blob, stream_, ptr_is_device);
+  int rc = b.flight_like(substeps);
+  if (rc) return rc;
+  if (!io.weights || !io.gain_u || !io.gain_t || !io.summary) { snprintf(g_err, sizeof g_err, "null weights, gain_u_out, gain_t_out or summary_out"); return ASCENT_E_ARG; }
+  if (ff && (!io.ff_dir || !io.ff_u || !io.ff_t)) { snprintf(g_err, sizeof g_err, "null ff_dir, ff_u_out or ff_t_out"); return ASCENT_E_ARG; }
+  if (io.jac_u && !io.jac) { snprintf(g_err, sizeof g_err, "jac_u_cl_out needs jac_cl_out"); return ASCENT_E_ARG; }
+  if (io.jac_nav && !io.jac) { snprintf(g_err, sizeof g_err, "jac_nav_out needs jac_cl_out"); return ASCENT_E_ARG; }
+  if (ff && io.jac && !io.ff_know) { snprintf(g_err, sizeof g_err, "jac_cl_out needs ff_know"); return ASCENT_E_ARG; }
+  if ((rc = b.open(device_id, gains_ws_bytes(o->n_nodes - 1, (long)batch)))) return rc;
+  Staging &st = b.st;
+  const size_t K = (size_t)b.K, B = (size_t)batch;
+  io.blob = b.blob;
+  io.weights = st.in(io.weights, 6 * B);
+  io.ff_dir = st.in(io.ff_dir, 16 * B);
+  io.ff_know = st.in(io.ff_know, 16 * B);
+  io.gain_u = st.out(io.gain_u, 7 * K * B);
+  io.gain_t = st.out(io.gain_t, 7 * B);
+  io.ff_u = st.out(io.ff_u, K * B);
+  io.ff_t = st.out(io.ff_t, B);
+  io.summary = st.out(io.summary, (ff ? ASCENT_GUIDE_FF_ROWS : ASCENT_GUIDE_ROWS) * B);
+  io.jac = st.out(io.jac, 9 * 24 * B);
+  io.jac_u = st.out(io.jac_u, 9 * K * B);
+  io.jac_nav = st.out(io.jac_nav, 9 * ASCENT_NAV_ROWS * B);
+  if ((rc = b.st.failed()) || (rc = gains_run(b.c, substeps, io, b.ws))) return rc;
+  return b.close();
 }
 }  // namespace
 
+int ascent_param_sensitivity(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                             double *grad_out, int device_id, void *stream_, int ptr_is_device) {
+  BlobCall b(p, batch, o, sol_blob, stream_, ptr_is_device);
+  int rc = b.options();
+  if (rc) return rc;
+  if (!sol_blob || !grad_out) { snprintf(g_err, sizeof g_err, "null solution blob or output pointer"); return ASCENT_E_ARG; }
+  if ((rc = b.solvable()) || (rc = b.open(device_id, 0))) return rc;
+  double *dg = b.st.out(grad_out, (size_t)16 * batch);
+  if ((rc = b.st.failed()) || (rc = sens_run(b.c, o->terminal, b.blob, dg))) return rc;
+  return b.close();
+}
+
+int ascent_fly_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                     double *flown_traj, double *local_err, double *summary, int device_id, void *stream_, int ptr_is_device) {
+  BlobCall b(p, batch, o, sol_blob, stream_, ptr_is_device);
+  int rc = b.options();
+  if (rc) return rc;
+  if (!sol_blob || !summary) { snprintf(g_err, sizeof g_err, "null solution blob or summary pointer"); return ASCENT_E_ARG; }
+  if ((rc = check_substeps(substeps)) || (rc = b.solvable()) || (rc = b.open(device_id, 0))) return rc;
+  double *dt = b.st.out(flown_traj, (size_t)ASCENT_TRAJ_FIELDS * o->n_nodes * batch), *dl = b.st.out(local_err, (size_t)7 * b.K * batch);
+  double *ds = b.st.out(summary, (size_t)ASCENT_FLIGHT_ROWS * batch);
+  if ((rc = b.st.failed()) || (rc = flight_run(b.c, substeps, b.blob, dt, dl, ds))) return rc;
+  return b.close();
+}
+
 int ascent_flight_jacobian(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
                            double *jac_out, double *jac_u_out, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_flight_like(p, batch, o, sol_blob, substeps, ptr_is_device);
+  BlobCall b(p, batch, o, sol_blob, stream_, ptr_is_device);
+  int rc = b.flight_like(substeps);
   if (rc) return rc;
   if (!jac_out) { snprintf(g_err, sizeof g_err, "null jac_out"); return ASCENT_E_ARG; }
-  if ((rc = check_device(device_id))) return rc;
-  std::lock_guard<std::mutex> lock(g_mu[device_id]);
-  HIPCHK(hipSetDevice(device_id));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int K = o->n_nodes - 1;
-  double *ws = nullptr;
-  if ((rc = trim_ws_claim(device_id, jac_ws_bytes(K, (long)batch), stream, &ws))) return rc;
-  Staging st(stream, ptr_is_device);
-  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
-  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch);
-  double *dj = st.out(jac_out, (size_t)9 * 24 * batch), *du = st.out(jac_u_out, (size_t)9 * K * batch);
-  if ((rc = st.failed()) || (rc = jac_run(c, substeps, db, dj, du, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
-  return st.finish();
+  if ((rc = b.open(device_id, jac_ws_bytes(o->n_nodes - 1, (long)batch)))) return rc;
+  double *dj = b.st.out(jac_out, (size_t)9 * 24 * batch), *du = b.st.out(jac_u_out, (size_t)9 * b.K * batch);
+  if ((rc = b.st.failed()) || (rc = jac_run(b.c, substeps, b.blob, dj, du, b.ws))) return rc;
+  return b.close();
 }
 
 int ascent_trim_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
                       int32_t rounds, double tol, double *trim_blob_out, double *summary_out, int device_id, void *stream_,
                       int ptr_is_device) {
-  int rc = check_flight_like(p, batch, o, sol_blob, substeps, ptr_is_device);
+  BlobCall b(p, batch, o, sol_blob, stream_, ptr_is_device);
+  int rc = b.flight_like(substeps);
   if (rc) return rc;
   if (!trim_blob_out || !summary_out) { snprintf(g_err, sizeof g_err, "null trim_blob_out or summary_out"); return ASCENT_E_ARG; }
   if (rounds < 0 || rounds > 32) { snprintf(g_err, sizeof g_err, "rounds out of range (1 .. 32, 0 = 6)"); return ASCENT_E_ARG; }
-  if ((rc = check_device(device_id))) return rc;
+  if ((rc = b.open(device_id, trim_ws_bytes(o->n_nodes - 1, (long)batch)))) return rc;
   if (rounds == 0) rounds = 6;
   if (!(tol > 0.0)) tol = 1e-10;
-  std::lock_guard<std::mutex> lock(g_mu[device_id]);
-  HIPCHK(hipSetDevice(device_id));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int K = o->n_nodes - 1;
-  const size_t nb = (21 * (size_t)K + NSC) * batch;
-  double *ws = nullptr;
-  if ((rc = trim_ws_claim(device_id, trim_ws_bytes(K, (long)batch), stream, &ws))) return rc;
-  Staging st(stream, ptr_is_device);
-  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
-  const double *db = st.in(sol_blob, nb);
-  double *dout = st.out(trim_blob_out, nb), *ds = st.out(summary_out, (size_t)ASCENT_TRIM_ROWS * batch);
-  if ((rc = st.failed()) || (rc = trim_run(c, o->terminal, substeps, rounds, tol, db, dout, ds, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
-  return st.finish();
+  double *dout = b.st.out(trim_blob_out, (21 * (size_t)b.K + NSC) * batch), *ds = b.st.out(summary_out, (size_t)ASCENT_TRIM_ROWS * batch);
+  if ((rc = b.st.failed()) || (rc = trim_run(b.c, o->terminal, substeps, rounds, tol, b.blob, dout, ds, b.ws))) return rc;
+  return b.close();
 }
 
-// Monte Carlo dispersion (ascent_disperse.hip); its workspace is the buffer of the flight Jacobian and the trim
 int ascent_disperse_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
                           int32_t samples, const double *xi, const double *sigma, const double *sigma_u, double *stats_out,
                           double *samples_out, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_options(p, batch, o);
-  if (rc) return rc;
-  if (!sol_blob || !xi || !sigma || !stats_out) { snprintf(g_err, sizeof g_err, "null solution blob, xi, sigma or stats_out"); return ASCENT_E_ARG; }
-  if (samples < 1 || samples > ASCENT_DISPERSE_MAX_SAMPLES) { snprintf(g_err, sizeof g_err, "samples out of range (1 .. %d)", ASCENT_DISPERSE_MAX_SAMPLES); return ASCENT_E_ARG; }
-  if ((rc = check_substeps(substeps)) || (rc = check_solvable(p, batch, o, ptr_is_device)) || (rc = check_device(device_id))) return rc;
-  std::lock_guard<std::mutex> lock(g_mu[device_id]);
-  HIPCHK(hipSetDevice(device_id));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int K = o->n_nodes - 1;
-  double *ws = nullptr;
-  if ((rc = trim_ws_claim(device_id, disperse_ws_bytes(K, (long)batch, samples), stream, &ws))) return rc;
-  Staging st(stream, ptr_is_device);
-  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
-  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch);
-  const double *dx = st.in(xi, (size_t)(ASCENT_DISPERSE_COLS + (sigma_u ? K : 0)) * samples);
-  const double *dsg = st.in(sigma, (size_t)ASCENT_DISPERSE_COLS * batch), *dsu = st.in(sigma_u, (size_t)K * batch);
-  double *dst = st.out(stats_out, (size_t)ASCENT_DISPERSE_STAT_ROWS * batch);
-  double *dsm = st.out(samples_out, (size_t)ASCENT_DISPERSE_ROWS * samples * batch);
-  if ((rc = st.failed()) || (rc = disperse_run(c, substeps, samples, db, dx, dsg, dsu, dst, dsm, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
-  return st.finish();
+  DisperseIO io{};
+  io.blob = sol_blob; io.xi = xi; io.sigma = sigma; io.sigma_u = sigma_u;
+  io.stats = stats_out; io.samples_out = samples_out;
+  return disperse_call(p, batch, o, substeps, samples, DISPERSE_OPEN, io, device_id, stream_, ptr_is_device);
 }
 
-// Guidance gains (ascent_guide.hip) and the guided dispersion (ascent_disperse.hip); their workspace is that same buffer
 int ascent_guidance_gains(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
                           const double *weights, double *gain_u_out, double *gain_t_out, double *summary_out, double *jac_cl_out,
                           double *jac_u_cl_out, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_flight_like(p, batch, o, sol_blob, substeps, ptr_is_device);
-  if (rc) return rc;
-  if (!weights || !gain_u_out || !gain_t_out || !summary_out) { snprintf(g_err, sizeof g_err, "null weights, gain_u_out, gain_t_out or summary_out"); return ASCENT_E_ARG; }
-  if (jac_u_cl_out && !jac_cl_out) { snprintf(g_err, sizeof g_err, "jac_u_cl_out needs jac_cl_out"); return ASCENT_E_ARG; }
-  if ((rc = check_device(device_id))) return rc;
-  std::lock_guard<std::mutex> lock(g_mu[device_id]);
-  HIPCHK(hipSetDevice(device_id));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int K = o->n_nodes - 1;
-  double *ws = nullptr;
-  if ((rc = trim_ws_claim(device_id, gains_ws_bytes(K, (long)batch), stream, &ws))) return rc;
-  Staging st(stream, ptr_is_device);
-  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
-  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch), *dw = st.in(weights, (size_t)6 * batch);
-  double *dgu = st.out(gain_u_out, (size_t)7 * K * batch), *dgt = st.out(gain_t_out, (size_t)7 * batch);
-  double *ds = st.out(summary_out, (size_t)ASCENT_GUIDE_ROWS * batch);
-  double *dj = st.out(jac_cl_out, (size_t)9 * 24 * batch), *du = st.out(jac_u_cl_out, (size_t)9 * K * batch);
-  if ((rc = st.failed()) || (rc = gains_run(c, substeps, db, dw, dgu, dgt, ds, dj, du, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
-  return st.finish();
+  GainsIO io{};
+  io.blob = sol_blob; io.weights = weights;
+  io.gain_u = gain_u_out; io.gain_t = gain_t_out; io.summary = summary_out; io.jac = jac_cl_out; io.jac_u = jac_u_cl_out;
+  return gains_call(p, batch, o, substeps, false, io, device_id, stream_, ptr_is_device);
 }
 
 int ascent_disperse_guided_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
                                  int32_t samples, const double *xi, const double *sigma, const double *sigma_u, const double *gain_u,
                                  const double *gain_t, const double *stretch_max, double *stats_out, double *samples_out,
                                  int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_options(p, batch, o);
-  if (rc) return rc;
-  if (!sol_blob || !xi || !sigma || !gain_u || !stats_out) { snprintf(g_err, sizeof g_err, "null solution blob, xi, sigma, gain_u or stats_out"); return ASCENT_E_ARG; }
-  if (samples < 1 || samples > ASCENT_DISPERSE_MAX_SAMPLES) { snprintf(g_err, sizeof g_err, "samples out of range (1 .. %d)", ASCENT_DISPERSE_MAX_SAMPLES); return ASCENT_E_ARG; }
-  if ((rc = check_substeps(substeps)) || (rc = check_solvable(p, batch, o, ptr_is_device)) || (rc = check_device(device_id))) return rc;
-  std::lock_guard<std::mutex> lock(g_mu[device_id]);
-  HIPCHK(hipSetDevice(device_id));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int K = o->n_nodes - 1;
-  double *ws = nullptr;
-  if ((rc = trim_ws_claim(device_id, disperse_ws_bytes(K, (long)batch, samples), stream, &ws))) return rc;
-  Staging st(stream, ptr_is_device);
-  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
-  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch);
-  const double *dx = st.in(xi, (size_t)(ASCENT_DISPERSE_COLS + (sigma_u ? K : 0)) * samples);
-  const double *dsg = st.in(sigma, (size_t)ASCENT_DISPERSE_COLS * batch), *dsu = st.in(sigma_u, (size_t)K * batch);
-  const double *dgu = st.in(gain_u, (size_t)7 * K * batch), *dgt = st.in(gain_t, (size_t)7 * batch), *dsx = st.in(stretch_max, (size_t)batch);
-  double *dst = st.out(stats_out, (size_t)ASCENT_DISPERSE_STAT_ROWS * batch);
-  double *dsm = st.out(samples_out, (size_t)ASCENT_GUIDED_SAMPLE_ROWS * samples * batch);
-  if ((rc = st.failed()) || (rc = disperse_guided_run(c, substeps, samples, db, dx, dsg, dsu, dgu, dgt, dsx, dst, dsm, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
-  return st.finish();
+  DisperseIO io{};
+  io.blob = sol_blob; io.xi = xi; io.sigma = sigma; io.sigma_u = sigma_u;
+  io.gain_u = gain_u; io.gain_t = gain_t; io.stretch_max = stretch_max;
+  io.stats = stats_out; io.samples_out = samples_out;
+  return disperse_call(p, batch, o, substeps, samples, DISPERSE_GUIDED, io, device_id, stream_, ptr_is_device);
 }
 
-// The feed-forward siblings of the two calls above: same checks, same workspace, same staging
 int ascent_guidance_feedforward(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
                                 const double *weights, const double *ff_dir, const double *ff_know, double *gain_u_out,
                                 double *gain_t_out, double *ff_u_out, double *ff_t_out, double *summary_out, double *jac_cl_out,
                                 double *jac_u_cl_out, double *jac_nav_out, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_flight_like(p, batch, o, sol_blob, substeps, ptr_is_device);
-  if (rc) return rc;
-  if (!weights || !gain_u_out || !gain_t_out || !summary_out) { snprintf(g_err, sizeof g_err, "null weights, gain_u_out, gain_t_out or summary_out"); return ASCENT_E_ARG; }
-  if (!ff_dir || !ff_u_out || !ff_t_out) { snprintf(g_err, sizeof g_err, "null ff_dir, ff_u_out or ff_t_out"); return ASCENT_E_ARG; }
-  if (jac_u_cl_out && !jac_cl_out) { snprintf(g_err, sizeof g_err, "jac_u_cl_out needs jac_cl_out"); return ASCENT_E_ARG; }
-  if (jac_nav_out && !jac_cl_out) { snprintf(g_err, sizeof g_err, "jac_nav_out needs jac_cl_out"); return ASCENT_E_ARG; }
-  if (jac_cl_out && !ff_know) { snprintf(g_err, sizeof g_err, "jac_cl_out needs ff_know"); return ASCENT_E_ARG; }
-  if ((rc = check_device(device_id))) return rc;
-  std::lock_guard<std::mutex> lock(g_mu[device_id]);
-  HIPCHK(hipSetDevice(device_id));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int K = o->n_nodes - 1;
-  double *ws = nullptr;
-  if ((rc = trim_ws_claim(device_id, gains_ws_bytes(K, (long)batch), stream, &ws))) return rc;
-  Staging st(stream, ptr_is_device);
-  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
-  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch), *dw = st.in(weights, (size_t)6 * batch);
-  const double *dd = st.in(ff_dir, (size_t)16 * batch), *dk = st.in(ff_know, (size_t)16 * batch);
-  double *dgu = st.out(gain_u_out, (size_t)7 * K * batch), *dgt = st.out(gain_t_out, (size_t)7 * batch);
-  double *dfu = st.out(ff_u_out, (size_t)K * batch), *dft = st.out(ff_t_out, (size_t)batch);
-  double *ds = st.out(summary_out, (size_t)ASCENT_GUIDE_FF_ROWS * batch);
-  double *dj = st.out(jac_cl_out, (size_t)9 * 24 * batch), *du = st.out(jac_u_cl_out, (size_t)9 * K * batch);
-  double *dn = st.out(jac_nav_out, (size_t)9 * ASCENT_NAV_ROWS * batch);
-  if ((rc = st.failed()) || (rc = gains_ff_run(c, substeps, db, dw, dd, dk, dgu, dgt, dfu, dft, ds, dj, du, dn, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
-  return st.finish();
+  GainsIO io{};
+  io.blob = sol_blob; io.weights = weights; io.ff_dir = ff_dir; io.ff_know = ff_know;
+  io.gain_u = gain_u_out; io.gain_t = gain_t_out; io.ff_u = ff_u_out; io.ff_t = ff_t_out; io.summary = summary_out;
+  io.jac = jac_cl_out; io.jac_u = jac_u_cl_out; io.jac_nav = jac_nav_out;
+  return gains_call(p, batch, o, substeps, true, io, device_id, stream_, ptr_is_device);
 }
 
 int ascent_disperse_navigated_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
@@ -986,31 +1005,12 @@ int ascent_disperse_navigated_batch(const ascent_params *p, int64_t batch, const
                                     const double *gain_t, const double *stretch_max, const double *ff_u, const double *ff_t,
                                     const double *ff_know, const double *xi_nav, const double *sigma_nav, double *stats_out,
                                     double *samples_out, int device_id, void *stream_, int ptr_is_device) {
-  int rc = check_options(p, batch, o);
-  if (rc) return rc;
-  if (!sol_blob || !xi || !sigma || !gain_u || !stats_out) { snprintf(g_err, sizeof g_err, "null solution blob, xi, sigma, gain_u or stats_out"); return ASCENT_E_ARG; }
-  if (samples < 1 || samples > ASCENT_DISPERSE_MAX_SAMPLES) { snprintf(g_err, sizeof g_err, "samples out of range (1 .. %d)", ASCENT_DISPERSE_MAX_SAMPLES); return ASCENT_E_ARG; }
-  if ((xi_nav != nullptr) != (sigma_nav != nullptr)) { snprintf(g_err, sizeof g_err, "xi_nav and sigma_nav come together"); return ASCENT_E_ARG; }
-  if (ff_know && !ff_u) { snprintf(g_err, sizeof g_err, "ff_know needs ff_u"); return ASCENT_E_ARG; }
-  if ((rc = check_substeps(substeps)) || (rc = check_solvable(p, batch, o, ptr_is_device)) || (rc = check_device(device_id))) return rc;
-  std::lock_guard<std::mutex> lock(g_mu[device_id]);
-  HIPCHK(hipSetDevice(device_id));
-  hipStream_t stream = (hipStream_t)stream_;
-  const int K = o->n_nodes - 1;
-  double *ws = nullptr;
-  if ((rc = trim_ws_claim(device_id, disperse_ws_bytes(K, (long)batch, samples), stream, &ws))) return rc;
-  Staging st(stream, ptr_is_device);
-  const Call c = call_of(st.in(p, (size_t)batch), batch, o, stream);
-  const double *db = st.in(sol_blob, (21 * (size_t)K + NSC) * batch);
-  const double *dx = st.in(xi, (size_t)(ASCENT_DISPERSE_COLS + (sigma_u ? K : 0)) * samples);
-  const double *dsg = st.in(sigma, (size_t)ASCENT_DISPERSE_COLS * batch), *dsu = st.in(sigma_u, (size_t)K * batch);
-  const double *dgu = st.in(gain_u, (size_t)7 * K * batch), *dgt = st.in(gain_t, (size_t)7 * batch), *dsx = st.in(stretch_max, (size_t)batch);
-  const double *dfu = st.in(ff_u, (size_t)K * batch), *dft = st.in(ff_t, (size_t)batch), *dfk = st.in(ff_know, (size_t)16 * batch);
-  const double *dxn = st.in(xi_nav, (size_t)ASCENT_NAV_ROWS * samples), *dsn = st.in(sigma_nav, (size_t)ASCENT_NAV_ROWS * batch);
-  double *dst = st.out(stats_out, (size_t)ASCENT_DISPERSE_STAT_ROWS * batch);
-  double *dsm = st.out(samples_out, (size_t)ASCENT_GUIDED_SAMPLE_ROWS * samples * batch);
-  if ((rc = st.failed()) || (rc = disperse_navigated_run(c, substeps, samples, db, dx, dsg, dsu, dgu, dgt, dsx, dfu, dft, dfk, dxn, dsn, dst, dsm, ws)) || (rc = trim_ws_release(device_id, stream))) return rc;
-  return st.finish();
+  DisperseIO io{};
+  io.blob = sol_blob; io.xi = xi; io.sigma = sigma; io.sigma_u = sigma_u;
+  io.gain_u = gain_u; io.gain_t = gain_t; io.stretch_max = stretch_max;
+  io.ff_u = ff_u; io.ff_t = ff_t; io.ff_know = ff_know; io.xi_nav = xi_nav; io.sigma_nav = sigma_nav;
+  io.stats = stats_out; io.samples_out = samples_out;
+  return disperse_call(p, batch, o, substeps, samples, DISPERSE_NAVIGATED, io, device_id, stream_, ptr_is_device);
 }
 
 int ascent_kkt_step(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,

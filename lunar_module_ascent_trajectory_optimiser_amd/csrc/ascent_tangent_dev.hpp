@@ -1,6 +1,8 @@
 // Device helpers of the flight Jacobian (ascent_trim.hip: j_jac) shared with the guidance gains (ascent_guide.hip: g_gains): the
-// shape of a workgroup and of a step record, one RK4 collocation step with a tangent column carried along, and the gradient
-// of the two-body apsides.
+// shape of a workgroup and of a step record, one RK4 collocation step with a tangent column carried along, the gradient of the
+// two-body apsides, and the two ends of the Jacobian's sweep: the rows of Lambda_K it starts from (lambda_apsis_rows) and the chain
+// rule from its accumulators to the 24 columns (jac_columns), with that rule's transpose for a direction of the parameters
+// (tangent_coefficients).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -116,6 +118,71 @@ ASC_DEV bool apsides_grad(const ascent_params &prm, double x, double y, double v
   ASC_UNROLL
   for (int i = 0; i < 5; i++) { gp[i] = (1.0 - e) * da[i] - a * de[i]; ga[i] = (1.0 + e) * da[i] + a * de[i]; }
   return true;
+}
+
+// the direct dependence of an apsis row on G, M, R0 and r_peri (the sweep carries only what passes through the flown state)
+struct ApsisDirect { double G, M, R0, S; };
+
+// Lambda_K is the Jacobian of the nine end quantities with respect to the flown last state zK: the identity for the seven states
+// -- the caller's L[i] = q == i, for every thread, and dir = 0 -- and here, for the lanes of the sweeping wavefront, rows q = 7 / 8:
+// the gradient of the periapsis / apoapsis altitude and its direct terms.  (The identity stays outside and the gradient is
+// taken by every lane that calls: with either inside the branch j_jac is no longer the parent's instruction stream.)
+ASC_DEV void lambda_apsis_rows(const ascent_params &prm, const double *zK, int q, double *L, ApsisDirect &dir) {
+  double gp[5], ga[5];
+  apsides_grad(prm, zK[IX], zK[IY], zK[IVX], zK[IVY], gp, ga);
+  if (q == 7 || q == 8) {
+    const double *gq = q == 7 ? gp : ga;
+    const double S = prm.r_peri;
+    L[IX] = S * gq[0]; L[IY] = S * gq[1]; L[IVX] = S * gq[2]; L[IVY] = S * gq[3];
+    dir.S = zK[IX] * gq[0] + zK[IY] * gq[1] + zK[IVX] * gq[2] + zK[IVY] * gq[3];
+    dir.R0 = gq[1] - 1.0;
+    dir.G = prm.M * gq[4];
+    dir.M = prm.G * gq[4];
+  }
+}
+
+// The chain rule d(dt, Der)/d(params, t_f) (derive of ascent_device.hpp) at the end of the sweep: one row of the Jacobian, o[24] =
+// [z_0 | the 16 fields | t_f], from its row L0 of Lambda_0, its accumulators A[NACC] (columns C_DT .. C_MRATE summed over the
+// steps) and its direct terms.  tf: the blob's, K: intervals.
+template <int FORM>
+ASC_DEV void jac_columns(const ascent_params &prm, const Der &d, double tf, int K, const double *L0, const double *A,
+                         const ApsisDirect &dir, double *o) {
+  const double S = prm.r_peri, R0 = prm.R0;
+  const double aDT = A[0], aRHO0 = A[1 + ACC_RHO0], aGAM = A[1 + ACC_GAM], aTHR = A[1 + ACC_THR], aM0 = A[1 + ACC_M0],
+               aMS = A[1 + ACC_MS], aAL = A[C_ALPHA - C_DT], aMR = A[C_MRATE - C_DT];
+  ASC_UNROLL
+  for (int i = 0; i < 7; i++) o[i] = L0[i];
+  const double S3 = S * S * S;
+  o[7 + 0] = aGAM * prm.M / S3 + dir.G;                             // G
+  o[7 + 1] = aGAM * prm.G / S3 + dir.M;                             // M
+  o[7 + 2] = aRHO0 / S + dir.R0;                                    // R0
+  o[7 + 3] = aTHR / S;                                              // Ft
+  o[7 + 4] = aM0;                                                   // M0
+  o[7 + 5] = aMR / prm.fuel_mass;                                   // mdot
+  o[7 + 6] = -aMR * d.mrate / prm.fuel_mass;                        // fuel_mass
+  o[7 + 7] = aMS;                                                   // mass_scalar
+  o[7 + 8] = FORM == 1 ? 0.0 : aAL / 3.0;                           // ang_acc_max
+  o[7 + 9] = -aRHO0 * R0 / (S * S) - 3.0 * aGAM * d.gam / S - aTHR * d.thr / S + dir.S;     // r_peri
+  o[7 + 10] = 0.0;                                                  // r_apo
+  o[7 + 11] = aDT * (tf / K);                                       // T_scale
+  o[7 + 12] = FORM == 1 ? aAL : 0.0;                                // angle_ub
+  o[7 + 13] = 0.0; o[7 + 14] = 0.0; o[7 + 15] = 0.0;                // tf_lb, tf_ub, dcost
+  o[23] = aDT * (d.T / K);                                          // t_f
+}
+
+// The transpose of the rule above without its direct terms: what a unit step along the direction dd of the 16 fields does to
+// (dt, Der), coef[NACC] in the order of the accumulators -- column by column the factors of jac_columns.
+template <int FORM>
+ASC_DEV void tangent_coefficients(const ascent_params &prm, const Der &d, double tf, int K, const double *dd, double *coef) {
+  const double S = prm.r_peri, S3 = S * S * S;
+  coef[0] = dd[11] * (tf / K);
+  coef[1 + ACC_RHO0] = dd[2] / S - dd[9] * prm.R0 / (S * S);
+  coef[1 + ACC_GAM] = dd[0] * prm.M / S3 + dd[1] * prm.G / S3 - dd[9] * 3.0 * d.gam / S;
+  coef[1 + ACC_THR] = dd[3] / S - dd[9] * d.thr / S;
+  coef[1 + ACC_M0] = dd[4];
+  coef[1 + ACC_MS] = dd[7];
+  coef[C_ALPHA - C_DT] = FORM == 1 ? dd[12] : dd[8] / 3.0;
+  coef[C_MRATE - C_DT] = dd[5] / prm.fuel_mass - dd[6] * d.mrate / prm.fuel_mass;
 }
 
 }  // namespace ascent

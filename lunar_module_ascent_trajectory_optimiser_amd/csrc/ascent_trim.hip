@@ -19,7 +19,8 @@
 //          Lambda_{k-1} = Lambda_k Phi_k; Lambda_k g_k goes to jac_u, Lambda_k Gamma_k is summed into 8 accumulators, steps in
 //          descending order -- a fixed order, so a problem gives the same bits alone as inside any batch.
 //   epilogue    chain rule d(dt, Der)/d(params, t_f) (derive of ascent_device.hpp) plus the direct dependence of the apsis rows
-//          on G, M, R0, r_peri; Lambda_0 gives the z_0 columns.
+//          on G, M, R0, r_peri; Lambda_0 gives the z_0 columns.  Lambda_K's apsis rows and the epilogue are lambda_apsis_rows and
+//          jac_columns of ascent_tangent_dev.hpp, shared with g_gains.
 // t_update one wavefront per NLP, lanes over the steps: the conditions c = (e3, g1, g2) of terminal_eval at the flown last
 //          node, A = grad c [J_tf | J_u], the 3 x 3 normal matrix A W A' (per-lane partial sums over k = lane, lane + 64, ..,
 //          then a butterfly of cross-lane shuffles: a fixed order), delta = -W A' (A W A')^-1 c, the update in place.
@@ -61,24 +62,16 @@ __global__ __launch_bounds__(JB) void j_jac(const ascent_params *__restrict__ P,
   const double hs = dt / m;
 
   // the sweep's state, wave 0: lane q holds row q of Lambda, its accumulators and (rows 7, 8) the direct parameter terms
-  double L[7], A[NACC], dirG = 0.0, dirM = 0.0, dirR0 = 0.0, dirS = 0.0;
+  double L[7], A[NACC];
+  ApsisDirect dir = {0.0, 0.0, 0.0, 0.0};
   ASC_UNROLL
   for (int i = 0; i < 7; i++) L[i] = t == i ? 1.0 : 0.0;
   ASC_UNROLL
   for (int a = 0; a < NACC; a++) A[a] = 0.0;
   if (t < TW) {
-    double zK[7], gp[5], ga[5];
+    double zK[7];
     load_node(tr, B, nt, K, zK);
-    apsides_grad(prm, zK[IX], zK[IY], zK[IVX], zK[IVY], gp, ga);
-    if (t == 7 || t == 8) {
-      const double *gq = t == 7 ? gp : ga;
-      const double S = prm.r_peri;
-      L[IX] = S * gq[0]; L[IY] = S * gq[1]; L[IVX] = S * gq[2]; L[IVY] = S * gq[3];
-      dirS = zK[IX] * gq[0] + zK[IY] * gq[1] + zK[IVX] * gq[2] + zK[IVY] * gq[3];
-      dirR0 = gq[1] - 1.0;
-      dirG = prm.M * gq[4];
-      dirM = prm.G * gq[4];
-    }
+    lambda_apsis_rows(prm, zK, t, L, dir);
   }
 
   const int nch = (K + CH - 1) / CH;
@@ -118,37 +111,16 @@ __global__ __launch_bounds__(JB) void j_jac(const ascent_params *__restrict__ P,
   }
 
   if (t < JROWS) {
-    const double S = prm.r_peri, R0 = prm.R0;
-    const double aDT = A[0], aRHO0 = A[1 + ACC_RHO0], aGAM = A[1 + ACC_GAM], aTHR = A[1 + ACC_THR], aM0 = A[1 + ACC_M0],
-                 aMS = A[1 + ACC_MS], aAL = A[C_ALPHA - C_DT], aMR = A[C_MRATE - C_DT];
     double o[JCOLS];
-    ASC_UNROLL
-    for (int i = 0; i < 7; i++) o[i] = L[i];
-    const double S3 = S * S * S;
-    o[7 + 0] = aGAM * prm.M / S3 + dirG;                              // G
-    o[7 + 1] = aGAM * prm.G / S3 + dirM;                              // M
-    o[7 + 2] = aRHO0 / S + dirR0;                                     // R0
-    o[7 + 3] = aTHR / S;                                              // Ft
-    o[7 + 4] = aM0;                                                   // M0
-    o[7 + 5] = aMR / prm.fuel_mass;                                   // mdot
-    o[7 + 6] = -aMR * d.mrate / prm.fuel_mass;                        // fuel_mass
-    o[7 + 7] = aMS;                                                   // mass_scalar
-    o[7 + 8] = FORM == 1 ? 0.0 : aAL / 3.0;                           // ang_acc_max
-    o[7 + 9] = -aRHO0 * R0 / (S * S) - 3.0 * aGAM * d.gam / S - aTHR * d.thr / S + dirS;     // r_peri
-    o[7 + 10] = 0.0;                                                  // r_apo
-    o[7 + 11] = aDT * (tf / K);                                       // T_scale
-    o[7 + 12] = FORM == 1 ? aAL : 0.0;                                // angle_ub
-    o[7 + 13] = 0.0; o[7 + 14] = 0.0; o[7 + 15] = 0.0;                // tf_lb, tf_ub, dcost
-    o[23] = aDT * (d.T / K);                                          // t_f
+    jac_columns<FORM>(prm, d, tf, K, L, A, dir, o);
     ASC_UNROLL
     for (int cc = 0; cc < JCOLS; cc++) jac[((size_t)t * JCOLS + cc) * B + p] = o[cc];
   }
 }
 
-ASC_DEV double max_nan2(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
 ASC_DEV double wave_max_nan(double v) {
   ASC_UNROLL
-  for (int off = 32; off >= 1; off >>= 1) v = max_nan2(v, __shfl_xor(v, off));
+  for (int off = 32; off >= 1; off >>= 1) v = max_nan(v, __shfl_xor(v, off));
   return v;
 }
 ASC_DEV bool finite3(double a, double b, double c) {
@@ -255,7 +227,7 @@ __global__ __launch_bounds__(TW) void t_final(const ascent_params *__restrict__ 
     ASC_UNROLL
     for (int i = 0; i < 7; i++) b[(size_t)(7 * k + i) * B] = z[i];
     du = fmax(du, fabs(b[(size_t)(7 * K + k) * B] - bi[(size_t)(7 * K + k) * B]));
-    viol = max_nan2(viol, fmax(-z[IA], z[IA] - d.aub));
+    viol = max_nan(viol, fmax(-z[IA], z[IA] - d.aub));
   }
   du = wave_max_nan(du);
   viol = wave_max_nan(viol);
@@ -282,21 +254,14 @@ __global__ __launch_bounds__(TW) void t_final(const ascent_params *__restrict__ 
 
 struct TrimWs { double *traj, *fsum, *jac, *jac_u, *st; };
 TrimWs carve(double *ws, int K, long batch) {
-  TrimWs w;
-  const size_t B = (size_t)batch;
-  w.traj = ws;
-  w.fsum = w.traj + (size_t)ASCENT_TRAJ_FIELDS * (K + 1) * B;
-  w.jac = w.fsum + (size_t)ASCENT_FLIGHT_ROWS * B;
-  w.jac_u = w.jac + (size_t)JROWS * JCOLS * B;
-  w.st = w.jac_u + (size_t)JROWS * K * B;
-  return w;
+  const FlightWs f = flight_ws(ws, K, batch);
+  double *jac_u = f.rest + (size_t)JROWS * JCOLS * (size_t)batch;
+  return TrimWs{f.traj, f.fsum, f.rest, jac_u, jac_u + (size_t)JROWS * K * (size_t)batch};
 }
 
 }  // namespace
 
-size_t jac_ws_bytes(int K, long batch) {
-  return ((size_t)ASCENT_TRAJ_FIELDS * (K + 1) + ASCENT_FLIGHT_ROWS) * (size_t)batch * sizeof(double);
-}
+size_t jac_ws_bytes(int K, long batch) { return flight_ws_bytes(K, batch); }
 size_t trim_ws_bytes(int K, long batch) {
   return jac_ws_bytes(K, batch) + ((size_t)JROWS * JCOLS + (size_t)JROWS * K + ST_ROWS) * (size_t)batch * sizeof(double);
 }
@@ -313,7 +278,7 @@ static int jac_launch(const Call &c, int substeps, const double *dblob, const do
 }
 
 int jac_run(const Call &c, int substeps, const double *dblob, double *djac, double *djac_u, double *ws) {
-  const TrimWs w = carve(ws, c.K, c.batch);
+  const FlightWs w = flight_ws(ws, c.K, c.batch);
   if (const int rc = flight_fly_only(c, substeps, dblob, w.traj, w.fsum)) return rc;
   return jac_launch(c, substeps, dblob, w.traj, nullptr, djac, djac_u);
 }
