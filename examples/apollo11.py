@@ -4,7 +4,7 @@
 This is this repository's own counterpart of the reference script: the same problem, declared with
 the same modelling calls, solved by libascent on an MI355X instead of GEKKO/APMonitor/IPOPT.  It prints
 the quantities the reference prints (/root/reference/Launch_Optimiser.py:178-194) and writes the same
-three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim] [--disperse] [--guide [--feedforward]]
+three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim] [--disperse] [--guide [--feedforward]] [--corridor]
 --fly also integrates the ODEs under the control just found (RK4 on the device) and prints where that flight ends.
 --trim corrects (t_f, u) so that the flown control reaches the target orbit (trim_batch) and prints t_f and the flown apsides
 before and after.
@@ -131,29 +131,65 @@ def trim(m, scheme):
     return t
 
 
-def disperse(m, scheme, samples=1024):
+def corridor_report(name, d, params, tf, outdir=None, figure=None):
+    """What the samples of one dispersed flight did on the way (d.history, disperse_batch(history=True)): four lines, and with
+    outdir the figure `figure` (corridor_<name>.png if not named) -- nominal altitude against downrange with the min / max and
+    +-1-sigma bands."""
+    h, K = d.history, d.history.nodes[-1]
+    t = h.nodes * tf * params[0, 11] / K
+    ALT, ANG = 7, 4
+    sd = h.std[0, :, ALT]
+    i = int(np.nanargmax(sd))
+    print("%s: widest 1-sigma altitude band at node %d (t = %.1f s): +-%.1f m" % (name, h.nodes[i], t[i], sd[i]))
+    i = int(np.nanargmin(h.min[0, :, ALT]))
+    print("%s: lowest altitude any sample reached: %.2f m at node %d (t = %.1f s); nominal there %.2f m"
+          % (name, h.min[0, i, ALT], h.nodes[i], t[i], h.nominal[0, i, ALT]))
+    out = np.maximum(np.maximum(-h.min[0, :, ANG], h.max[0, :, ANG] - params[0, 12]), 0.0)
+    i = int(np.nanargmax(out))
+    print("%s: largest excursion of the angle beyond [0, angle_ub]: %.3g (angle_ub %.4g) at node %d" % (name, out[i], params[0, 12], h.nodes[i]))
+    i = int(np.argmax(h.clipped[0]))
+    print("%s: step with the most clipped commands: step %d (t = %.1f s), %d of %d samples" % (name, h.nodes[i], t[i], h.clipped[0, i], h.n_valid[0, i]))
+    if outdir is not None:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+        x = -h.nominal[0, :, 0] * ORBIT["periapsis"]                  # downrange positive, as plots() has it
+        fig, ax = plt.subplots()
+        ax.fill_between(x, h.min[0, :, ALT], h.max[0, :, ALT], color=(0.9, 0.4, 0, 0.25), label="min / max")
+        ax.fill_between(x, h.mean[0, :, ALT] - sd, h.mean[0, :, ALT] + sd, color=(0.9, 0.4, 0, 0.5), label="+-1 sigma")
+        ax.plot(x, h.nominal[0, :, ALT], color="k", lw=0.8, label="nominal")
+        ax.set(title="Dispersion corridor (%s)" % name, xlabel="downrange / m", ylabel="altitude / m")
+        ax.legend()
+        ax.grid()
+        fig.savefig(os.path.join(outdir, figure or "corridor_%s.png" % name.replace(" ", "_")), dpi=300)
+
+
+def disperse(m, scheme, samples=1024, corridor=False, outdir=None):
     """The trimmed solution under a dispersed thrust and control: Monte Carlo on the device beside the flight Jacobian's linear
-    prediction from the same draws."""
+    prediction from the same draws.  corridor: with the per-node history, and its lines (corridor_report)."""
     from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, flight_jacobian, trim_batch
     res = m.result
     kw = dict(scheme=scheme, formulation=m._formulation)
     t = trim_batch(res.params, res.flight_blob(), res.nt, **kw)
     thrust = np.zeros(16)
     thrust[3] = 50.0
-    d = disperse_batch(res.params, t.blob, res.nt, param_sigma=thrust, control_sigma=1e-3, samples=samples, **kw)
+    d = disperse_batch(res.params, t.blob, res.nt, param_sigma=thrust, control_sigma=1e-3, samples=samples, history=corridor, **kw)
     lin = np.sqrt(np.diagonal(d.linear_covariance(flight_jacobian(res.params, t.blob, res.nt, **kw)), axis1=1, axis2=2))
     print("dispersion: %d of %d samples valid; thrust 1-sigma 50 N, control 1-sigma 1e-3 per step" % (d.n_valid[0], samples))
     print("flown altitude (m)      nominal   Monte Carlo 1-sigma   linear 1-sigma   mean shift          min          max")
     for name, q in (("periapsis", 7), ("apoapsis", 8)):
         print("%-18s %12.1f %21.1f %16.1f %12.1f %12.1f %12.1f"
               % (name, d.nominal[0, q], d.std[0, q], lin[0, q], d.mean[0, q] - d.nominal[0, q], d.min[0, q], d.max[0, q]))
+    if corridor:
+        corridor_report("open loop", d, res.params, t.tf[0], outdir, "corridor.png")
     return d
 
 
-def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=False):
+def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=False, corridor=False, outdir=None):
     """The trimmed solution under the same dispersions, open loop and steering back to the nominal with a cutoff on the state.
     The cutoff channel stretches the last step only, T / K = 2.2 s here: 50 N of 15 kN over a 435 s burn is 1.4 s (1-sigma) of burn
-    time, so the stretch is allowed +-2 steps; at stretch_max = 0.5 it sits on its bound for most samples."""
+    time, so the stretch is allowed +-2 steps; at stretch_max = 0.5 it sits on its bound for most samples.
+    corridor: every flight flown with its per-node history, and the lines of corridor_report for each."""
     from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, guidance_gains, trim_batch
     res = m.result
     kw = dict(scheme=scheme, formulation=m._formulation)
@@ -161,7 +197,7 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
     g = guidance_gains(res.params, t.blob, res.nt, cond_weights=(weight,) * 3, control_weight=1.0, cutoff_weight=1.0, stretch_max=stretch_max, **kw)
     thrust = np.zeros(16)
     thrust[3] = 50.0
-    dkw = dict(param_sigma=thrust, control_sigma=1e-3, samples=samples, **kw)
+    dkw = dict(param_sigma=thrust, control_sigma=1e-3, samples=samples, history=corridor, **kw)
     op = disperse_batch(res.params, t.blob, res.nt, **dkw)
     cl = disperse_batch(res.params, t.blob, res.nt, guidance=g, keep_samples=True, **dkw)
     print("guidance: status %d, %d of %d controls free, largest steering gain %.4g, largest cutoff gain %.4g (weights %g, 1, 1)"
@@ -173,6 +209,9 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
     e = cl.effort[0]
     print("control authority: a command clipped on %.2f steps per flight, largest |K.dz| %.3g, cutoff stretch 1-sigma %.3g (largest %.3g of %g)"
           % (e[:, 0].mean(), np.nanmax(e[:, 1]), np.nanstd(e[:, 2]), np.nanmax(np.abs(e[:, 2])), stretch_max))
+    if corridor:
+        corridor_report("open loop", op, res.params, t.tf[0], outdir)
+        corridor_report("closed loop", cl, res.params, t.tf[0], outdir, "corridor.png")
     if feedforward:
         # the same draws with the feed-forward: the feedback gains are the same bits, the samples now plan with their own thrust
         gf = guidance_gains(res.params, t.blob, res.nt, cond_weights=(weight,) * 3, control_weight=1.0, cutoff_weight=1.0, stretch_max=stretch_max,
@@ -186,6 +225,9 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
             print("%-24s %13.1f %15.2f %30.2f %25.2f (%.2f)" % (name, op.std[0, q], cl.std[0, q], known.std[0, q], nav.std[0, q], lin[q]))
         print("commands clipped per flight: feedback only %.2f, thrust known %.2f, 10 N and navigation bias %.2f"
               % (e[:, 0].mean(), known.effort[0, :, 0].mean(), nav.effort[0, :, 0].mean()))
+        if corridor:
+            corridor_report("thrust known", known, res.params, t.tf[0], outdir)
+            corridor_report("known to 10 N", nav, res.params, t.tf[0], outdir)
     return op, cl, g
 
 
@@ -227,7 +269,11 @@ if __name__ == "__main__":
     ap.add_argument("--disperse", action="store_true", help="trim, then fly the trimmed control under 50 N of thrust and 1e-3 of control error 1024 times; prints Monte Carlo and linear 1-sigma of the flown apsides")
     ap.add_argument("--guide", action="store_true", help="trim, compute LQ feedback gains and fly 1024 dispersed samples open loop and closed loop; prints both 1-sigmas of the flown apsides")
     ap.add_argument("--feedforward", action="store_true", help="with --guide: also fly the same draws with the thrust feed-forward, once with the thrust known exactly and once known to 10 N (1-sigma) under a navigation bias of 1-sigma %g (scaled; %.1f m) on both positions and %g (scaled; %.1f cm/s) on both velocities" % (NAV_BIAS[0], NAV_BIAS[0] * ORBIT["periapsis"], NAV_BIAS[2], NAV_BIAS[2] * ORBIT["periapsis"] * 100))
+    ap.add_argument("--corridor", action="store_true", help="with --disperse or --guide: reduce the samples at every node as well (disperse_batch(history=True)); prints, per flight flown, the widest 1-sigma altitude band, the lowest altitude any sample reached, the largest excursion of the angle beyond its bounds and the step with the most clipped commands, and writes corridor.png (with --guide: of the closed loop; the other flights as corridor_<flight>.png)")
     a = ap.parse_args()
+    if a.corridor and not (a.disperse or a.guide):
+        ap.error("--corridor needs --disperse or --guide")
+    figdir = None if a.no_plots else a.outdir
     model, variables, v_ins = build()
     if a.no_dcost:
         model.options.ASCENT_DCOST = 0
@@ -240,8 +286,8 @@ if __name__ == "__main__":
     if a.trim:
         trim(model, a.scheme)
     if a.disperse:
-        disperse(model, a.scheme)
+        disperse(model, a.scheme, corridor=a.corridor, outdir=figdir)
     if a.guide:
-        guide(model, a.scheme, feedforward=a.feedforward)
+        guide(model, a.scheme, feedforward=a.feedforward, corridor=a.corridor, outdir=figdir)
     if not a.no_plots:
         plots(model, variables, a.outdir)

@@ -501,6 +501,59 @@ int ascent_disperse_navigated_batch(const ascent_params *p, int64_t batch, const
                                     double *stats_out, double *samples_out_or_null, int device_id, void *hip_stream_or_null,
                                     int ptr_is_device);
 
+/* Monte Carlo history: the dispersion corridor of a flight.  One of the three dispersion calls above, with the samples reduced
+ * not only at the end of the burn but at the nodes on the way: how wide the corridor is, whether a sample comes back to the
+ * surface, whether the guided vehicle leaves its angle bounds, where the feedback clips.
+ * Which flight: gain_u null -- ascent_disperse_batch's (gain_t, stretch_max, ff_*, xi_nav and sigma_nav must then be null);
+ *   gain_u given -- ascent_disperse_navigated_batch's, which with everything after stretch_max null is
+ *   ascent_disperse_guided_batch's bit for bit.  stats_out [82][batch] and the rows of samples_out_or_null are the bits of that
+ *   call on the same inputs; samples_out is always [ASCENT_GUIDED_SAMPLE_ROWS][samples][batch], rows 9..11 exactly 0 in the
+ *   open-loop flight.  The history changes nothing those calls compute.
+ * History nodes: node_stride in 1 .. K; NJ = K / node_stride + (K % node_stride != 0) nodes j_i = min((i + 1) * node_stride, K),
+ *   i = 0 .. NJ-1: every node_stride-th node and always the last one.  Node 0 (the perturbation of z_0 itself) is not reported.
+ * The ASCENT_HISTORY_QUANTITIES quantities q of sample s at node j:
+ *   0..6  the flown state z at node j, scaled units (on the last node after the cutoff stretch)
+ *   7     altitude (m): sqrt(X*X + Y*Y) - R0, X = x * r_peri, Y = y * r_peri + R0, with the sample's own perturbed fields
+ *   8     the executed control of step j, the step that ends at node j: the command + sigma_u * xi, what the flight was given (in
+ *         formulation 1 the normalised angle command)
+ *   9     the correction of step j, K_j . dz + f_j * theta-hat; exactly 0 where the step's gain row and f_j are all zero, and in
+ *         the open-loop flight.
+ * A sample is valid at node j if its ten quantities there are all finite (a NaN stays: the count does not rise with j).  This
+ *   is not the rule of stats_out, which also asks for a finite apoapsis: an escaping sample is valid in the history.
+ * hist_out [ASCENT_HISTORY_ROWS][NJ][batch], element (row r, node i, problem) at ((r*NJ + i)*batch + problem):
+ *   0        n, the number of samples valid at the node
+ *   1..10    the nominal flight's ten quantities: state and altitude from the trajectory of ascent_fly_batch on the blob with the
+ *            nominal fields, the blob's u_j, correction 0
+ *   11..20   mean              21..30   unbiased variance (NaN where n < 2)
+ *   31..40 / 41..50   minimum / maximum over the valid samples (NaN where n = 0)
+ *   51       the number of valid samples whose command of step j was clipped (the rule behind samples_out row 9; counted only where
+ *            the step has a gain or a feed-forward; 0 in the open-loop flight)
+ *   Moments on the differences from the nominal rows (centre 0 where a nominal row is not finite), the expressions of stats_out:
+ *   mean = centre + sum / n (n = 1: the sample itself), variance = (sum of squares - sum * sum / n) / (n - 1).  The order of the
+ *   additions is that of stats_out: a butterfly inside a wavefront, the wavefronts of a workgroup in order, the workgroups in
+ *   ascending order.  Where every sample is valid under both rules, rows 0, 11..17, 21..27, 31..37 and 41..47 of the last node are,
+ *   bit for bit, rows 0, 10..16, the seven diagonal covariance entries of the state (19, 28, 36, 43, 49, 54, 58), 64..70 and
+ *   73..79 of stats_out.  A node's rows do not depend on node_stride, the batch size, the problem's place in the batch, host or
+ *   device pointers, or whether the optional outputs were asked for.
+ * hist_samples_out_or_null [ASCENT_HISTORY_QUANTITIES][NJ][samples][batch], element (q, i, s, problem) at
+ *   (((q*NJ + i)*samples + s)*batch + problem): every sample's ten quantities, invalid ones as they came out.  The only thing of
+ *   size samples * K, and only when asked for.
+ * Refuses (ASCENT_E_ARG, before the device is looked at, no array touched) what ascent_disperse_navigated_batch refuses, a null
+ *   hist_out, node_stride outside 1 .. K, and any of gain_t, stretch_max, ff_*, xi_nav, sigma_nav without gain_u.  terminal = 2 is
+ *   accepted.  Garbage blobs: bounded work as ascent_disperse_batch; a non-finite t_f gives n = 0 and NaN rows at every node.
+ * Host or device pointers; with device pointers and a stream the call only enqueues (f_fly, f_disperse with the history or f_history_guided,
+ *   f_disperse_stats, f_history_stats; no host read, no synchronisation).  Device workspace: that of ascent_disperse_batch plus
+ *   ceil(samples / 256) * NJ * 42 * batch doubles of partial records. */
+#define ASCENT_HISTORY_QUANTITIES 10
+#define ASCENT_HISTORY_ROWS 52
+int ascent_disperse_history_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                                  int32_t substeps, int32_t samples, const double *xi, const double *sigma,
+                                  const double *sigma_u_or_null, const double *gain_u_or_null, const double *gain_t_or_null,
+                                  const double *stretch_max_or_null, const double *ff_u_or_null, const double *ff_t_or_null,
+                                  const double *ff_know_or_null, const double *xi_nav_or_null, const double *sigma_nav_or_null,
+                                  int32_t node_stride, double *stats_out, double *samples_out_or_null, double *hist_out,
+                                  double *hist_samples_out_or_null, int device_id, void *hip_stream_or_null, int ptr_is_device);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

@@ -19,6 +19,10 @@
 // f_disperse_guided f_disperse under state feedback (ascent_disperse_guided_batch): same mapping, same record, same reduction.
 // f_disperse_navigated  f_disperse_guided with the feed-forward f_k theta-hat and the navigation errors of
 //          ascent_disperse_navigated_batch: one body with f_disperse_guided (guided_body<FORM, NAV>).
+// f_disperse<FORM, true> / f_history_guided  f_disperse / f_disperse_navigated with the per-node history of
+//          ascent_disperse_history_batch (HIST, an `if constexpr` in the two step loops): at a history node every lane holds its ten
+//          quantities, and the 42 values of the node's record are reduced like the end record -- one barrier per history node.
+// f_history_stats   one lane per (problem, node): the node's partial records added in ascending chunk order, then the 52 rows.
 // The kernels share their head (sample_lane, perturbed_sample) and their tail (end_rows, reduce_partial); only the step loops
 // differ.  One host function, disperse_run, launches whichever kernel the call's kind names.
 // The order of every addition is fixed by `samples` alone: a problem gives the same bits alone as inside any batch.
@@ -45,6 +49,12 @@ constexpr int R_N = 0, R_SUM = 1, R_PROD = R_SUM + NQ, R_MIN = R_PROD + NQ * (NQ
 constexpr int O_N = 0, O_NOM = 1, O_MEAN = O_NOM + NQ, O_COV = O_MEAN + NQ, O_MIN = O_COV + NQ * (NQ + 1) / 2, O_MAX = O_MIN + NQ;
 static_assert(O_MAX + NQ == ASCENT_DISPERSE_STAT_ROWS, "stats_out layout");
 constexpr long MAX_GRID = 1L << 22;        // workgroups per launch: 2^30 threads
+// the history (ascent_disperse_history_batch): a partial record per workgroup and history node, rows of [nwg][NJ][HREC][batch]
+constexpr int HQ = ASCENT_HISTORY_QUANTITIES;
+constexpr int H_N = 0, H_SUM = 1, H_SQ = H_SUM + HQ, H_MIN = H_SQ + HQ, H_MAX = H_MIN + HQ, H_CLIP = H_MAX + HQ, HREC = H_CLIP + 1;
+// hist_out rows
+constexpr int HO_N = 0, HO_NOM = 1, HO_MEAN = HO_NOM + HQ, HO_VAR = HO_MEAN + HQ, HO_MIN = HO_VAR + HQ, HO_MAX = HO_MIN + HQ, HO_CLIP = HO_MAX + HQ;
+static_assert(HO_CLIP + 1 == ASCENT_HISTORY_ROWS, "hist_out layout");
 
 // butterflies: every lane ends with the same bits (no lane contributes a NaN: invalid samples enter as +-inf)
 ASC_DEV double wave_min(double v) {
@@ -179,18 +189,107 @@ ASC_DEV void reduce_partial(const Lane &l, const double *r, const double *cen, d
   }
 }
 
-template <int FORM>
+// What a history kernel is given beyond its plain sibling: every stride-th node and the last one, nj of them; the partial
+// records and the caller's per-sample rows (or null)
+struct HistArgs {
+  int stride, nj;
+  double *partial, *samples;
+};
+
+// altitude above R0 (m) of a scaled position, fields as apsides_of takes them.  Not contracted: f_history_stats and the flights
+// compute the nominal one each for itself and must agree in every bit
+// The position is taken through an empty asm: apsides_of forms the same products on the last node, and a product the compiler
+// found shared with this function would no longer be fused into its addition there -- the end rows would lose the bits of the
+// call without the history.
+ASC_DEV double altitude_of(double x, double y, double r_peri, double R0) {
+#pragma clang fp contract(off)
+  asm volatile("" : "+v"(x), "+v"(y));
+  const double X = x * r_peri, Y = y * r_peri + R0;
+  return sqrt(X * X + Y * Y) - R0;
+}
+
+// the nominal flight's ten quantities at node j (1 .. K): f_fly's trajectory with the nominal fields, the blob's u_j, no correction
+ASC_DEV void history_nominal(const double *__restrict__ tr, const double *__restrict__ b, const double *__restrict__ pf, size_t B,
+                             int K, int j, double *nom) {
+  load_node(tr, B, K + 1, j, nom);
+  nom[7] = altitude_of(nom[IX], nom[IY], pf[9], pf[2]);
+  nom[8] = b[(size_t)(7 * K + j - 1) * B];
+  nom[9] = 0.0;
+}
+
+// One history node, every lane of the workgroup (a lane without a sample: has = false): the ten quantities h of the lane's
+// sample at node j and whether the command of step j was clipped.  The 42 values of the node's record are reduced exactly as
+// wave_record and reduce_partial reduce the end rows -- a butterfly per value, then the wavefronts in order -- so that the last
+// node's count, sums, squares and extrema of the state are the end statistics' bits.  One barrier per history node: the two
+// halves of hred alternate, and the barrier of node i + 1 stands between the reads of node i and the writes of node i + 2.
+ASC_DEV void history_node(const Lane &l, bool has, int K, int j, const HistArgs &H, const double *__restrict__ traj, const double *h,
+                          bool clip) {
+#pragma clang fp contract(off)      // as wave_record: a square fused into the first addition of its butterfly would differ between the lanes
+  __shared__ double hred[2][DNW][HREC];
+  const int i = (j + H.stride - 1) / H.stride - 1, lane = l.t & 63;
+  double cen[HQ];
+  history_nominal(traj + l.p, l.b, l.pf, l.B, K, j, cen);
+  bool valid = has;
+  ASC_UNROLL
+  for (int q = 0; q < HQ; q++) {
+    cen[q] = finite1(cen[q]) ? cen[q] : 0.0;
+    valid = valid && finite1(h[q]);
+  }
+  if (H.samples && has) {
+    ASC_UNROLL
+    for (int q = 0; q < HQ; q++) H.samples[(((size_t)q * H.nj + i) * l.NS + l.s) * l.B + l.p] = h[q];
+  }
+  double *red = hred[i & 1][l.t >> 6];
+  double v = wave_sum(valid ? 1.0 : 0.0);
+  if (lane == 0) red[H_N] = v;
+  ASC_UNROLL
+  for (int q = 0; q < HQ; q++) {
+    const double dq = valid ? h[q] - cen[q] : 0.0;
+    v = wave_sum(dq);
+    if (lane == 0) red[H_SUM + q] = v;
+    const double sq = dq * dq;
+    v = wave_sum(sq);
+    if (lane == 0) red[H_SQ + q] = v;
+    v = wave_min(valid ? h[q] : INFINITY);
+    if (lane == 0) red[H_MIN + q] = v;
+    v = wave_max(valid ? h[q] : -INFINITY);
+    if (lane == 0) red[H_MAX + q] = v;
+  }
+  v = wave_sum(valid && clip ? 1.0 : 0.0);
+  if (lane == 0) red[H_CLIP] = v;
+  __syncthreads();
+  if (l.t < HREC) {
+    const int nw = (int)blockDim.x >> 6;
+    double a = hred[i & 1][0][l.t];
+    for (int w = 1; w < nw; w++) {
+      const double o = hred[i & 1][w][l.t];
+      a = l.t < H_MIN || l.t == H_CLIP ? a + o : l.t < H_MAX ? fmin(a, o) : fmax(a, o);
+    }
+    H.partial[(((size_t)l.c * H.nj + i) * HREC + l.t) * l.B + l.p] = a;
+  }
+}
+
+// HIST (include/ascent.h: ascent_disperse_history_batch): after the steps that end at a history node the ten quantities of the
+// node are reduced over the workgroup (history_node).  Its barrier needs every wavefront, so a lane without a sample flies the
+// last sample again and is left out of every record and output.  samples_out has the twelve rows of the guided calls, the last
+// three zero.  HIST = false: no trace of the history in the code (the kernel is a kernel, not a wrapper of a shared body as the
+// guided ones are, because the wrapping alone changes the code the compiler emits for it).
+template <int FORM, bool HIST>
 __global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
                                                  int nwg, long g0, const double *__restrict__ blob,
                                                  const double *__restrict__ traj, const double *__restrict__ fsum,
                                                  const double *__restrict__ xi, const double *__restrict__ sigma,
                                                  const double *__restrict__ sigma_u, double *__restrict__ partial,
-                                                 double *__restrict__ samples_out) {
+                                                 double *__restrict__ samples_out, HistArgs H) {
   __shared__ double red[DNW][NREC];
   Lane l;
   double cen[NQ], r[NQ];
   sample_lane(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, l, cen, r);
-  if (l.s < samples) {
+  const bool has = l.s < samples;
+  if constexpr (HIST) {
+    if (!has) { l.s = samples - 1; samples_out = nullptr; }
+  }
+  if (HIST || has) {
     const size_t B = l.B, NS = l.NS;
     const int m = l.m;
     double sg[NC], xv[NC], z[7], dt, hs;
@@ -207,9 +306,25 @@ __global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict
       const int kn = k + 1 < K ? k + 1 : k;
       const double un = ub[(size_t)kn * B], sgn = su ? su[(size_t)kn * B] : 0.0, xn = su ? xu[(size_t)kn * NS] : 0.0;
       fly_step<FORM>(d, z, u, hs, m);
+      if constexpr (HIST) {
+        if ((k + 1) % H.stride == 0 || k + 1 == K) {
+          const double h[HQ] = {z[0], z[1], z[2], z[3], z[4], z[5], z[6], altitude_of(z[IX], z[IY], prm.r_peri, prm.R0), u, 0.0};
+          history_node(l, has, K, k + 1, H, traj, h, false);
+        }
+      }
       u = sgn != 0.0 ? un + sgn * xn : un;
     }
     end_rows(l, prm, z, r, samples_out);
+    if constexpr (HIST) {
+      if (samples_out) {
+        ASC_UNROLL
+        for (int q = NQ; q < ASCENT_GUIDED_SAMPLE_ROWS; q++) samples_out[((size_t)q * NS + l.s) * B + l.p] = 0.0;
+      }
+      if (!has) {
+        ASC_UNROLL
+        for (int q = 0; q < NQ; q++) r[q] = NAN;
+      }
+    }
   }
   reduce_partial(l, r, cen, red, partial);
 }
@@ -223,7 +338,9 @@ __global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict
 // not zero, and theta-hat, what the sample believes its parameter deviation is.  Each addition is skipped where its factor is
 // zero, so with nothing new given, or all of it zero, a flight has f_disperse_guided's bits.  NAV = false: f_disperse_guided, the
 // new arguments all null and no trace of them in the code.
-template <int FORM, bool NAV>
+// HIST (f_history_guided): as in f_disperse; quantity 9 is the correction `dot` of the step, exactly 0 where the step has neither
+// gain nor feed-forward, and the clipped flag of the step is the comparison behind nclip.
+template <int FORM, bool NAV, bool HIST>
 ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
                          int nwg, long g0, const double *__restrict__ blob,
                          const double *__restrict__ traj, const double *__restrict__ fsum,
@@ -232,12 +349,16 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
                          const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
                          const double *__restrict__ ff_u, const double *__restrict__ ff_t, const double *__restrict__ ff_know,
                          const double *__restrict__ xi_nav, const double *__restrict__ sigma_nav,
-                         double *__restrict__ partial, double *__restrict__ samples_out) {
+                         double *__restrict__ partial, double *__restrict__ samples_out, const HistArgs &H) {
   __shared__ double red[DNW][NREC];
   Lane l;
   double cen[NQ], r[NQ];
   sample_lane(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, l, cen, r);
-  if (l.s < samples) {
+  const bool has = l.s < samples;
+  if constexpr (HIST) {
+    if (!has) { l.s = samples - 1; samples_out = nullptr; }
+  }
+  if (HIST || has) {
     const size_t B = l.B, NS = l.NS;
     const long p = l.p;
     const int s = l.s, m = l.m, nt = K + 1;
@@ -288,6 +409,7 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
         zero = zero && kn[i] == 0.0;
       }
       double uc = un;
+      [[maybe_unused]] bool clip = false;
       if constexpr (NAV) zero = zero && fn == 0.0;
       if (!zero) {
         double w = un - dot;
@@ -300,6 +422,7 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
         }
         uc = finite1(dot) ? fmin(1.0, fmax(-1.0, w)) : NAN;
         nclip += uc != w ? 1.0 : 0.0;
+        if constexpr (HIST) clip = uc != w;
         dmax = (dot != dot || dmax != dmax) ? NAN : fmax(dmax, fabs(dot));
       }
       const double u = sgn != 0.0 ? uc + sgn * xn : uc;
@@ -322,12 +445,29 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
       for (int i = 0; i < 7; i++) kn[i] = gu[((size_t)i * K + kq) * B];
       if constexpr (NAV) fn = ff_u ? ff_u[(size_t)kq * B + p] : 0.0;
       fly_step<FORM>(d, z, u, h, m);
+      if constexpr (HIST) {
+        if ((k + 1) % H.stride == 0 || k + 1 == K) {
+          const double hq[HQ] = {z[0], z[1], z[2], z[3], z[4], z[5], z[6], altitude_of(z[IX], z[IY], prm.r_peri, prm.R0), u,
+                                 zero ? 0.0 : dot};
+          history_node(l, has, K, k + 1, H, traj, hq, clip);
+        }
+      }
+    }
+    if constexpr (HIST) {
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) asm volatile("" : "+v"(z[i]));
     }
     end_rows(l, prm, z, r, samples_out);
     if (samples_out) {
       samples_out[((size_t)(NQ + 0) * NS + s) * B + p] = nclip;
       samples_out[((size_t)(NQ + 1) * NS + s) * B + p] = dmax;
       samples_out[((size_t)(NQ + 2) * NS + s) * B + p] = stretch;
+    }
+    if constexpr (HIST) {
+      if (!has) {
+        ASC_UNROLL
+        for (int q = 0; q < NQ; q++) r[q] = NAN;
+      }
     }
   }
   reduce_partial(l, r, cen, red, partial);
@@ -341,8 +481,8 @@ __global__ __launch_bounds__(DB) void f_disperse_guided(const ascent_params *__r
                                                         const double *__restrict__ sigma_u, const double *__restrict__ gain_u,
                                                         const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
                                                         double *__restrict__ partial, double *__restrict__ samples_out) {
-  guided_body<FORM, false>(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, xi, sigma, sigma_u, gain_u, gain_t, stretch_max,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, partial, samples_out);
+  guided_body<FORM, false, false>(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, xi, sigma, sigma_u, gain_u, gain_t, stretch_max,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, partial, samples_out, HistArgs{});
 }
 
 struct NavArgs { const double *ff_u, *ff_t, *ff_know, *xi_nav, *sigma_nav; };
@@ -355,8 +495,21 @@ __global__ __launch_bounds__(DB) void f_disperse_navigated(const ascent_params *
                                                            const double *__restrict__ sigma_u, const double *__restrict__ gain_u,
                                                            const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
                                                            NavArgs nav, double *__restrict__ partial, double *__restrict__ samples_out) {
-  guided_body<FORM, true>(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, xi, sigma, sigma_u, gain_u, gain_t, stretch_max,
-                          nav.ff_u, nav.ff_t, nav.ff_know, nav.xi_nav, nav.sigma_nav, partial, samples_out);
+  guided_body<FORM, true, false>(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, xi, sigma, sigma_u, gain_u, gain_t, stretch_max,
+                                 nav.ff_u, nav.ff_t, nav.ff_know, nav.xi_nav, nav.sigma_nav, partial, samples_out, HistArgs{});
+}
+
+template <int FORM>
+__global__ __launch_bounds__(DB) void f_history_guided(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
+                                                       int nwg, long g0, const double *__restrict__ blob,
+                                                       const double *__restrict__ traj, const double *__restrict__ fsum,
+                                                       const double *__restrict__ xi, const double *__restrict__ sigma,
+                                                       const double *__restrict__ sigma_u, const double *__restrict__ gain_u,
+                                                       const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
+                                                       NavArgs nav, double *__restrict__ partial, double *__restrict__ samples_out,
+                                                       HistArgs hist) {
+  guided_body<FORM, true, true>(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, xi, sigma, sigma_u, gain_u, gain_t, stretch_max,
+                                nav.ff_u, nav.ff_t, nav.ff_know, nav.xi_nav, nav.sigma_nav, partial, samples_out, hist);
 }
 
 __global__ __launch_bounds__(SW) void f_disperse_stats(long batch, int K, int nwg, const double *__restrict__ traj,
@@ -399,23 +552,76 @@ __global__ __launch_bounds__(SW) void f_disperse_stats(long batch, int K, int nw
   }
 }
 
+// The 52 rows of hist_out from the partial records of the history nodes: one lane per (problem, node), problem fastest, lane
+// e0 + ... of B * NJ; the chunks added in ascending order, the expressions of f_disperse_stats
+__global__ __launch_bounds__(SW) void f_history_stats(const ascent_params *__restrict__ P, long batch, int K, int nwg, int stride, int nj,
+                                                      long e0, const double *__restrict__ blob, const double *__restrict__ traj,
+                                                      const double *__restrict__ partial, double *__restrict__ hist) {
+  const long e = e0 + (long)blockIdx.x * SW + threadIdx.x;
+  if (e >= batch * nj) return;
+  const int i = (int)(e / batch);
+  const long p = e - (long)i * batch;
+  const size_t B = (size_t)batch;
+  const int j = (i + 1) * stride < K ? (i + 1) * stride : K;
+  const double *pr = partial + ((size_t)i * HREC) * B + p;      // chunk c: + c * nj * HREC * B
+  const size_t cs = (size_t)nj * HREC * B;
+  double *out = hist + (size_t)i * B + p;                       // row r: + r * nj * B
+  const size_t rs = (size_t)nj * B;
+  double nom[HQ];
+  history_nominal(traj + p, blob + p, reinterpret_cast<const double *>(P + p), B, K, j, nom);
+  double n = 0.0, nc = 0.0;
+  for (int c = 0; c < nwg; c++) {
+    n += pr[c * cs + (size_t)H_N * B];
+    nc += pr[c * cs + (size_t)H_CLIP * B];
+  }
+  out[HO_N * rs] = n;
+  out[HO_CLIP * rs] = nc;
+  ASC_UNROLL
+  for (int q = 0; q < HQ; q++) {
+    double a = 0.0, sq = 0.0, lo = INFINITY, hi = -INFINITY;
+    for (int c = 0; c < nwg; c++) {
+      a += pr[c * cs + (size_t)(H_SUM + q) * B];
+      sq += pr[c * cs + (size_t)(H_SQ + q) * B];
+      lo = fmin(lo, pr[c * cs + (size_t)(H_MIN + q) * B]);
+      hi = fmax(hi, pr[c * cs + (size_t)(H_MAX + q) * B]);
+    }
+    out[(HO_NOM + q) * rs] = nom[q];
+    out[(HO_MEAN + q) * rs] = n == 1.0 ? lo : (finite1(nom[q]) ? nom[q] : 0.0) + a / n;
+    out[(HO_VAR + q) * rs] = n >= 2.0 ? (sq - a * a / n) / (n - 1.0) : NAN;
+    out[(HO_MIN + q) * rs] = n > 0.0 ? lo : NAN;
+    out[(HO_MAX + q) * rs] = n > 0.0 ? hi : NAN;
+  }
+}
+
 int groups_per_problem(int samples) { return (samples + DB - 1) / DB; }
 // below 193 samples a workgroup holds only the wavefronts that fly: whole wavefronts, so the butterflies see 64 lanes
 int threads_per_group(int samples) { return samples >= DB ? DB : (samples + 63) / 64 * 64; }
 
 }  // namespace
 
-size_t disperse_ws_bytes(int K, long batch, int samples) {
-  return flight_ws_bytes(K, batch) + (size_t)groups_per_problem(samples) * NREC * (size_t)batch * sizeof(double);
+int history_nodes(int K, int node_stride) { return K / node_stride + (K % node_stride != 0); }
+
+size_t disperse_ws_bytes(int K, long batch, int samples, int node_stride) {
+  const size_t nj = node_stride > 0 ? (size_t)history_nodes(K, node_stride) : 0;
+  return flight_ws_bytes(K, batch) + (size_t)groups_per_problem(samples) * (NREC + nj * HREC) * (size_t)batch * sizeof(double);
 }
 
 template <int FORM>
 static void disperse_launch(const Call &c, DisperseKind kind, dim3 grid, dim3 block, int substeps, int samples, int nwg, long g0,
                             const DisperseIO &io, const FlightWs &w) {
   double *partial = w.rest;
-  if (kind == DISPERSE_OPEN)
-    hipLaunchKernelGGL((f_disperse<FORM>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob, w.traj,
-                       w.fsum, io.xi, io.sigma, io.sigma_u, partial, io.samples_out);
+  if (io.hist) {      // the history: the partial records of the nodes follow the end records
+    const HistArgs h{io.node_stride, history_nodes(c.K, io.node_stride), partial + (size_t)nwg * NREC * c.batch, io.hist_samples};
+    if (kind == DISPERSE_OPEN)
+      hipLaunchKernelGGL((f_disperse<FORM, true>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob,
+                         w.traj, w.fsum, io.xi, io.sigma, io.sigma_u, partial, io.samples_out, h);
+    else
+      hipLaunchKernelGGL((f_history_guided<FORM>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob,
+                         w.traj, w.fsum, io.xi, io.sigma, io.sigma_u, io.gain_u, io.gain_t, io.stretch_max,
+                         NavArgs{io.ff_u, io.ff_t, io.ff_know, io.xi_nav, io.sigma_nav}, partial, io.samples_out, h);
+  } else if (kind == DISPERSE_OPEN)
+    hipLaunchKernelGGL((f_disperse<FORM, false>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob, w.traj,
+                       w.fsum, io.xi, io.sigma, io.sigma_u, partial, io.samples_out, HistArgs{});
   else if (kind == DISPERSE_GUIDED)
     hipLaunchKernelGGL((f_disperse_guided<FORM>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob,
                        w.traj, w.fsum, io.xi, io.sigma, io.sigma_u, io.gain_u, io.gain_t, io.stretch_max, partial, io.samples_out);
@@ -439,6 +645,16 @@ int disperse_run(const Call &c, DisperseKind kind, int substeps, int samples, co
   const dim3 gst((unsigned)((c.batch + SW - 1) / SW)), bst(SW);
   hipLaunchKernelGGL(f_disperse_stats, gst, bst, 0, c.stream, c.batch, c.K, nwg, w.traj, w.fsum, w.rest, io.stats);
   ASC_CHK(c.err, c.errlen, hipGetLastError());
+  if (io.hist) {
+    const int nj = history_nodes(c.K, io.node_stride);
+    const long lanes = c.batch * nj, per = MAX_GRID * SW;
+    for (long e0 = 0; e0 < lanes; e0 += per) {
+      const long left = lanes - e0 < per ? lanes - e0 : per;
+      hipLaunchKernelGGL(f_history_stats, dim3((unsigned)((left + SW - 1) / SW)), bst, 0, c.stream, c.dp, c.batch, c.K, nwg,
+                         io.node_stride, nj, e0, io.blob, w.traj, w.rest + (size_t)nwg * NREC * c.batch, io.hist);
+      ASC_CHK(c.err, c.errlen, hipGetLastError());
+    }
+  }
   return ASCENT_OK;
 }
 

@@ -843,9 +843,11 @@ class BlobCall {
   double *ws = nullptr;              // the analysis workspace, where the call claimed one
 };
 
-// ascent_disperse_batch, ascent_disperse_guided_batch and ascent_disperse_navigated_batch: io holds the caller's pointers
+// ascent_disperse_batch, ascent_disperse_guided_batch and ascent_disperse_navigated_batch: io holds the caller's pointers.
+// history: ascent_disperse_history_batch, the kind picked from gain_u by the entry point; its own refusals stand after the
+// refusals the three share, each of which keeps its place and its text.
 int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, int32_t samples, DisperseKind kind,
-                  DisperseIO io, int device_id, void *stream_, int ptr_is_device) {
+                  DisperseIO io, int device_id, void *stream_, int ptr_is_device, bool history = false) {
   BlobCall b(p, batch, o, io.blob, stream_, ptr_is_device);
   int rc = b.options();
   if (rc) return rc;
@@ -855,7 +857,16 @@ int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, i
   if ((rc = check_samples(samples))) return rc;
   if ((io.xi_nav != nullptr) != (io.sigma_nav != nullptr)) { snprintf(g_err, sizeof g_err, "xi_nav and sigma_nav come together"); return ASCENT_E_ARG; }
   if (io.ff_know && !io.ff_u) { snprintf(g_err, sizeof g_err, "ff_know needs ff_u"); return ASCENT_E_ARG; }
-  if ((rc = check_substeps(substeps)) || (rc = b.solvable()) || (rc = b.open(device_id, disperse_ws_bytes(o->n_nodes - 1, (long)batch, samples)))) return rc;
+  if ((rc = check_substeps(substeps))) return rc;
+  if (history) {
+    if (!io.hist) { snprintf(g_err, sizeof g_err, "null hist_out"); return ASCENT_E_ARG; }
+    if (io.node_stride < 1 || io.node_stride > o->n_nodes - 1) { snprintf(g_err, sizeof g_err, "node_stride out of range (1 .. K = %d)", o->n_nodes - 1); return ASCENT_E_ARG; }
+    if (!io.gain_u && (io.gain_t || io.stretch_max || io.ff_u || io.ff_t || io.ff_know || io.xi_nav || io.sigma_nav)) {
+      snprintf(g_err, sizeof g_err, "gain_t, stretch_max, ff_u, ff_t, ff_know, xi_nav and sigma_nav need gain_u");
+      return ASCENT_E_ARG;
+    }
+  }
+  if ((rc = b.solvable()) || (rc = b.open(device_id, disperse_ws_bytes(o->n_nodes - 1, (long)batch, samples, history ? io.node_stride : 0)))) return rc;
   Staging &st = b.st;
   const size_t K = (size_t)b.K, B = (size_t)batch, S = (size_t)samples;
   io.blob = b.blob;
@@ -871,7 +882,12 @@ int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, i
   io.xi_nav = st.in(io.xi_nav, ASCENT_NAV_ROWS * S);
   io.sigma_nav = st.in(io.sigma_nav, ASCENT_NAV_ROWS * B);
   io.stats = st.out(io.stats, ASCENT_DISPERSE_STAT_ROWS * B);
-  io.samples_out = st.out(io.samples_out, (kind == DISPERSE_OPEN ? ASCENT_DISPERSE_ROWS : ASCENT_GUIDED_SAMPLE_ROWS) * S * B);
+  io.samples_out = st.out(io.samples_out, (kind == DISPERSE_OPEN && !history ? ASCENT_DISPERSE_ROWS : ASCENT_GUIDED_SAMPLE_ROWS) * S * B);
+  if (history) {
+    const size_t NJ = (size_t)history_nodes(b.K, io.node_stride);
+    io.hist = st.out(io.hist, ASCENT_HISTORY_ROWS * NJ * B);
+    io.hist_samples = st.out(io.hist_samples, ASCENT_HISTORY_QUANTITIES * NJ * S * B);
+  }
   if ((rc = b.st.failed()) || (rc = disperse_run(b.c, kind, substeps, samples, io, b.ws))) return rc;
   return b.close();
 }
@@ -1011,6 +1027,21 @@ int ascent_disperse_navigated_batch(const ascent_params *p, int64_t batch, const
   io.ff_u = ff_u; io.ff_t = ff_t; io.ff_know = ff_know; io.xi_nav = xi_nav; io.sigma_nav = sigma_nav;
   io.stats = stats_out; io.samples_out = samples_out;
   return disperse_call(p, batch, o, substeps, samples, DISPERSE_NAVIGATED, io, device_id, stream_, ptr_is_device);
+}
+
+int ascent_disperse_history_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                                  int32_t samples, const double *xi, const double *sigma, const double *sigma_u, const double *gain_u,
+                                  const double *gain_t, const double *stretch_max, const double *ff_u, const double *ff_t,
+                                  const double *ff_know, const double *xi_nav, const double *sigma_nav, int32_t node_stride,
+                                  double *stats_out, double *samples_out, double *hist_out, double *hist_samples_out, int device_id,
+                                  void *stream_, int ptr_is_device) {
+  DisperseIO io{};
+  io.blob = sol_blob; io.xi = xi; io.sigma = sigma; io.sigma_u = sigma_u;
+  io.gain_u = gain_u; io.gain_t = gain_t; io.stretch_max = stretch_max;
+  io.ff_u = ff_u; io.ff_t = ff_t; io.ff_know = ff_know; io.xi_nav = xi_nav; io.sigma_nav = sigma_nav;
+  io.stats = stats_out; io.samples_out = samples_out;
+  io.node_stride = node_stride; io.hist = hist_out; io.hist_samples = hist_samples_out;
+  return disperse_call(p, batch, o, substeps, samples, gain_u ? DISPERSE_NAVIGATED : DISPERSE_OPEN, io, device_id, stream_, ptr_is_device, true);
 }
 
 int ascent_kkt_step(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,

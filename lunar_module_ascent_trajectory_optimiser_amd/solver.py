@@ -156,6 +156,7 @@ class DispersionResult:
     effort: np.ndarray | None = None    # (batch, samples, 3) guided flights with keep_samples: EFFORT_ROWS
     xi_nav: np.ndarray | None = None    # (8, samples) the navigation draws (ascent_disperse_navigated_batch), shared by every problem
     nav_sigma: np.ndarray | None = None     # (batch, 8): 7 state-knowledge biases (scaled units), the error of theta-hat
+    history: "DispersionHistory | None" = None      # disperse_batch(history=...): the statistics at the nodes on the way
 
     @property
     def std(self) -> np.ndarray:
@@ -183,6 +184,37 @@ class DispersionResult:
         A = np.concatenate(A, axis=2)
         C = np.atleast_2d(np.cov(draws))
         return np.einsum("bqc,cd,brd->bqr", A, C, A)
+
+
+HISTORY_ROWS = ("x", "y", "xdot", "ydot", "angle", "angledot", "mass", "altitude", "control", "correction")
+
+
+@dataclasses.dataclass
+class DispersionHistory:
+    """The dispersion corridor of a flight (disperse_batch(history=...); include/ascent.h: ascent_disperse_history_batch): the
+    statistics over the samples of the ten quantities HISTORY_ROWS -- the flown state in scaled units, the altitude in metres,
+    the executed control and the feedback's correction of the step that ends at the node -- at every stride-th node and the last.
+    A sample is valid at a node if its ten quantities there are finite (an escaping sample is valid here).  Problem index first."""
+    nodes: np.ndarray               # (NJ,) the node numbers, 1-based (node 0 is not reported); the last one is K
+    n_valid: np.ndarray             # (batch, NJ)
+    nominal: np.ndarray             # (batch, NJ, 10) the unperturbed flight: fly_batch's trajectory, the blob's control, correction 0
+    mean: np.ndarray                # (batch, NJ, 10)
+    var: np.ndarray                 # (batch, NJ, 10) unbiased; NaN where n_valid < 2
+    min: np.ndarray                 # (batch, NJ, 10) NaN where n_valid = 0
+    max: np.ndarray                 # (batch, NJ, 10)
+    clipped: np.ndarray             # (batch, NJ) valid samples whose command of the step was clipped; 0 in open loop
+    samples: np.ndarray | None      # (batch, samples, NJ, 10) every sample's quantities (keep_history_samples=True)
+
+    @property
+    def std(self) -> np.ndarray:
+        """(batch, NJ, 10)"""
+        return np.sqrt(self.var)
+
+
+def history_nodes(K: int, stride: int) -> np.ndarray:
+    """The 1-based nodes a history of this stride reports: every stride-th and always node K."""
+    nj = K // stride + (K % stride != 0)
+    return np.minimum((np.arange(nj) + 1) * stride, K)
 
 
 EFFORT_ROWS = ("clipped_steps", "max_feedback", "stretch")
@@ -494,7 +526,8 @@ def trim_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, t
 def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, control_sigma=None, tf_sigma=None, z0_sigma=None,
                    samples: int = 256, seed: int = 0, xi=None, keep_samples: bool = False, scheme=0, formulation=0, terminal=0,
                    move_penalty: bool = False, substeps: int = 0, device: int = 0, guidance: GuidanceResult | None = None,
-                   nav_sigma=None, knowledge_sigma=None, xi_nav=None, nav_seed: int = 1) -> DispersionResult:
+                   nav_sigma=None, knowledge_sigma=None, xi_nav=None, nav_seed: int = 1, history=False,
+                   keep_history_samples: bool = False) -> DispersionResult:
     """Monte Carlo dispersion (include/ascent.h: ascent_disperse_batch): every blob's control flown `samples` times on the
     device as fly_batch flies it, with the initial state, the 16 parameter fields, t_f and every control perturbed by
     sigma * xi, and the nine end quantities reduced on the device to count, mean, covariance and extrema.  The blob is shared
@@ -509,8 +542,19 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     Where `guidance` carries a feed-forward (ff_u, ff_t, ff_know; guidance_gains(feedforward=...)) or a navigation error is given,
     the call is ascent_disperse_navigated_batch: nav_sigma (7,) or (batch, 7), scaled units, the 1-sigma bias of each sample's state
     knowledge; knowledge_sigma a scalar or (batch,), the 1-sigma error of theta-hat in the units of theta; xi_nav (8, samples) their
-    draws, None draws np.random.default_rng(nav_seed).standard_normal((8, samples))."""
+    draws, None draws np.random.default_rng(nav_seed).standard_normal((8, samples)).
+    history: True, or a node stride in 1 .. K: the same flight through ascent_disperse_history_batch, and `history` of the result a
+    DispersionHistory of every stride-th node and the last; everything else of the result has the bits of the call without it.
+    keep_history_samples: also every sample's ten quantities at those nodes (the one array of size samples x K).  False: the
+    entry points above, exactly as without the keyword."""
     L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
+    stride = 0
+    if history is not False and history is not None:
+        stride = 1 if history is True else int(history)
+        if not 1 <= stride <= K:
+            raise ValueError(f"history: the node stride must be in 1 .. K = {K}")
+    elif keep_history_samples:
+        raise ValueError("keep_history_samples needs history")
     if xi is None:
         xi = np.random.default_rng(seed).standard_normal((24 + K, int(samples)))
     xi = np.ascontiguousarray(xi, dtype=np.float64)
@@ -523,13 +567,25 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     sig = np.ascontiguousarray(np.concatenate([zs, ps, ts], axis=1).T)
     sig_u = np.ascontiguousarray(us.T) if control_sigma is not None else None
     stats = np.empty((82, B))
-    smp = np.empty((9 if guidance is None else 12, S, B)) if keep_samples else None
+    smp = np.empty((9 if guidance is None and not stride else 12, S, B)) if keep_samples else None
+    hist = hsmp = None
+    if stride:
+        NJ = len(history_nodes(K, stride))
+        hist = np.empty((52, NJ, B))
+        hsmp = np.empty((10, NJ, S, B)) if keep_history_samples else None
+
+    def with_history(*a):      # the arguments from gain_u to sigma_nav, as the navigated call takes them
+        _lib.check(L.ascent_disperse_history_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
+                                                   *[_ptr(x) for x in a], stride, _ptr(stats), _ptr(smp), _ptr(hist), _ptr(hsmp),
+                                                   device, None, 0))
     ffu = getattr(guidance, "ff_u", None)
     navigated = ffu is not None or nav_sigma is not None or knowledge_sigma is not None
     if navigated and guidance is None:
         raise ValueError("nav_sigma and knowledge_sigma need guidance")
     nav_s = None
-    if guidance is None:
+    if guidance is None and stride:
+        with_history(*[None] * 8)
+    elif guidance is None:
         _lib.check(L.ascent_disperse_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
                                            _ptr(stats), _ptr(smp), device, None, 0))
     else:
@@ -540,7 +596,9 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
         if gt is not None and gt.shape != (7, B):
             raise ValueError(f"guidance.gain_t must have shape {(B, 7)}")
         sm = None if gt is None else _sigma_rows(np.asarray(guidance.stretch_max, dtype=np.float64)[..., None], 1, B, "stretch_max")[:, 0].copy()
-        if not navigated:
+        if not navigated and stride:
+            with_history(gu, gt, sm, None, None, None, None, None)
+        elif not navigated:
             _lib.check(L.ascent_disperse_guided_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
                                                       _ptr(gu), _ptr(gt), _ptr(sm), _ptr(stats), _ptr(smp), device, None, 0))
         else:
@@ -571,15 +629,25 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
                     raise ValueError(f"xi_nav must have shape (8, samples) = {(8, S)}")
             else:
                 xi_nav = None
-            _lib.check(L.ascent_disperse_navigated_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
-                                                         _ptr(gu), _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(xi_nav), _ptr(sn),
-                                                         _ptr(stats), _ptr(smp), device, None, 0))
+            if stride:
+                with_history(gu, gt, sm, fu, ft, fk, xi_nav, sn)
+            else:
+                _lib.check(L.ascent_disperse_navigated_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
+                                                             _ptr(gu), _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(xi_nav), _ptr(sn),
+                                                             _ptr(stats), _ptr(smp), device, None, 0))
     st = stats.T
+    hres = None
+    if stride:
+        h = hist.transpose(2, 1, 0)      # (batch, NJ, 52)
+        hres = DispersionHistory(history_nodes(K, stride), h[:, :, 0].astype(np.int64), np.ascontiguousarray(h[:, :, 1:11]),
+                                 np.ascontiguousarray(h[:, :, 11:21]), np.ascontiguousarray(h[:, :, 21:31]),
+                                 np.ascontiguousarray(h[:, :, 31:41]), np.ascontiguousarray(h[:, :, 41:51]), h[:, :, 51].astype(np.int64),
+                                 None if hsmp is None else np.ascontiguousarray(hsmp.transpose(3, 2, 1, 0)))
     return DispersionResult(st[:, 0].astype(np.int64), np.ascontiguousarray(st[:, 1:10]), np.ascontiguousarray(st[:, 10:19]),
                             _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
                             None if smp is None else np.ascontiguousarray(smp[:9].transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us,
                             None if smp is None or guidance is None else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)),
-                            xi_nav if nav_s is not None else None, nav_s)
+                            xi_nav if nav_s is not None else None, nav_s, hres)
 
 
 def guidance_gains(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,
