@@ -91,7 +91,11 @@ typedef struct ascent_opts {
                                becomes the eighth state of a stage, the pair reduces to one pivot); scheme 2: dense-block path.
                                With formulation 1 (the v1 script's angle.DCOST, PDF p26; scheme 0): the penalty is on the angle,
                                i.e. weight dcost * angle_ub / 2 on the normalised control, which starts from -1 (angle 0).
-                               Needs dcost > 0 for every problem                                                     */
+                               Needs dcost > 0 for every problem.  Host-resident parameters (ptr_is_device = 0): a dcost that is
+                               not positive (zero, negative, NaN) is refused for the whole call, ASCENT_E_ARG.  Device-resident
+                               parameters are not read by the host: the kernels that set the starting point check the weight, and
+                               such a problem is not iterated -- status ASCENT_INVALID_PROBLEM, 0 iterations, and tf, traj and blob
+                               hold its starting point (all finite); the other problems of the batch are solved as without it */
   int32_t reserved;     /* 0 */
 } ascent_opts;
 
@@ -111,7 +115,8 @@ enum ascent_problem_status {   /* values written to status_out[] */
   ASCENT_CONVERGED = 0,
   ASCENT_MAX_ITER = 1,
   ASCENT_LINESEARCH_FAILED = 2,
-  ASCENT_REGULARISATION_FAILED = 3   /* numerical breakdown: inertia could not be corrected */
+  ASCENT_REGULARISATION_FAILED = 3,  /* numerical breakdown: inertia could not be corrected */
+  ASCENT_INVALID_PROBLEM = 4         /* move_penalty = 1 with a dcost that is not positive (device-resident parameters): not iterated */
 };
 
 /* Row counts of the SoA arrays, K = n_nodes-1 (node 0 is fixed by the initial conditions,
@@ -569,6 +574,17 @@ int ascent_disperse_history_batch(const ascent_params *p, int64_t batch, const a
 int ascent_kkt_solve(int64_t batch, int32_t n_nodes, int32_t bs, int32_t nb, const double *diag, const double *lower,
                      const double *upper, const double *border, const double *border_diag, const double *rhs,
                      double *sol, int device_id, int algo);
+
+/* Test hook: the lane reductions of the persistent kernels on caller data (host pointers).  in: n records of 64 doubles, one
+ * wavefront each; out: [n][ASCENT_REDUCE_PROBE_ROWS][64], per lane
+ *   rows 0-2   sum / max / min over the lane's row of 16 lanes, by the DPP helpers the kernels use
+ *   rows 3-5   the same by the __shfl_xor butterflies they replaced
+ *   rows 6-8   sum / max / min over the wavefront by the helpers (DPP inside a row, shuffles across rows)
+ *   rows 9-11  the same by shuffles alone
+ *   rows 12,13 the inclusive prefix sum over the lane's row of 16: on DPP row shifts, and with __shfl_up
+ * The two versions of each quantity agree bit for bit (NaN where either is NaN): tests/test_gpu_reduce_probe.py. */
+#define ASCENT_REDUCE_PROBE_ROWS 14
+int ascent_reduce_probe(const double *in, int64_t n, double *out, int device_id);
 
 /* Device time (ms) of the solve kernel of the most recent ascent_solve_batch on this device,
  * measured with HIP events recorded on the launch stream around the kernel; waits for that

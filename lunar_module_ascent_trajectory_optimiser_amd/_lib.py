@@ -35,7 +35,9 @@ SYMBOLS = ("ascent_version", "ascent_device_count", "ascent_strerror", "ascent_s
            "ascent_dense_records", "ascent_coast_batch", "ascent_kkt_solve", "ascent_last_kernel_ms", "ascent_default_path",
            "ascent_workspace_layout", "ascent_param_sensitivity", "ascent_fly_batch", "ascent_flight_jacobian",
            "ascent_trim_batch", "ascent_disperse_batch", "ascent_guidance_gains", "ascent_disperse_guided_batch",
-           "ascent_guidance_feedforward", "ascent_disperse_navigated_batch", "ascent_disperse_history_batch")
+           "ascent_guidance_feedforward", "ascent_disperse_navigated_batch", "ascent_disperse_history_batch",
+           "ascent_reduce_probe")
+REDUCE_PROBE_ROWS = 14     # ASCENT_REDUCE_PROBE_ROWS
 PATHS = {"auto": 0, "fused": 1, "split_lane": 2, "split_wide": 3, "dense": 4, "persist": 5}     # enum ascent_path
 
 _lib = None
@@ -136,6 +138,8 @@ def load():
     L.ascent_dense_records.argtypes = [C.c_void_p, C.c_int64, C.POINTER(AscentOptsC), C.c_void_p, C.c_void_p, C.c_int]
     L.ascent_kkt_solve.restype = C.c_int
     L.ascent_kkt_solve.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int, C.c_int]
+    L.ascent_reduce_probe.restype = C.c_int
+    L.ascent_reduce_probe.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
     L.ascent_coast_batch.restype = C.c_int
     L.ascent_coast_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int, C.c_void_p, C.c_int]

@@ -155,7 +155,8 @@ __global__ __launch_bounds__(WAVE) void d_init(const ascent_params *params, long
   if (g.dc) {      // slacks of the movement equation around the guess's own movement; multipliers that zero their stationarity rows
     double up = (k > 0 && warm) ? guess[(7L * K + k - 1) * batch + p] : 0.0;
     if (k > 0 && !probe) up = push_in(up, -1.0, 1.0);
-    const double dl = u - up, eps = warm ? 1e-4 : 1e-2, dc = params[p].dcost;
+    // (a weight that is not positive: a harmless one; the NLP is refused below and never iterated)
+    const double dl = u - up, eps = warm ? 1e-4 : 1e-2, dc = params[p].dcost > 0.0 ? params[p].dcost : 1.0;
     it[O_LU * K + k] = 0.0;
     it[O_PP * K + k] = fmax(dl, 0.0) + eps; it[O_PN * K + k] = fmax(-dl, 0.0) + eps;
     it[O_ZP * K + k] = dc; it[O_ZN * K + k] = dc;
@@ -188,6 +189,8 @@ __global__ __launch_bounds__(WAVE) void d_init(const ascent_params *params, long
   sc[X_STATE] = ST_TRIAL; sc[X_FIRST] = 1.0; sc[X_STATUS] = ASCENT_MAX_ITER;
   sc[X_MU] = probe ? probe_mu[p] : ((asked_warm && !warm) ? 0.1 : mu_init);
   sc[X_NUP] = 1.0;
+  // move penalty with a weight that is not positive (NaN included): refused per problem -- the starting point, 0 iterations, status 4
+  if (g.dc && !(params[p].dcost > 0.0)) { sc[X_STATE] = ST_DONE; sc[X_STATUS] = ASCENT_INVALID_PROBLEM; }
 }
 
 // ==============================================================================================================

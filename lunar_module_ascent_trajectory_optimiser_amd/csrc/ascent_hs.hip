@@ -471,12 +471,7 @@ ASC_PASS double hs_eval_forward(const ldbl *dp, const gdbl *it, const gdbl *gain
     x0m = -rc[IM];
   }
   // dz_m: inclusive prefix sum of x0_m over the nodes of the NLP (the chunk here, the chunks before in carry_m)
-  double incl = x0m;
-  ASC_UNROLL
-  for (int sft = 1; sft < (WIDE ? 64 : 16); sft *= 2) {
-    const double t = __shfl_up(incl, sft, WIDE ? 64 : 16);
-    if (nl >= sft) incl += t;
-  }
+  const double incl = scanW<WIDE>(x0m, nl);
   const double dzm_k = carry_m + incl, dzm_p = dzm_k - x0m;
   carry_m += WIDE ? __shfl(incl, HCW - 1) : bcast16<HCH - 1>(incl);
   if (on) {

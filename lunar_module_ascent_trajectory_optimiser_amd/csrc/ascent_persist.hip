@@ -51,6 +51,10 @@ namespace {
 // Move penalty: the slack pair of the movement equation u_k - u_{k-1} = p_k - n_k at a starting point -- around the guess's own
 // movement (u, up: the pushed controls of nodes k and k-1), multipliers that zero the pair's stationarity rows
 // (d_init of the dense-block path, solve_one of the C restatement)
+// A weight the move penalty cannot take (zero, negative, NaN: z_p = z_n = dcw would start on or outside the boundary).  Such an NLP
+// is given a harmless pair weight, ST_DONE and ASCENT_INVALID_PROBLEM by p_init and keeps them through p_transfer: it reports its
+// starting point, 0 iterations and status 4 without a round spent on it -- and without a host read of device-resident parameters.
+ASC_DEV bool bad_weight(const ascent_params &prm) { return !(prm.dcost > 0.0); }
 ASC_DEV void start_move(double *w, int Kp, int k, double u, double up, bool warm, double dcw) {
   const double dl = u - up, eps = warm ? 1e-4 : 1e-2;
   w[(R_IT + O_LU) * Kp + k] = 0.0;
@@ -151,7 +155,7 @@ __global__ __launch_bounds__(WAVE) void p_init(const ascent_params *params, long
     const double ha = 0.5 * d.aub, f0 = (double)kk / K * 0.5;             // (cold start: the straight-line guess of node kk-1)
     double up = kk == 0 ? (g.form == 1 ? -1.0 : 0.0) : warm ? guess[(7L * K + kk - 1) * batch + p] : (g.form == 1 ? f0 / ha - 1.0 : 0.0);
     if (kk > 0 && !probe) up = push_in(up, -1.0, 1.0);
-    start_move(w, Kp, k, u, up, warm != 0, g.form == 1 ? params[p].dcost * ha : params[p].dcost);
+    start_move(w, Kp, k, u, up, warm != 0, bad_weight(params[p]) ? 1.0 : g.form == 1 ? params[p].dcost * ha : params[p].dcost);
   }
   if (k != K - 1) return;
   double *sc = w + (size_t)g.nrows() * Kp;
@@ -168,6 +172,7 @@ __global__ __launch_bounds__(WAVE) void p_init(const ascent_params *params, long
   sc[X_STATE] = ST_TRIAL; sc[X_FIRST] = 1.0; sc[X_STATUS] = ASCENT_MAX_ITER;
   sc[X_MU] = (asked_warm && !warm) ? 0.1 : mu_init; sc[X_NUP] = 1.0;
   if (probe) { sc[X_MU] = probe_mu[p]; sc[X_PDW] = probe_dw[p]; sc[X_PROBE] = (double)probe_kind; }
+  if (g.mp && bad_weight(params[p])) { sc[X_STATE] = ST_DONE; sc[X_STATUS] = ASCENT_INVALID_PROBLEM; }      // never iterated: p_solve skips it
 }
 
 // Nested iteration, from one grid to the next finer one without leaving the kernel's own layout: the converged primal-dual
@@ -184,6 +189,7 @@ __global__ __launch_bounds__(WAVE) void p_transfer(const ascent_params *params, 
   double *wf = wsf + (size_t)p * gf.nlp_doubles();
   const Der d = derive_t(params[p], gf.term);
   const int warm = (int)scc[X_STATUS] == ASCENT_CONVERGED ? 2 : 0;
+  const bool invalid = (int)scc[X_STATUS] == ASCENT_INVALID_PROBLEM;      // refused by p_init: stays refused, at a cold start of this grid
   const double *ic = wc + (size_t)((int)scc[X_CUR] * gc.nit()) * Kpc;
   double z[7], l[7], zb[6], u = 0.0, up = 0.0;
   const int kk = k < Kf ? k : Kf - 1;
@@ -222,7 +228,7 @@ __global__ __launch_bounds__(WAVE) void p_transfer(const ascent_params *params, 
   if (gf.mp) {
     if (kk == 0) up = gf.form == 1 ? -1.0 : 0.0;
     else if (!warm && gf.form == 1) up = push_in((double)kk / Kf * 0.5 / (0.5 * d.aub) - 1.0, -1.0, 1.0);      // (cold: the guess of node kk-1)
-    start_move(wf, Kpf, k, u, up, warm != 0, gf.form == 1 ? params[p].dcost * 0.5 * d.aub : params[p].dcost);
+    start_move(wf, Kpf, k, u, up, warm != 0, invalid ? 1.0 : gf.form == 1 ? params[p].dcost * 0.5 * d.aub : params[p].dcost);
   }
   if (k != Kf - 1) return;
   double *sc = wf + (size_t)gf.nrows() * Kpf;
@@ -234,6 +240,7 @@ __global__ __launch_bounds__(WAVE) void p_transfer(const ascent_params *params, 
   sc[X_STATE] = ST_TRIAL; sc[X_FIRST] = 1.0; sc[X_STATUS] = ASCENT_MAX_ITER;
   sc[X_MU] = warm ? mu : 0.1; sc[X_NUP] = 1.0;
   sc[X_ITB] = scc[X_ITB] + scc[X_ITERS];
+  if (invalid) { sc[X_STATE] = ST_DONE; sc[X_STATUS] = ASCENT_INVALID_PROBLEM; }
 }
 
 // Results in the external layouts ([field][node][NLP], NLP contiguous).  Lane = NLP, a block = 64 NLPs x one 16-node chunk, one
@@ -291,6 +298,23 @@ __global__ __launch_bounds__(WAVE * FIN_WAVES) void p_finish(const ascent_params
       for (int f = 0; f < 10; f++) traj[((long)f * nt + k + 1) * batch + p] = v[f];
     }
   }
+}
+
+// p_reduce_probe: see reduce_probe_run.  One wavefront per record: in[64], out[14][64].
+__global__ __launch_bounds__(WAVE) void p_reduce_probe(const double *in, long n, double *out) {
+  const long r = blockIdx.x;
+  if (r >= n) return;
+  const int lane = threadIdx.x;
+  const double v = in[r * WAVE + lane];
+  double *o = out + r * ASCENT_REDUCE_PROBE_ROWS * WAVE + lane;
+  const double s16 = gsum16_shfl(v), x16 = gmax16_shfl(v), n16 = gmin16_shfl(v);
+  o[0 * WAVE] = gsum16(v); o[1 * WAVE] = gmax16(v); o[2 * WAVE] = gmin16(v);
+  o[3 * WAVE] = s16; o[4 * WAVE] = x16; o[5 * WAVE] = n16;
+  o[6 * WAVE] = gsumW<1>(v); o[7 * WAVE] = gmaxW<1>(v); o[8 * WAVE] = gminW<1>(v);
+  { double t = s16; t += __shfl_xor(t, 16); t += __shfl_xor(t, 32); o[9 * WAVE] = t; }
+  { double t = x16; t = fmax(t, __shfl_xor(t, 16)); t = fmax(t, __shfl_xor(t, 32)); o[10 * WAVE] = t; }
+  { double t = n16; t = fmin(t, __shfl_xor(t, 16)); t = fmin(t, __shfl_xor(t, 32)); o[11 * WAVE] = t; }
+  o[12 * WAVE] = scan16(v, lane & 15); o[13 * WAVE] = scan_shfl<16>(v, lane & 15);
 }
 
 // p_probe_out: the Newton step one probe round left behind, in the external blob layout; inertia[p] = 1: refused
@@ -582,7 +606,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
               trial_node<SCHEME, FORM, MP, TERM>(d, K, Kp, k, n, dn, t, live, in, P);
             }
           }
-          P.template reduceW<MP, WIDE>();
+          P.template reduceW<MP, WIDE, MP>();
         }
         double rd = P.rd, cinf = P.cinf, pmin = P.pmin, pmax = P.pmax, l1 = P.l1, zsum = P.zsum;
         const double rth = 1.0 + P.rth, c1 = P.c1, sl = P.sl;
@@ -939,8 +963,8 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
       }
       // ---- border: the 2x2 Schur complement in (theta, nu3); inertia ---------------------------------------------------------
       const double U0 = bcast16<RL>(U), U1 = bcast16<RL + 1>(U), V1 = bcast16<RL + 1>(V), U2 = bcast16<RL + 2>(U), V2 = bcast16<RL + 2>(V);
-      k10 = gsumW<WIDE>(k10); k11 = gsumW<WIDE>(k11); k12 = gsumW<WIDE>(k12); k20 = gsumW<WIDE>(k20); k22 = gsumW<WIDE>(k22);
-      bad = (int)gmaxW<WIDE>((double)bad);
+      k10 = gsumW<WIDE, MP>(k10); k11 = gsumW<WIDE, MP>(k11); k12 = gsumW<WIDE, MP>(k12); k20 = gsumW<WIDE, MP>(k20); k22 = gsumW<WIDE, MP>(k22);
+      bad = (int)gmaxW<WIDE, MP>((double)bad);
       if (probe_rows) {
         if (act && role == 0) sc[X_STATE] = ST_DONE;
       } else if (act) {
@@ -1053,12 +1077,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             if constexpr (MP) du00 -= ka[7] * x0u;
           }
           // dz_m: inclusive prefix sum of x0_m over the nodes of the NLP (16 here, the chunks before in carry_m)
-          double incl = x0[IM];
-          ASC_UNROLL
-          for (int sft = 1; sft < CHN; sft *= 2) {
-            const double t = __shfl_up(incl, sft, CHN);
-            if (nl >= sft) incl += t;
-          }
+          const double incl = scanW<WIDE, MP>(x0[IM], nl);
           const double dzm_k = carry_m + incl, dzm_p = dzm_k - x0[IM];
           carry_m += WIDE ? __shfl(incl, 63) : bcast16<15>(incl);
           if (on) {
@@ -1217,10 +1236,10 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
           wsync();
           PROF(6);
         }
-        rmax = gmaxW<WIDE>(rmax); gsum = gsumW<WIDE>(gsum); adu = gminW<WIDE>(adu);
-        if constexpr (MP) { gmove = gsumW<WIDE>(gmove); clu = gsumW<WIDE>(clu); }
+        rmax = gmaxW<WIDE, MP>(rmax); gsum = gsumW<WIDE, MP>(gsum); adu = gminW<WIDE, MP>(adu);
+        if constexpr (MP) { gmove = gsumW<WIDE, MP>(gmove); clu = gsumW<WIDE, MP>(clu); }
         ASC_UNROLL
-        for (int i = 0; i < 7; i++) dzK[i] = gsumW<WIDE>(dzK[i]);          // only the lane of the last node holds non-zeros
+        for (int i = 0; i < 7; i++) dzK[i] = gsumW<WIDE, MP>(dzK[i]);          // only the lane of the last node holds non-zeros
         // ---- the scalars of the step and the step lengths: known once the primal step is (the adjoint below only adds the
         //      multiplier steps), so that the adjoint phase can evaluate the first trial point of the line search as it goes ----
         double zK[7];
@@ -1416,9 +1435,9 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
           }
           PROF(0);
         }
-        P.template reduceW<MP, WIDE>();
+        P.template reduceW<MP, WIDE, MP>();
         // ---- scalars of the step, merit bookkeeping -------------------------------------------------------------------------
-        ccl = gsumW<WIDE>(ccl);
+        ccl = gsumW<WIDE, MP>(ccl);
         if (act) {
           cl += ccl;
           const Terminal &tm = tmK;
@@ -1575,6 +1594,15 @@ int persist_probe_rows(const Call &c, bool wide, double *ws, const ProbeIO &io) 
   launch_solve(c.scheme, c.form, 0, c.batch, c.stream, c.dp, g, ws, 1000, -1.0);
   hipLaunchKernelGGL(p_probe_rows_out, ng, dim3(WAVE), 0, c.stream, c.dp, c.batch, g, (const double *)ws, io.defects, io.jac, io.hess);
   ASC_CHK(c.err, c.errlen, hipGetLastError());
+  return ASCENT_OK;
+}
+
+// Test hook (ascent_reduce_probe): the reductions and the scan of ascent_persist_dev.hpp on caller data, one wavefront per 64 inputs.
+// Rows of an output record: 0-2 sum / max / min over each 16 lanes by the DPP helpers, 3-5 by the shuffle versions; 6-8 over the
+// wavefront by the helpers (gsumW<1> ...), 9-11 by shuffles alone; 12 the inclusive 16-lane scan on DPP, 13 with __shfl_up.
+int reduce_probe_run(const double *in, long n, double *out, hipStream_t stream, char *err, size_t errlen) {
+  hipLaunchKernelGGL(p_reduce_probe, dim3((unsigned)n), dim3(WAVE), 0, stream, in, n, out);
+  ASC_CHK(err, errlen, hipGetLastError());
   return ASCENT_OK;
 }
 

@@ -31,6 +31,10 @@ int persist_probe(const Call &c, bool wide, double *ws, const ProbeIO &io);
 // leaves in LDS for its factorisation sweep, copied out instead of swept.  io.mu: `batch` zeros on the device.
 int persist_probe_rows(const Call &c, bool wide, double *ws, const ProbeIO &io);
 
+// Test hook: the 16-lane / wavefront reductions and the 16-lane scan of the persistent kernels on n records of 64 doubles (device
+// pointers), by the DPP helpers and by the shuffle versions they replaced: out[n][ASCENT_REDUCE_PROBE_ROWS][64].
+int reduce_probe_run(const double *in, long n, double *out, hipStream_t stream, char *err, size_t errlen);
+
 // Hermite-Simpson (scheme 2) in the same layout: ascent_hs.hip.  One launch = one grid level of the batch; the node arrays are padded to
 // chunks of hs_chunk_nodes(wide) nodes (12: four NLPs per wavefront, 48: one).
 void hs_launch_solve(long batch, hipStream_t stream, const ascent_params *dp, int K, int Kp, int nch, int term, int wide, double *w, int max_iter, double tol);

@@ -83,14 +83,59 @@ ASC_DEV void wsync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// reductions over the 16 lanes of an NLP (xor strides stay inside the row of 16)
-ASC_DEV double gsum16(double v) { v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8); return v; }
-ASC_DEV double gmax16(double v) { v = fmax(v, __shfl_xor(v, 1)); v = fmax(v, __shfl_xor(v, 2)); v = fmax(v, __shfl_xor(v, 4)); return fmax(v, __shfl_xor(v, 8)); }
-ASC_DEV double gmin16(double v) { v = fmin(v, __shfl_xor(v, 1)); v = fmin(v, __shfl_xor(v, 2)); v = fmin(v, __shfl_xor(v, 4)); return fmin(v, __shfl_xor(v, 8)); }
+// reductions over the 16 lanes of an NLP (xor strides stay inside the row of 16): the butterfly written with shuffles -- every stage an
+// LDS round trip (two ds_bpermute_b32 and a wait) on a chain of four.  Kept for p_solve without the move penalty (see gsumW below) and as
+// the reference of the reduce probe (ascent_reduce_probe).
+ASC_DEV double gsum16_shfl(double v) { v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8); return v; }
+ASC_DEV double gmax16_shfl(double v) { v = fmax(v, __shfl_xor(v, 1)); v = fmax(v, __shfl_xor(v, 2)); v = fmax(v, __shfl_xor(v, 4)); return fmax(v, __shfl_xor(v, 8)); }
+ASC_DEV double gmin16_shfl(double v) { v = fmin(v, __shfl_xor(v, 1)); v = fmin(v, __shfl_xor(v, 2)); v = fmin(v, __shfl_xor(v, 4)); return fmin(v, __shfl_xor(v, 8)); }
+// The same butterfly on DPP moves (v_mov_b32_dpp pairs: no LDS operation, no wait).  Stages 1 and 2 are the xor-1 and xor-2 exchanges
+// (quad_perm [1,0,3,2], [2,3,0,1]); after them the four lanes of a quad hold the same bits, so the mirrored partner of stage 3 (the
+// other quad of the half, row_half_mirror) and of stage 4 (the other half of the row, row_mirror) delivers the operand the xor-4 / xor-8
+// partner would: the results equal the shuffle versions' bit for bit (tests/test_gpu_reduce_probe.py).
+constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_ROW_SHR = 0x110, DPP_ROW_MIRROR = 0x140, DPP_HALF_MIRROR = 0x141;
+template <int CTRL>
+ASC_DEV double dpp16(double v) {
+  const long x = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(long, v), CTRL, 0xf, 0xf, false);
+  return __builtin_bit_cast(double, x);
+}
+ASC_DEV double gsum16(double v) { v += dpp16<DPP_XOR1>(v); v += dpp16<DPP_XOR2>(v); v += dpp16<DPP_HALF_MIRROR>(v); v += dpp16<DPP_ROW_MIRROR>(v); return v; }
+ASC_DEV double gmax16(double v) { v = fmax(v, dpp16<DPP_XOR1>(v)); v = fmax(v, dpp16<DPP_XOR2>(v)); v = fmax(v, dpp16<DPP_HALF_MIRROR>(v)); return fmax(v, dpp16<DPP_ROW_MIRROR>(v)); }
+ASC_DEV double gmin16(double v) { v = fmin(v, dpp16<DPP_XOR1>(v)); v = fmin(v, dpp16<DPP_XOR2>(v)); v = fmin(v, dpp16<DPP_HALF_MIRROR>(v)); return fmin(v, dpp16<DPP_ROW_MIRROR>(v)); }
+// inclusive prefix sum over the 16 lanes of an NLP (nl: the lane's index in its row): row_shr with the lane's own value as the old
+// operand, so that the lanes nl < sft, which have no source, keep theirs -- what __shfl_up with width 16 hands them
+template <int SFT>
+ASC_DEV double shr16(double v) {
+  const long x = __builtin_bit_cast(long, v);
+  const int lo = (int)x, hi = (int)(x >> 32);
+  const unsigned rlo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, DPP_ROW_SHR + SFT, 0xf, 0xf, false);
+  const unsigned rhi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, DPP_ROW_SHR + SFT, 0xf, 0xf, false);
+  return __builtin_bit_cast(double, (long)(((unsigned long)rhi << 32) | rlo));
+}
+ASC_DEV double scan16(double v, int nl) {
+  double t;
+  t = shr16<1>(v); if (nl >= 1) v += t;
+  t = shr16<2>(v); if (nl >= 2) v += t;
+  t = shr16<4>(v); if (nl >= 4) v += t;
+  t = shr16<8>(v); if (nl >= 8) v += t;
+  return v;
+}
+template <int W>      // (W = 16: the reference of the probe; W = 64: the scan of the one-NLP-per-wavefront form)
+ASC_DEV double scan_shfl(double v, int nl) {
+  ASC_UNROLL
+  for (int sft = 1; sft < W; sft *= 2) {
+    const double t = __shfl_up(v, sft, W);
+    if (nl >= sft) v += t;
+  }
+  return v;
+}
+template <int WIDE, int DPP = 1> ASC_DEV double scanW(double v, int nl) { if constexpr (WIDE) return scan_shfl<64>(v, nl); else if constexpr (DPP) return scan16(v, nl); else return scan_shfl<16>(v, nl); }
 // ... or over the whole wavefront (WIDE: one NLP per wavefront)
-template <int WIDE> ASC_DEV double gsumW(double v) { v = gsum16(v); if constexpr (WIDE) { v += __shfl_xor(v, 16); v += __shfl_xor(v, 32); } return v; }
-template <int WIDE> ASC_DEV double gmaxW(double v) { v = gmax16(v); if constexpr (WIDE) { v = fmax(v, __shfl_xor(v, 16)); v = fmax(v, __shfl_xor(v, 32)); } return v; }
-template <int WIDE> ASC_DEV double gminW(double v) { v = gmin16(v); if constexpr (WIDE) { v = fmin(v, __shfl_xor(v, 16)); v = fmin(v, __shfl_xor(v, 32)); } return v; }
+// (DPP = 0: the shuffle versions.  p_solve without the move penalty keeps them: with the DPP forms its register allocation moves -- 52 more
+//  AGPR copies in the adjoint chunk loop, +0.9 % on the unpenalised sweep -- while the penalised kernels and h_solve gain)
+template <int WIDE, int DPP = 1> ASC_DEV double gsumW(double v) { v = DPP ? gsum16(v) : gsum16_shfl(v); if constexpr (WIDE) { v += __shfl_xor(v, 16); v += __shfl_xor(v, 32); } return v; }
+template <int WIDE, int DPP = 1> ASC_DEV double gmaxW(double v) { v = DPP ? gmax16(v) : gmax16_shfl(v); if constexpr (WIDE) { v = fmax(v, __shfl_xor(v, 16)); v = fmax(v, __shfl_xor(v, 32)); } return v; }
+template <int WIDE, int DPP = 1> ASC_DEV double gminW(double v) { v = DPP ? gmin16(v) : gmin16_shfl(v); if constexpr (WIDE) { v = fmin(v, __shfl_xor(v, 16)); v = fmin(v, __shfl_xor(v, 32)); } return v; }
 
 template <typename PT>      // (a generic or an LDS pointer)
 ASC_DEV Scal lds_scal(PT sc, int r0) {
@@ -151,11 +196,11 @@ struct Part {
     l1 = gsum16(l1); zsum = gsum16(zsum); rth = gsum16(rth); c1 = gsum16(c1); sl = gsum16(sl);
     if constexpr (MP) mv = gsum16(mv);
   }
-  template <int MP, int WIDE>
+  template <int MP, int WIDE, int DPP = 1>
   ASC_DEV void reduceW() {
-    rd = gmaxW<WIDE>(rd); cinf = gmaxW<WIDE>(cinf); pmin = gminW<WIDE>(pmin); pmax = gmaxW<WIDE>(pmax);
-    l1 = gsumW<WIDE>(l1); zsum = gsumW<WIDE>(zsum); rth = gsumW<WIDE>(rth); c1 = gsumW<WIDE>(c1); sl = gsumW<WIDE>(sl);
-    if constexpr (MP) mv = gsumW<WIDE>(mv);
+    rd = gmaxW<WIDE, DPP>(rd); cinf = gmaxW<WIDE, DPP>(cinf); pmin = gminW<WIDE, DPP>(pmin); pmax = gmaxW<WIDE, DPP>(pmax);
+    l1 = gsumW<WIDE, DPP>(l1); zsum = gsumW<WIDE, DPP>(zsum); rth = gsumW<WIDE, DPP>(rth); c1 = gsumW<WIDE, DPP>(c1); sl = gsumW<WIDE, DPP>(sl);
+    if constexpr (MP) mv = gsumW<WIDE, DPP>(mv);
   }
 };
 struct TrialCtx {       // what the trial point of an NLP needs besides the node data

@@ -351,7 +351,7 @@ size_t ws_bytes(const Route &r, int K, int64_t batch, int mp) {
 int check_solvable(const ascent_params *p, int64_t batch, const ascent_opts *o, int ptr_is_device, Route *route_out = nullptr) {
   const Route r = route(o, batch, ASCENT_PATH_AUTO, false);
   if (const char *why = unsupported(r.path, o)) { snprintf(g_err, sizeof g_err, "%s", why); return ASCENT_E_ARG; }
-  // (device-resident parameter sets are the caller's to check: the weight must be positive)
+  // (device-resident parameter sets are not read here: p_init / d_init refuse a bad weight per problem, ASCENT_INVALID_PROBLEM)
   if (o->move_penalty && !ptr_is_device) if (const int rc = check_dcost(p, batch)) return rc;
   if (route_out) *route_out = r;
   return 0;
@@ -1047,6 +1047,20 @@ int ascent_disperse_history_batch(const ascent_params *p, int64_t batch, const a
 int ascent_kkt_step(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,
                     const double *mu, const double *delta_w, double *step, int32_t *inertia_out, int device_id) {
   return ascent_kkt_step_path(p, batch, o, iterate, mu, delta_w, step, inertia_out, device_id, ASCENT_PATH_AUTO);
+}
+
+int ascent_reduce_probe(const double *in, int64_t n, double *out, int device_id) {
+  if (!in || !out || n <= 0 || n > 65535) { snprintf(g_err, sizeof g_err, "ascent_reduce_probe: null pointer or n outside 1 .. 65535"); return ASCENT_E_ARG; }
+  int rc = check_device(device_id);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(g_mu[device_id]);
+  HIPCHK(hipSetDevice(device_id));
+  Staging st(nullptr, 0);
+  const double *din = st.in(in, (size_t)n * WAVE);
+  double *dout = st.out(out, (size_t)n * ASCENT_REDUCE_PROBE_ROWS * WAVE);
+  if ((rc = st.failed())) return rc;
+  if ((rc = reduce_probe_run(din, (long)n, dout, nullptr, g_err, sizeof g_err))) return rc;
+  return st.finish();
 }
 
 int ascent_kkt_solve(int64_t batch, int32_t n, int32_t bs, int32_t nb, const double *diag, const double *lower,

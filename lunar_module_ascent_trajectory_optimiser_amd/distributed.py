@@ -52,6 +52,10 @@ def solve_sharded(params, nt: int = 200, tol: float = 1e-9, max_iter: int = 300,
         local = torch.zeros((m + 1, width), dtype=torch.float64, device=dev)   # last row: this rank's error flag
         if k:
             try:
+                # (the shard is still on the host: the weights are refused here as the host-pointer call refuses them;
+                #  solve_batch_torch itself leaves them to the device, status 4 per problem)
+                if kw.get("move_penalty") and not np.all(P[idx][:, 15] > 0):
+                    raise ValueError("move_penalty needs dcost > 0 (column 15 of the parameter sets) for every problem")
                 o = solve_batch_torch(torch.from_numpy(np.ascontiguousarray(P[idx])).to(dev), nt, tol=tol, max_iter=max_iter,
                                       want_traj=gather_traj, **kw)
                 local[:k, 0], local[:k, 1], local[:k, 2] = o["tf"], o["status"].double(), o["iters"].double()

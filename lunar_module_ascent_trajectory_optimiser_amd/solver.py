@@ -12,7 +12,7 @@ from .params import PARAM_FIELDS, AscentParams, pack
 
 TRAJ_FIELDS = ("x", "y", "xdot", "ydot", "xdoubledot", "ydoubledot", "angle", "angledot",
                "angledoubledot", "mass")
-STATUS_NAMES = {0: "converged", 1: "max_iter", 2: "linesearch_failed", 3: "regularisation_failed"}
+STATUS_NAMES = {0: "converged", 1: "max_iter", 2: "linesearch_failed", 3: "regularisation_failed", 4: "invalid_problem"}
 
 
 def blob_rows(nt: int) -> int:
@@ -793,7 +793,9 @@ def solve_batch_torch(params_t, nt: int = 200, tol: float = 1e-9, max_iter: int 
     torch CUDA tensors (allocated here unless passed in `out`).  Enqueues on torch's current stream
     and returns without waiting unless sync=True.  torch is only the owner of device memory/streams.
     Options as solve_batch (scheme, formulation, terminal, path, move_penalty: the weights params_t[:, 15] must be
-    positive then -- checked here on the device, the library cannot look into device memory from the host).
+    positive then -- checked by the kernels that set the starting point, with no host read: a problem whose weight is
+    zero, negative or NaN comes back with status 4 (invalid_problem), 0 iterations and its starting point in tf / traj /
+    blob, and the rest of the batch is solved as without it).
     sensitivity: also out["sensitivity"], (batch, 16) d(T_scale J*)/dp as solve_batch(sensitivity=True) computes it (NaN rows
     for problems that did not converge), enqueued on the same stream right after the solve: no host read.
     flight: also out["flight_summary"] (batch, 10), out["flight_traj"] (batch, 10, nt) and out["flight_local"] (batch, K, 7) as
@@ -817,8 +819,6 @@ def solve_batch_torch(params_t, nt: int = 200, tol: float = 1e-9, max_iter: int 
         return t
     if params_t.dim() != 2 or params_t.shape[1] != 16:
         raise ValueError("params_t must have shape (batch, 16)")
-    if move_penalty and not bool((params_t[:, 15] > 0).all()):
-        raise ValueError("move_penalty needs dcost > 0 (column 15 of params_t) for every problem")
     if warm_start not in (0, 1, 2) or (warm_start and guess_t is None):
         raise ValueError("warm_start 1/2 needs guess_t")
     if guess_t is not None and not (guess_t.device == dev and guess_t.dtype == torch.float64 and guess_t.is_contiguous()
