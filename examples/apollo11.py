@@ -185,12 +185,38 @@ def disperse(m, scheme, samples=1024, corridor=False, outdir=None):
     return d
 
 
-def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=False, corridor=False, outdir=None):
+def lincov_report(name, lc, d, params, tf, outdir=None, figure=None):
+    """The linear covariance corridor lc (linear_corridor) beside the Monte Carlo history of the same flight (d.history): the
+    altitude's 1-sigma band of both at the node where the sampled one is widest, and with outdir both bands in one figure."""
+    h, K, ALT = d.history, d.history.nodes[-1], 7
+    mc, lin = h.std[0, :, ALT], lc.std[0, :, ALT]
+    i = int(np.nanargmax(mc))
+    print("%s: linear 1-sigma altitude band at node %d (t = %.1f s): +-%.1f m; Monte Carlo +-%.1f m (%d samples)"
+          % (name, h.nodes[i], h.nodes[i] * tf * params[0, 11] / K, lin[i], mc[i], h.n_valid[0, i]))
+    print("%s: largest gap between the two bands over the nodes: %.2f m of %.1f m at node %d"
+          % (name, np.nanmax(np.abs(lin - mc)), mc[int(np.nanargmax(np.abs(lin - mc)))], h.nodes[int(np.nanargmax(np.abs(lin - mc)))]))
+    if outdir is not None:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+        x = -h.nominal[0, :, 0] * ORBIT["periapsis"]
+        fig, ax = plt.subplots()
+        ax.fill_between(x, -mc, mc, color=(0.9, 0.4, 0, 0.4), label="Monte Carlo +-1 sigma")
+        ax.plot(x, lin, color="k", lw=0.8, label="linear covariance +-1 sigma")
+        ax.plot(x, -lin, color="k", lw=0.8)
+        ax.set(title="Altitude dispersion about the nominal (%s)" % name, xlabel="downrange / m", ylabel="altitude deviation / m")
+        ax.legend()
+        ax.grid()
+        fig.savefig(os.path.join(outdir, figure or "lincov_%s.png" % name.replace(" ", "_")), dpi=300)
+
+
+def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=False, corridor=False, outdir=None, lincov=False):
     """The trimmed solution under the same dispersions, open loop and steering back to the nominal with a cutoff on the state.
     The cutoff channel stretches the last step only, T / K = 2.2 s here: 50 N of 15 kN over a 435 s burn is 1.4 s (1-sigma) of burn
     time, so the stretch is allowed +-2 steps; at stretch_max = 0.5 it sits on its bound for most samples.
-    corridor: every flight flown with its per-node history, and the lines of corridor_report for each."""
-    from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, guidance_gains, trim_batch
+    corridor: every flight flown with its per-node history, and the lines of corridor_report for each.
+    lincov: the open and the closed loop flown once more with their history, beside linear_corridor's band (lincov_report)."""
+    from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, guidance_gains, linear_corridor, trim_batch
     res = m.result
     kw = dict(scheme=scheme, formulation=m._formulation)
     t = trim_batch(res.params, res.flight_blob(), res.nt, **kw)
@@ -228,6 +254,13 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
         if corridor:
             corridor_report("thrust known", known, res.params, t.tf[0], outdir)
             corridor_report("known to 10 N", nav, res.params, t.tf[0], outdir)
+    if lincov:
+        lkw = dict(param_sigma=thrust, control_sigma=1e-3, **kw)
+        hkw = dict(dkw, history=True)
+        lincov_report("open loop", linear_corridor(res.params, t.blob, res.nt, **lkw), op if corridor else disperse_batch(res.params, t.blob, res.nt, **hkw),
+                      res.params, t.tf[0], outdir)
+        lincov_report("closed loop", linear_corridor(res.params, t.blob, res.nt, guidance=g, **lkw),
+                      cl if corridor else disperse_batch(res.params, t.blob, res.nt, guidance=g, **hkw), res.params, t.tf[0], outdir, "lincov.png")
     return op, cl, g
 
 
@@ -270,9 +303,12 @@ if __name__ == "__main__":
     ap.add_argument("--guide", action="store_true", help="trim, compute LQ feedback gains and fly 1024 dispersed samples open loop and closed loop; prints both 1-sigmas of the flown apsides")
     ap.add_argument("--feedforward", action="store_true", help="with --guide: also fly the same draws with the thrust feed-forward, once with the thrust known exactly and once known to 10 N (1-sigma) under a navigation bias of 1-sigma %g (scaled; %.1f m) on both positions and %g (scaled; %.1f cm/s) on both velocities" % (NAV_BIAS[0], NAV_BIAS[0] * ORBIT["periapsis"], NAV_BIAS[2], NAV_BIAS[2] * ORBIT["periapsis"] * 100))
     ap.add_argument("--corridor", action="store_true", help="with --disperse or --guide: reduce the samples at every node as well (disperse_batch(history=True)); prints, per flight flown, the widest 1-sigma altitude band, the lowest altitude any sample reached, the largest excursion of the angle beyond its bounds and the step with the most clipped commands, and writes corridor.png (with --guide: of the closed loop; the other flights as corridor_<flight>.png)")
+    ap.add_argument("--lincov", action="store_true", help="with --guide: the linear covariance corridor (linear_corridor) of the open and the closed loop beside their Monte Carlo history; prints both 1-sigma altitude bands at the node where the sampled one is widest, and writes lincov.png (closed loop) and lincov_open_loop.png")
     a = ap.parse_args()
     if a.corridor and not (a.disperse or a.guide):
         ap.error("--corridor needs --disperse or --guide")
+    if a.lincov and not a.guide:
+        ap.error("--lincov needs --guide")
     figdir = None if a.no_plots else a.outdir
     model, variables, v_ins = build()
     if a.no_dcost:
@@ -288,6 +324,6 @@ if __name__ == "__main__":
     if a.disperse:
         disperse(model, a.scheme, corridor=a.corridor, outdir=figdir)
     if a.guide:
-        guide(model, a.scheme, feedforward=a.feedforward, corridor=a.corridor, outdir=figdir)
+        guide(model, a.scheme, feedforward=a.feedforward, corridor=a.corridor, outdir=figdir, lincov=a.lincov)
     if not a.no_plots:
         plots(model, variables, a.outdir)

@@ -559,6 +559,49 @@ int ascent_disperse_history_batch(const ascent_params *p, int64_t batch, const a
                                   int32_t node_stride, double *stats_out, double *samples_out_or_null, double *hist_out,
                                   double *hist_samples_out_or_null, int device_id, void *hip_stream_or_null, int ptr_is_device);
 
+/* Linear covariance corridor: what ascent_disperse_history_batch samples, to first order and without sampling -- the covariance
+ * of the ten history quantities at every history node from one deterministic forward sweep per problem, and their derivative.
+ * Model: the derivative of the arithmetic of ascent_disperse_history_batch's flight about the nominal flight of ascent_fly_batch at
+ *   the blob; clips ignored, the substeps m held, the blob fixed in scaled units.  Which flight: gain_u null -- the open loop;
+ *   gain_u given -- the navigated one (with everything after stretch_max null, the guided one), the arguments and their "both or
+ *   neither" rules as in that call.
+ * Constants c, ASCENT_LINCOV_COLS = ASCENT_DISPERSE_COLS + ASCENT_NAV_ROWS columns: 0..6 dz_0 (scaled), 7..22 the 16 fields (SI),
+ *   23 the scaled t_f, 24..30 the knowledge bias nu (scaled), 31 the error e of theta-hat = w . dp + e (w = ff_know, 0 where null).
+ *   sigma [24][batch] and sigma_nav_or_null [8][batch] (null: zero) are their standard deviations; sigma_u_or_null [K][batch] that
+ *   of the white execution error eps_k of step k, independent per step.
+ * Step k: corr_k = K_k . (dz_{k-1} + nu) + f_k theta-hat, du_k = -corr_k + eps_k, dz_k = Phi_k dz_{k-1} + g_k du_k + Gamma_k dp +
+ *   (dz_k/dt_f) dt_f, and on step K, with gain_t and stretch_max > 0, + gamma_K tau, tau = -k_t . (dz_{K-1} + nu) - f_t theta-hat;
+ *   Phi_k, g_k, Gamma_k, gamma_K as ascent_guidance_gains / ascent_guidance_feedforward state them.
+ * The ten quantities y_j: the rows of ascent_disperse_history_batch -- 0..6 dz_j, 7 the altitude (its gradient at the nominal
+ *   node times dz_j, plus its direct dependence on R0 and r_peri), 8 du_j, 9 corr_j.
+ * History nodes: node_stride, NJ and j_i as ascent_disperse_history_batch; node 0 is not reported.
+ * nominal_out [10][NJ][batch]: rows 1..10 of hist_out of ascent_disperse_history_batch on the same blob, bit for bit.
+ * jac_hist_out_or_null [10][ASCENT_LINCOV_COLS][NJ][batch], element (q, c, i, problem) at (((q*32 + c)*NJ + i)*batch + problem):
+ *   S_j = d y_j / d c.  At node K rows 0..6 are those of ascent_flight_jacobian (open loop) or of jac_cl | jac_nav of
+ *   ascent_guidance_feedforward, computed forward instead of by the adjoint sweep.
+ * cov_out [ASCENT_LINCOV_COV_ROWS][NJ][batch]: the upper triangle of cov_j, row by row ((0,0), (0,1), .., (0,9), (1,1), ..):
+ *   cov_j = S_j diag(sigma_c^2) S_j' + N_j, summed over the columns in ascending order, a column whose sigma is 0 contributing
+ *   exactly 0, the noise part added last: N_j = Y_j Q_{j-1} Y_j' + sigma_u,j^2 y_j y_j', Q_0 = 0, Q_k = A_k Q_{k-1} A_k' + sigma_u,k^2
+ *   g_k g_k', A_k = Phi_k - g_k K_k' (- gamma_K k_t' on a stretched last step), Y_j = d y_j / d dz_{j-1}, y_j = d y_j / d eps_j.
+ * All-zero gains without stretch give the bits of gain_u null.  The order of every addition is fixed: a node's rows do not
+ *   depend on node_stride, the batch size, the problem's place in the batch, host or device pointers, or whether jac_hist_out was
+ *   asked for.
+ * Refuses (ASCENT_E_ARG, before the device is looked at, no array touched) what ascent_disperse_history_batch refuses of these
+ *   arguments -- ff_know without ff_u, substeps or node_stride out of range, any of gain_t, stretch_max, ff_*, sigma_nav without
+ *   gain_u -- and a null sigma, nominal_out or cov_out.  terminal = 2 is accepted.  Garbage blobs: the work is bounded as in
+ *   ascent_flight_jacobian (K m tangent steps per problem whatever the blob holds); a non-finite t_f gives NaN rows at every node,
+ *   NaN or inf gains give NaN rows from the node where they enter.
+ * Host or device pointers; with device pointers and a stream the call only enqueues two kernels (f_fly, l_lincov; no host read,
+ *   no synchronisation).  Device workspace: that of ascent_flight_jacobian; the sweep's state lives in LDS. */
+#define ASCENT_LINCOV_COLS 32
+#define ASCENT_LINCOV_COV_ROWS 55
+int ascent_covariance_history_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                                    int32_t substeps, const double *sigma, const double *sigma_u_or_null,
+                                    const double *gain_u_or_null, const double *gain_t_or_null, const double *stretch_max_or_null,
+                                    const double *ff_u_or_null, const double *ff_t_or_null, const double *ff_know_or_null,
+                                    const double *sigma_nav_or_null, int32_t node_stride, double *nominal_out, double *cov_out,
+                                    double *jac_hist_out_or_null, int device_id, void *hip_stream_or_null, int ptr_is_device);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

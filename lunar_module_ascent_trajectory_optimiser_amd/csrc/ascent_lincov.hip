@@ -1,0 +1,285 @@
+// Linear covariance corridor (include/ascent.h: ascent_covariance_history_batch): the first-order dispersion of a flown solution at
+// every history node, in one deterministic forward sweep per problem -- what ascent_disperse_history_batch samples.
+//
+// The model is the derivative of that call's flight about the nominal flight f_fly writes (clips ignored, substeps held, blob
+// fixed in scaled units).  Constants c (32 columns): dz_0 (7) | the 16 fields | t_f | the knowledge bias nu (7) | the error e of
+// theta-hat = w . dp + e.  Step k, from the records [Phi_k | g_k | Gamma_k] of fly_step_tangent:
+//   corr_k = K_k . (dz_{k-1} + nu) + f_k theta-hat,   du_k = -corr_k + eps_k,   eps_k = sigma_u,k xi_k
+//   dz_k = Phi_k dz_{k-1} + g_k du_k + Gamma_k dp + (dz_k/dt_f) dt_f  [+ gamma_K tau on step K, tau = -k_t . (dz_{K-1} + nu) - f_t theta-hat]
+// The ten quantities y_j of a node are dz_j, the altitude (its gradient at the nominal node and its direct dependence on R0 and
+// r_peri), du_j and corr_j.  Outputs per node: S_j = dy_j/dc (10 x 32) and cov_j = S_j diag(sigma^2) S_j' + N_j with the white
+// noise N_j = Y_j Q_{j-1} Y_j' + sigma_u,j^2 y_j y_j', Q_k = A_k Q_{k-1} A_k' + sigma_u,k^2 g_k g_k', A_k = Phi_k - g_k K_k' (- gamma_K k_t').
+//
+// l_lincov  one workgroup of JB = 256 threads per problem, chunks of CH = 16 steps in ascending order; evaluation and LDS staging
+//          of the step records exactly as j_jac (ascent_trim.hip).  Beside its record every group stages what the sweep reads of
+//          its step: K_k, f_k, sigma_u,k^2, u_k and the nominal node k -- no global load on the serial path.
+//   sweep    the sensitivity is carried in the compressed column space X (7 x 23): z_0 (7) | the 8 tangent coefficients of
+//          tangent_coefficients / jac_columns | nu (7) | theta-hat, and Q (7 x 7); both stay in LDS across the chunks, each in two
+//          copies that alternate with the parity of the step, so a step is one phase and one barrier:
+//            lanes 0..160    entry (i, c) of X: its own copy of corr_c, then row i of the step; lanes of row 0 store corr
+//            lanes 161..168  the noise helpers A_k Q_{k-1} K_k (7) and K_k' Q_{k-1} K_k, two copies by parity as well
+//            lanes 192..240  entry (i, j) of Q: both halves N_ij and N_ji computed by the lane itself and averaged, as g_gains keeps
+//                            P, so Q stays exactly symmetric
+//          Without gain_u the same arithmetic runs on zero gains: all-zero gains give the bits of gain_u null.
+//   node     two more phases at a history node: lanes 0..9 expand their row of y_j to the 32 columns -- jac_columns for the
+//          fields and t_f, + (theta-hat column) w_c for a parameter column (the transpose of the E w_c rule of
+//          ascent_guidance_feedforward), the altitude's direct terms -- into LDS and jac_hist_out, and write the nominal row; then
+//          lanes 0..54 sum their covariance entry over the 32 columns in ascending order and add the noise part last.
+// The order of every addition is fixed: a problem gives the same bits alone as inside any batch, and a node's rows do not depend
+// on the stride or on whether the Jacobian was asked for.
+#include <hip/hip_runtime.h>
+#include <cstdio>
+#include <cmath>
+
+#include "ascent.h"
+#include "ascent_device.hpp"
+#include "ascent_disperse.hpp"
+#include "ascent_flight.hpp"
+#include "ascent_flight_dev.hpp"
+#include "ascent_lincov.hpp"
+#include "ascent_tangent_dev.hpp"
+
+namespace ascent {
+namespace {
+
+constexpr int XC = 23, XN = 7 * XC;                        // columns and entries of X
+constexpr int X_COEF = 7, X_NU = X_COEF + NACC, X_TH = X_NU + 7;
+static_assert(X_TH + 1 == XC, "compressed columns");
+constexpr int LC = ASCENT_LINCOV_COLS, HQ = ASCENT_HISTORY_QUANTITIES, NCOV = ASCENT_LINCOV_COV_ROWS;
+static_assert(LC == ASCENT_DISPERSE_COLS + ASCENT_NAV_ROWS && NCOV == HQ * (HQ + 1) / 2, "lincov layout");
+constexpr int T_NK = XN, T_Q = 192;                        // first lane of the noise helpers and of Q
+static_assert(T_NK + 8 <= T_Q && T_Q + 49 <= JB, "lane map");
+constexpr int ST_F = 7, ST_SU2 = 8, ST_U = 9, ST = 10;     // staged per step: K_k (7), f_k, sigma_u,k^2, u_k
+
+struct LincovArgs {
+  const double *sigma, *sigma_u, *gain_u, *gain_t, *stretch_max, *ff_u, *ff_t, *ff_know, *sigma_nav;
+  int stride, nj;
+  double *nominal, *cov, *jac;
+};
+
+// f_history_stats' altitude of the nominal node (ascent_disperse.hip: altitude_of), the same operations, none contracted:
+// nominal_out has the bits of hist_out
+ASC_DEV double nominal_altitude(double x, double y, double r_peri, double R0) {
+#pragma clang fp contract(off)
+  const double X = x * r_peri, Y = y * r_peri + R0;
+  return sqrt(X * X + Y * Y) - R0;
+}
+
+// row i of A_k = Phi_k - g_k K_k' (- gamma_K k_t' on a stretched last step)
+ASC_DEV void closed_row(const double *R, const double *kv, const double *kt, bool last, double dt, int i, double *a) {
+  const double gi = R[i * NCOL + C_U], ti = dt * R[i * NCOL + C_DT];
+  ASC_UNROLL
+  for (int l = 0; l < 7; l++) {
+    double v = R[i * NCOL + l] - gi * kv[l];
+    if (last) v -= ti * kt[l];
+    a[l] = v;
+  }
+}
+
+template <int FORM>
+__global__ __launch_bounds__(JB) void l_lincov(const ascent_params *__restrict__ P, long batch, int K, int substeps,
+                                               const double *__restrict__ blob, const double *__restrict__ traj, LincovArgs A) {
+  __shared__ double rec[CH * REC];
+  __shared__ double Xs[2][XN], Qs[2][49], nks[2][8], stp[CH][ST], nod[CH][7], cors[XC], Ss[HQ * LC], sgs[LC], kts[8], wks[16];
+  const long p = blockIdx.x;
+  const size_t B = (size_t)batch;
+  const int t = threadIdx.x, g = t >> 4, col = t & (NCOL - 1);
+  const int nt = K + 1;
+  const double *b = blob + p, *tr = traj + p;
+  const ascent_params prm = P[p];
+  const Der d = derive(prm);
+  const double tf = b[(size_t)(21 * K + S_TH) * B];
+  const double dt = (tf * d.T) / K;
+  const int m = flight_substeps(dt, substeps);
+  const double hs = dt / m;
+  const double smax = A.gain_t && A.stretch_max ? A.stretch_max[p] : 0.0;
+  const bool stretch = smax > 0.0;            // the flight's rule: gain_t and stretch_max given, stretch_max > 0
+
+  // X_0 = [I | 0], Q_0 = 0, and what every step shares; the barrier after the first evaluation publishes them
+  if (t < XN) Xs[0][t] = t / XC == t % XC ? 1.0 : 0.0;
+  if (t < 49) Qs[0][t] = 0.0;
+  if (t < LC) sgs[t] = t < ASCENT_DISPERSE_COLS ? A.sigma[(size_t)t * B + p]
+                                                : A.sigma_nav ? A.sigma_nav[(size_t)(t - ASCENT_DISPERSE_COLS) * B + p] : 0.0;
+  if (t < 7) kts[t] = stretch ? A.gain_t[(size_t)t * B + p] : 0.0;
+  if (t == 7) kts[7] = stretch && A.ff_t ? A.ff_t[p] : 0.0;
+  if (t < 16) wks[t] = A.ff_know ? A.ff_know[(size_t)t * B + p] : 0.0;
+
+  const int nch = (K + CH - 1) / CH;
+  for (int c = 0; c < nch; c++) {
+    const int k = c * CH + g + 1;             // this group's step: node k-1 -> k
+    if (k <= K) {
+      double z[7], dz[7];
+      load_node(tr, B, nt, k - 1, z);
+      const double u = b[(size_t)(7 * K + k - 1) * B];
+      if (col < 7) {
+        stp[g][col] = A.gain_u ? A.gain_u[((size_t)col * K + k - 1) * B + p] : 0.0;
+      } else if (col == ST_F) {
+        stp[g][ST_F] = A.ff_u ? A.ff_u[(size_t)(k - 1) * B + p] : 0.0;
+      } else if (col == ST_SU2) {
+        const double su = A.sigma_u ? A.sigma_u[(size_t)(k - 1) * B + p] : 0.0;
+        stp[g][ST_SU2] = su * su;
+      } else if (col == ST_U) {
+        stp[g][ST_U] = u;
+      } else if (col == NCOL - 1) {           // the nominal node the step ends at, f_fly's
+        double zk[7];
+        load_node(tr, B, nt, k, zk);
+        ASC_UNROLL
+        for (int i = 0; i < 7; i++) nod[g][i] = zk[i];
+      }
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) dz[i] = col == i ? 1.0 : 0.0;
+      fly_step_tangent<FORM>(d, z, dz, u, hs, m, col);
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) rec[g * REC + i * NCOL + col] = dz[i];
+    }
+    __syncthreads();
+    const int top = K - c * CH < CH ? K - c * CH : CH;
+    for (int s = 0; s < top; s++) {
+      const int kk = c * CH + s, par = kk & 1;            // step kk + 1 reads copy par and writes the other
+      const double *R = rec + s * REC, *kv = stp[s], *Xo = Xs[par], *Qo = Qs[par];
+      const bool last = stretch && kk + 1 == K;
+      if (t < XN) {
+        const int xi = t / XC, xc = t - xi * XC;
+        double x[7], corr = 0.0, a = 0.0;
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) x[l] = Xo[l * XC + xc];
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) corr += kv[l] * x[l];
+        if (xc >= X_NU && xc < X_TH) corr += kv[xc - X_NU];
+        if (xc == X_TH) corr += kv[ST_F];
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) a += R[xi * NCOL + l] * x[l];
+        a -= R[xi * NCOL + C_U] * corr;
+        if (xc >= X_COEF && xc < X_NU) a += R[xi * NCOL + C_DT + (xc - X_COEF)];
+        if (last) {
+          double tau = 0.0;
+          ASC_UNROLL
+          for (int l = 0; l < 7; l++) tau -= kts[l] * x[l];
+          if (xc >= X_NU && xc < X_TH) tau -= kts[xc - X_NU];
+          if (xc == X_TH) tau -= kts[7];
+          a += (dt * R[xi * NCOL + C_DT]) * tau;
+        }
+        Xs[par ^ 1][t] = a;
+        if (xi == 0) cors[xc] = corr;
+      } else if (t >= T_NK && t < T_NK + 8) {
+        const int q = t - T_NK;
+        double v[7], ar[7], a = 0.0;
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) {
+          double w = 0.0;
+          ASC_UNROLL
+          for (int mm = 0; mm < 7; mm++) w += Qo[l * 7 + mm] * kv[mm];
+          v[l] = w;
+        }
+        closed_row(R, kv, kts, last, dt, q < 7 ? q : 0, ar);
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) a += (q < 7 ? ar[l] : kv[l]) * v[l];
+        nks[par][q] = a;
+      } else if (t >= T_Q && t < T_Q + 49) {
+        const int q = t - T_Q, qi = q / 7, qj = q - qi * 7;
+        double ai[7], aj[7], nij = 0.0, nji = 0.0;
+        closed_row(R, kv, kts, last, dt, qi, ai);
+        closed_row(R, kv, kts, last, dt, qj, aj);
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) {
+          double wi = 0.0, wj = 0.0;
+          ASC_UNROLL
+          for (int mm = 0; mm < 7; mm++) {
+            const double ql = Qo[l * 7 + mm];
+            wj += ql * aj[mm];
+            wi += ql * ai[mm];
+          }
+          nij += ai[l] * wj;
+          nji += aj[l] * wi;
+        }
+        const double su2 = kv[ST_SU2];
+        const double gg = su2 != 0.0 ? su2 * (R[qi * NCOL + C_U] * R[qj * NCOL + C_U]) : 0.0;
+        Qs[par ^ 1][q] = 0.5 * ((nij + gg) + (nji + gg));
+      }
+      __syncthreads();
+      const int j = kk + 1;
+      if (j % A.stride == 0 || j == K) {                  // a history node (uniform)
+        const int i = (j + A.stride - 1) / A.stride - 1;
+        const double *Xn = Xs[par ^ 1], *Qn = Qs[par ^ 1], *zn = nod[s];
+        // the altitude's gradient at the nominal node: (gax, gay) on (x, y), and the unit vector (ex, ey) of its direct terms
+        const double S = prm.r_peri;
+        const double Xp = zn[IX] * S, Yp = zn[IY] * S + prm.R0, rr = sqrt(Xp * Xp + Yp * Yp);
+        const double ex = Xp / rr, ey = Yp / rr, gax = S * ex, gay = S * ey;
+        if (t < HQ) {
+          double cp[XC], o[LC];
+          ASC_UNROLL
+          for (int cc = 0; cc < XC; cc++) {
+            const double xr = Xn[(t < 7 ? t : 0) * XC + cc], al = gax * Xn[IX * XC + cc] + gay * Xn[IY * XC + cc], cr = cors[cc];
+            cp[cc] = t < 7 ? xr : t == 7 ? al : t == 8 ? -cr : cr;
+          }
+          const ApsisDirect dir = {0.0, 0.0, t == 7 ? ey - 1.0 : 0.0, t == 7 ? zn[IX] * ex + zn[IY] * ey : 0.0};
+          jac_columns<FORM>(prm, d, tf, K, cp, cp + X_COEF, dir, o);
+          if (A.ff_know) {
+            ASC_UNROLL
+            for (int cc = 0; cc < 16; cc++) o[7 + cc] += cp[X_TH] * wks[cc];
+          }
+          ASC_UNROLL
+          for (int a = 0; a < ASCENT_NAV_ROWS; a++) o[ASCENT_DISPERSE_COLS + a] = cp[X_NU + a];
+          if (!finite1(tf)) {                 // a blob without a final time: NaN rows, the structurally zero columns included
+            ASC_UNROLL
+            for (int cc = 0; cc < LC; cc++) o[cc] = NAN;
+          }
+          ASC_UNROLL
+          for (int cc = 0; cc < LC; cc++) {
+            Ss[t * LC + cc] = o[cc];
+            if (A.jac) A.jac[(((size_t)t * LC + cc) * A.nj + i) * B + p] = o[cc];
+          }
+          const double nom = t < 7 ? zn[t] : t == 7 ? nominal_altitude(zn[IX], zn[IY], prm.r_peri, prm.R0) : t == 8 ? kv[ST_U] : 0.0;
+          A.nominal[((size_t)t * A.nj + i) * B + p] = nom;
+        }
+        __syncthreads();
+        if (t < NCOV) {
+          int a = 0, rem = t;
+          while (rem >= HQ - a) { rem -= HQ - a; a++; }
+          const int bq = a + rem;             // entry (a, bq), a <= bq
+          double acc = 0.0;
+          for (int cc = 0; cc < LC; cc++) {
+            const double sg = sgs[cc];
+            if (sg != 0.0) acc += (Ss[a * LC + cc] * Ss[bq * LC + cc]) * (sg * sg);
+          }
+          // the noise part: rows 0..6 Q_j, 7 the altitude's gradient on it, 8 / 9 through K_j' dz_{j-1} and eps_j
+          const double *nk = nks[par];
+          const double su2 = kv[ST_SU2];
+          const int ar = a < 7 ? a : 0;
+          const double qa = gax * Qn[ar * 7 + IX] + gay * Qn[ar * 7 + IY];
+          const double n8 = (su2 != 0.0 ? su2 * R[ar * NCOL + C_U] : 0.0) - nk[ar];
+          const double n8x = (su2 != 0.0 ? su2 * R[IX * NCOL + C_U] : 0.0) - nk[IX], n8y = (su2 != 0.0 ? su2 * R[IY * NCOL + C_U] : 0.0) - nk[IY];
+          double n;
+          if (bq < 7) n = Qn[a * 7 + bq];
+          else if (a < 7) n = bq == 7 ? qa : bq == 8 ? n8 : nk[a];
+          else if (a == 7)
+            n = bq == 7 ? gax * (gax * Qn[IX * 7 + IX] + gay * Qn[IX * 7 + IY]) + gay * (gax * Qn[IY * 7 + IX] + gay * Qn[IY * 7 + IY])
+                : bq == 8 ? gax * n8x + gay * n8y : gax * nk[IX] + gay * nk[IY];
+          else if (a == 8) n = bq == 8 ? nk[7] + su2 : -nk[7];
+          else n = nk[7];
+          acc += n;
+          A.cov[((size_t)t * A.nj + i) * B + p] = finite1(tf) ? acc : NAN;
+        }
+      }
+    }
+    __syncthreads();                          // the records and the staged steps are rewritten by the next chunk
+  }
+}
+
+}  // namespace
+
+size_t lincov_ws_bytes(int K, long batch) { return flight_ws_bytes(K, batch); }
+
+int lincov_run(const Call &c, int substeps, const LincovIO &io, double *ws) {
+  const FlightWs w = flight_ws(ws, c.K, c.batch);
+  if (const int rc = flight_fly_only(c, substeps, io.blob, w.traj, w.fsum)) return rc;
+  const LincovArgs a{io.sigma, io.sigma_u, io.gain_u, io.gain_t, io.stretch_max, io.ff_u, io.ff_t, io.ff_know, io.sigma_nav,
+                     io.node_stride, history_nodes(c.K, io.node_stride), io.nominal, io.cov, io.jac};
+  const dim3 grid((unsigned)c.batch), block(JB);
+  if (c.form == 1) hipLaunchKernelGGL((l_lincov<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, io.blob, w.traj, a);
+  else hipLaunchKernelGGL((l_lincov<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, io.blob, w.traj, a);
+  ASC_CHK(c.err, c.errlen, hipGetLastError());
+  return ASCENT_OK;
+}
+
+}  // namespace ascent

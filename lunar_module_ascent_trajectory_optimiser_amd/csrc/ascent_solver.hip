@@ -18,6 +18,7 @@
 //   flight Jacobian and trim j_jac / t_update / t_final   ascent_trim.hpp (ascent_trim.hip)
 //   guidance gains g_gains / g_gains_ff                   ascent_guide.hpp (ascent_guide.hip), one GainsIO for both calls
 //   dispersion f_disperse / _guided / _navigated          ascent_disperse.hpp (ascent_disperse.hip), one DisperseIO for all three
+//   linear covariance corridor l_lincov                   ascent_lincov.hpp (ascent_lincov.hip)
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -41,6 +42,7 @@
 #include "ascent_trim.hpp"
 #include "ascent_disperse.hpp"
 #include "ascent_guide.hpp"
+#include "ascent_lincov.hpp"
 
 using namespace ascent;
 
@@ -787,7 +789,7 @@ int check_samples(int32_t samples) {
   return 0;
 }
 
-// What the nine entry points below share, in the order their defects have always been reported.  An entry point puts its own
+// What the ten entry points below share, in the order their defects have always been reported.  An entry point puts its own
 // null and range checks between the steps, then names its buffers (st.in / st.out) and its run function:
 //   options()               check_options
 //   solvable()              check_solvable
@@ -843,6 +845,21 @@ class BlobCall {
   double *ws = nullptr;              // the analysis workspace, where the call claimed one
 };
 
+// The refusals ascent_disperse_history_batch and ascent_covariance_history_batch share beyond BlobCall's, each with its one text:
+// the knowledge row without a feed-forward, and the history nodes with what needs gain_u (guided: any such argument was given)
+int check_ff_know(const double *ff_know, const double *ff_u) {
+  if (ff_know && !ff_u) { snprintf(g_err, sizeof g_err, "ff_know needs ff_u"); return ASCENT_E_ARG; }
+  return 0;
+}
+int check_history_nodes(const ascent_opts *o, int32_t node_stride, const double *gain_u, bool guided) {
+  if (node_stride < 1 || node_stride > o->n_nodes - 1) { snprintf(g_err, sizeof g_err, "node_stride out of range (1 .. K = %d)", o->n_nodes - 1); return ASCENT_E_ARG; }
+  if (!gain_u && guided) {
+    snprintf(g_err, sizeof g_err, "gain_t, stretch_max, ff_u, ff_t, ff_know, xi_nav and sigma_nav need gain_u");
+    return ASCENT_E_ARG;
+  }
+  return 0;
+}
+
 // ascent_disperse_batch, ascent_disperse_guided_batch and ascent_disperse_navigated_batch: io holds the caller's pointers.
 // history: ascent_disperse_history_batch, the kind picked from gain_u by the entry point; its own refusals stand after the
 // refusals the three share, each of which keeps its place and its text.
@@ -856,15 +873,10 @@ int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, i
   } else if (!io.blob || !io.xi || !io.sigma || !io.gain_u || !io.stats) { snprintf(g_err, sizeof g_err, "null solution blob, xi, sigma, gain_u or stats_out"); return ASCENT_E_ARG; }
   if ((rc = check_samples(samples))) return rc;
   if ((io.xi_nav != nullptr) != (io.sigma_nav != nullptr)) { snprintf(g_err, sizeof g_err, "xi_nav and sigma_nav come together"); return ASCENT_E_ARG; }
-  if (io.ff_know && !io.ff_u) { snprintf(g_err, sizeof g_err, "ff_know needs ff_u"); return ASCENT_E_ARG; }
-  if ((rc = check_substeps(substeps))) return rc;
+  if ((rc = check_ff_know(io.ff_know, io.ff_u)) || (rc = check_substeps(substeps))) return rc;
   if (history) {
     if (!io.hist) { snprintf(g_err, sizeof g_err, "null hist_out"); return ASCENT_E_ARG; }
-    if (io.node_stride < 1 || io.node_stride > o->n_nodes - 1) { snprintf(g_err, sizeof g_err, "node_stride out of range (1 .. K = %d)", o->n_nodes - 1); return ASCENT_E_ARG; }
-    if (!io.gain_u && (io.gain_t || io.stretch_max || io.ff_u || io.ff_t || io.ff_know || io.xi_nav || io.sigma_nav)) {
-      snprintf(g_err, sizeof g_err, "gain_t, stretch_max, ff_u, ff_t, ff_know, xi_nav and sigma_nav need gain_u");
-      return ASCENT_E_ARG;
-    }
+    if ((rc = check_history_nodes(o, io.node_stride, io.gain_u, io.gain_t || io.stretch_max || io.ff_u || io.ff_t || io.ff_know || io.xi_nav || io.sigma_nav))) return rc;
   }
   if ((rc = b.solvable()) || (rc = b.open(device_id, disperse_ws_bytes(o->n_nodes - 1, (long)batch, samples, history ? io.node_stride : 0)))) return rc;
   Staging &st = b.st;
@@ -889,6 +901,35 @@ int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, i
     io.hist_samples = st.out(io.hist_samples, ASCENT_HISTORY_QUANTITIES * NJ * S * B);
   }
   if ((rc = b.st.failed()) || (rc = disperse_run(b.c, kind, substeps, samples, io, b.ws))) return rc;
+  return b.close();
+}
+
+// ascent_covariance_history_batch: io holds the caller's pointers.  The order of the refusals is disperse_call's.
+int lincov_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, LincovIO io, int device_id, void *stream_,
+                int ptr_is_device) {
+  BlobCall b(p, batch, o, io.blob, stream_, ptr_is_device);
+  int rc = b.options();
+  if (rc) return rc;
+  if (!io.blob || !io.sigma || !io.nominal || !io.cov) { snprintf(g_err, sizeof g_err, "null solution blob, sigma, nominal_out or cov_out"); return ASCENT_E_ARG; }
+  if ((rc = check_ff_know(io.ff_know, io.ff_u)) || (rc = check_substeps(substeps))) return rc;
+  if ((rc = check_history_nodes(o, io.node_stride, io.gain_u, io.gain_t || io.stretch_max || io.ff_u || io.ff_t || io.ff_know || io.sigma_nav))) return rc;
+  if ((rc = b.solvable()) || (rc = b.open(device_id, lincov_ws_bytes(o->n_nodes - 1, (long)batch)))) return rc;
+  Staging &st = b.st;
+  const size_t K = (size_t)b.K, B = (size_t)batch, NJ = (size_t)history_nodes(b.K, io.node_stride);
+  io.blob = b.blob;
+  io.sigma = st.in(io.sigma, ASCENT_DISPERSE_COLS * B);
+  io.sigma_u = st.in(io.sigma_u, K * B);
+  io.gain_u = st.in(io.gain_u, 7 * K * B);
+  io.gain_t = st.in(io.gain_t, 7 * B);
+  io.stretch_max = st.in(io.stretch_max, B);
+  io.ff_u = st.in(io.ff_u, K * B);
+  io.ff_t = st.in(io.ff_t, B);
+  io.ff_know = st.in(io.ff_know, 16 * B);
+  io.sigma_nav = st.in(io.sigma_nav, ASCENT_NAV_ROWS * B);
+  io.nominal = st.out(io.nominal, ASCENT_HISTORY_QUANTITIES * NJ * B);
+  io.cov = st.out(io.cov, ASCENT_LINCOV_COV_ROWS * NJ * B);
+  io.jac = st.out(io.jac, (size_t)ASCENT_HISTORY_QUANTITIES * ASCENT_LINCOV_COLS * NJ * B);
+  if ((rc = b.st.failed()) || (rc = lincov_run(b.c, substeps, io, b.ws))) return rc;
   return b.close();
 }
 
@@ -1042,6 +1083,19 @@ int ascent_disperse_history_batch(const ascent_params *p, int64_t batch, const a
   io.stats = stats_out; io.samples_out = samples_out;
   io.node_stride = node_stride; io.hist = hist_out; io.hist_samples = hist_samples_out;
   return disperse_call(p, batch, o, substeps, samples, gain_u ? DISPERSE_NAVIGATED : DISPERSE_OPEN, io, device_id, stream_, ptr_is_device, true);
+}
+
+int ascent_covariance_history_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                                    const double *sigma, const double *sigma_u, const double *gain_u, const double *gain_t,
+                                    const double *stretch_max, const double *ff_u, const double *ff_t, const double *ff_know,
+                                    const double *sigma_nav, int32_t node_stride, double *nominal_out, double *cov_out,
+                                    double *jac_hist_out, int device_id, void *stream_, int ptr_is_device) {
+  LincovIO io{};
+  io.blob = sol_blob; io.sigma = sigma; io.sigma_u = sigma_u;
+  io.gain_u = gain_u; io.gain_t = gain_t; io.stretch_max = stretch_max;
+  io.ff_u = ff_u; io.ff_t = ff_t; io.ff_know = ff_know; io.sigma_nav = sigma_nav;
+  io.node_stride = node_stride; io.nominal = nominal_out; io.cov = cov_out; io.jac = jac_hist_out;
+  return lincov_call(p, batch, o, substeps, io, device_id, stream_, ptr_is_device);
 }
 
 int ascent_kkt_step(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,

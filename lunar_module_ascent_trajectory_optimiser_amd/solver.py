@@ -523,6 +523,114 @@ def trim_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, t
     return TrimResult(out, np.ascontiguousarray(summ.T), nt)
 
 
+def _dispersion_sigmas(z0_sigma, param_sigma, tf_sigma, control_sigma, K, B):
+    """The sigma arguments of disperse_batch and linear_corridor, broadcast: -> z0 (B, 7), params (B, 16), tf (B, 1), controls
+    (B, K), and the arrays the C ABI takes: sigma [24][B], sigma_u [K][B] or None where control_sigma is None"""
+    zs, ps = _sigma_rows(z0_sigma, 7, B, "z0_sigma"), _sigma_rows(param_sigma, 16, B, "param_sigma")
+    ts = _sigma_rows(None if tf_sigma is None else np.asarray(tf_sigma, dtype=np.float64)[..., None], 1, B, "tf_sigma")
+    us = _sigma_rows(control_sigma, K, B, "control_sigma")
+    sig = np.ascontiguousarray(np.concatenate([zs, ps, ts], axis=1).T)
+    sig_u = np.ascontiguousarray(us.T) if control_sigma is not None else None
+    return zs, ps, ts, us, sig, sig_u
+
+
+def _feedback_arrays(guidance, K, B):
+    """gain_u [7][K][B], gain_t [7][B] or None, stretch_max [B] or None of a GuidanceResult-like object, as the C ABI takes them"""
+    gu = np.ascontiguousarray(np.asarray(guidance.gain_u, dtype=np.float64).transpose(2, 1, 0))
+    if gu.shape != (7, K, B):
+        raise ValueError(f"guidance.gain_u must have shape {(B, K, 7)}")
+    gt = None if guidance.gain_t is None else np.ascontiguousarray(np.asarray(guidance.gain_t, dtype=np.float64).T)
+    if gt is not None and gt.shape != (7, B):
+        raise ValueError(f"guidance.gain_t must have shape {(B, 7)}")
+    sm = None if gt is None else _sigma_rows(np.asarray(guidance.stretch_max, dtype=np.float64)[..., None], 1, B, "stretch_max")[:, 0].copy()
+    return gu, gt, sm
+
+
+def _feedforward_arrays(guidance, K, B):
+    """ff_u [K][B], ff_t [B], ff_know [16][B] of a GuidanceResult-like object, None where it has none"""
+    ffu = getattr(guidance, "ff_u", None)
+    fu = ft = fk = None
+    if ffu is not None:
+        fu = np.ascontiguousarray(np.asarray(ffu, dtype=np.float64).T)
+        if fu.shape != (K, B):
+            raise ValueError(f"guidance.ff_u must have shape {(B, K)}")
+        ft, fk = getattr(guidance, "ff_t", None), getattr(guidance, "ff_know", None)
+        if ft is not None:
+            ft = np.ascontiguousarray(np.asarray(ft, dtype=np.float64))
+            if ft.shape != (B,):
+                raise ValueError(f"guidance.ff_t must have shape {(B,)}")
+        if fk is not None:
+            fk = np.ascontiguousarray(np.asarray(fk, dtype=np.float64).T)
+            if fk.shape != (16, B):
+                raise ValueError(f"guidance.ff_know must have shape {(B, 16)}")
+    return fu, ft, fk
+
+
+def _nav_sigma_rows(nav_sigma, knowledge_sigma, B):
+    """(B, 8): the 1-sigma biases of the state knowledge and the 1-sigma error of theta-hat"""
+    ks = _sigma_rows(None if knowledge_sigma is None else np.asarray(knowledge_sigma, dtype=np.float64)[..., None], 1, B,
+                     "knowledge_sigma")
+    return np.concatenate([_sigma_rows(nav_sigma, 7, B, "nav_sigma"), ks], axis=1)
+
+
+LINCOV_COLS = tuple(f"z0_{n}" for n in HISTORY_ROWS[:7]) + PARAM_FIELDS + ("tf",) + tuple(f"nav_{n}" for n in HISTORY_ROWS[:7]) + (
+    "knowledge",)
+
+
+@dataclasses.dataclass
+class LinearCorridor:
+    """The linear covariance corridor of a flight (linear_corridor; include/ascent.h: ascent_covariance_history_batch): the
+    first-order covariance of the ten quantities HISTORY_ROWS at every stride-th node and the last -- what
+    disperse_batch(history=...) samples, without sampling noise and with the covariances between the quantities.  Problem first."""
+    nodes: np.ndarray               # (NJ,) the node numbers, 1-based; the last one is K
+    nominal: np.ndarray             # (batch, NJ, 10) the bits of DispersionHistory.nominal
+    cov: np.ndarray                 # (batch, NJ, 10, 10) symmetric
+    jacobian: np.ndarray | None     # (batch, NJ, 10, 32) d HISTORY_ROWS / d LINCOV_COLS (want_jacobian=True)
+
+    @property
+    def std(self) -> np.ndarray:
+        """(batch, NJ, 10)"""
+        return np.sqrt(np.diagonal(self.cov, axis1=2, axis2=3))
+
+
+def linear_corridor(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, control_sigma=None, tf_sigma=None, z0_sigma=None,
+                    guidance: GuidanceResult | None = None, nav_sigma=None, knowledge_sigma=None, history=True,
+                    want_jacobian: bool = True, scheme=0, formulation=0, terminal=0, move_penalty: bool = False, substeps: int = 0,
+                    device: int = 0) -> LinearCorridor:
+    """Linear covariance analysis (include/ascent.h: ascent_covariance_history_batch): the flight disperse_batch(history=...)
+    samples, linearised about the nominal flight and swept forward once per problem -- clips ignored, the execution errors of
+    control_sigma independent white noise.  The sigmas broadcast as disperse_batch's and `guidance` is taken as there: None the
+    open loop, a GuidanceResult the guided flight, with its feed-forward where it carries one; nav_sigma and knowledge_sigma
+    need guidance.  history: True, or a node stride in 1 .. K.  Returns a LinearCorridor; jacobian None unless want_jacobian.
+    terminal 2 is accepted."""
+    L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
+    stride = 1 if history is True else int(history) if history is not False and history is not None else 0
+    if not 1 <= stride <= K:
+        raise ValueError(f"history: the node stride must be in 1 .. K = {K}")
+    _, _, _, _, sig, sig_u = _dispersion_sigmas(z0_sigma, param_sigma, tf_sigma, control_sigma, K, B)
+    if guidance is None and (nav_sigma is not None or knowledge_sigma is not None):
+        raise ValueError("nav_sigma and knowledge_sigma need guidance")
+    gu = gt = sm = fu = ft = fk = sn = None
+    if guidance is not None:
+        gu, gt, sm = _feedback_arrays(guidance, K, B)
+        fu, ft, fk = _feedforward_arrays(guidance, K, B)
+        if nav_sigma is not None or knowledge_sigma is not None:
+            sn = np.ascontiguousarray(_nav_sigma_rows(nav_sigma, knowledge_sigma, B).T)
+    nodes = history_nodes(K, stride)
+    NJ = len(nodes)
+    nom, cov = np.empty((10, NJ, B)), np.empty((55, NJ, B))
+    jac = np.empty((10, len(LINCOV_COLS), NJ, B)) if want_jacobian else None
+    _lib.check(L.ascent_covariance_history_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(sig), _ptr(sig_u), _ptr(gu),
+                                                 _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(sn), stride, _ptr(nom), _ptr(cov),
+                                                 _ptr(jac), device, None, 0))
+    full = np.empty((B, NJ, 10, 10))
+    iu = np.triu_indices(10)
+    full[:, :, iu[0], iu[1]] = cov.transpose(2, 1, 0)
+    full[:, :, iu[1], iu[0]] = cov.transpose(2, 1, 0)
+    return LinearCorridor(nodes, np.ascontiguousarray(nom.transpose(2, 1, 0)), full,
+                          None if jac is None else np.ascontiguousarray(jac.transpose(3, 2, 0, 1)))
+
+
 def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, control_sigma=None, tf_sigma=None, z0_sigma=None,
                    samples: int = 256, seed: int = 0, xi=None, keep_samples: bool = False, scheme=0, formulation=0, terminal=0,
                    move_penalty: bool = False, substeps: int = 0, device: int = 0, guidance: GuidanceResult | None = None,
@@ -561,11 +669,7 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     if xi.ndim != 2 or xi.shape[0] != 24 + K:
         raise ValueError(f"xi must have shape (24 + K, samples) = ({24 + K}, samples)")
     S = xi.shape[1]
-    zs, ps = _sigma_rows(z0_sigma, 7, B, "z0_sigma"), _sigma_rows(param_sigma, 16, B, "param_sigma")
-    ts = _sigma_rows(None if tf_sigma is None else np.asarray(tf_sigma, dtype=np.float64)[..., None], 1, B, "tf_sigma")
-    us = _sigma_rows(control_sigma, K, B, "control_sigma")
-    sig = np.ascontiguousarray(np.concatenate([zs, ps, ts], axis=1).T)
-    sig_u = np.ascontiguousarray(us.T) if control_sigma is not None else None
+    zs, ps, ts, us, sig, sig_u = _dispersion_sigmas(z0_sigma, param_sigma, tf_sigma, control_sigma, K, B)
     stats = np.empty((82, B))
     smp = np.empty((9 if guidance is None and not stride else 12, S, B)) if keep_samples else None
     hist = hsmp = None
@@ -589,38 +693,17 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
         _lib.check(L.ascent_disperse_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
                                            _ptr(stats), _ptr(smp), device, None, 0))
     else:
-        gu = np.ascontiguousarray(np.asarray(guidance.gain_u, dtype=np.float64).transpose(2, 1, 0))
-        if gu.shape != (7, K, B):
-            raise ValueError(f"guidance.gain_u must have shape {(B, K, 7)}")
-        gt = None if guidance.gain_t is None else np.ascontiguousarray(np.asarray(guidance.gain_t, dtype=np.float64).T)
-        if gt is not None and gt.shape != (7, B):
-            raise ValueError(f"guidance.gain_t must have shape {(B, 7)}")
-        sm = None if gt is None else _sigma_rows(np.asarray(guidance.stretch_max, dtype=np.float64)[..., None], 1, B, "stretch_max")[:, 0].copy()
+        gu, gt, sm = _feedback_arrays(guidance, K, B)
         if not navigated and stride:
             with_history(gu, gt, sm, None, None, None, None, None)
         elif not navigated:
             _lib.check(L.ascent_disperse_guided_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
                                                       _ptr(gu), _ptr(gt), _ptr(sm), _ptr(stats), _ptr(smp), device, None, 0))
         else:
-            fu = ft = fk = None
-            if ffu is not None:
-                fu = np.ascontiguousarray(np.asarray(ffu, dtype=np.float64).T)
-                if fu.shape != (K, B):
-                    raise ValueError(f"guidance.ff_u must have shape {(B, K)}")
-                ft, fk = getattr(guidance, "ff_t", None), getattr(guidance, "ff_know", None)
-                if ft is not None:
-                    ft = np.ascontiguousarray(np.asarray(ft, dtype=np.float64))
-                    if ft.shape != (B,):
-                        raise ValueError(f"guidance.ff_t must have shape {(B,)}")
-                if fk is not None:
-                    fk = np.ascontiguousarray(np.asarray(fk, dtype=np.float64).T)
-                    if fk.shape != (16, B):
-                        raise ValueError(f"guidance.ff_know must have shape {(B, 16)}")
+            fu, ft, fk = _feedforward_arrays(guidance, K, B)
             sn = None
             if nav_sigma is not None or knowledge_sigma is not None:
-                ks = _sigma_rows(None if knowledge_sigma is None else np.asarray(knowledge_sigma, dtype=np.float64)[..., None], 1, B,
-                                 "knowledge_sigma")
-                nav_s = np.concatenate([_sigma_rows(nav_sigma, 7, B, "nav_sigma"), ks], axis=1)
+                nav_s = _nav_sigma_rows(nav_sigma, knowledge_sigma, B)
                 sn = np.ascontiguousarray(nav_s.T)
                 if xi_nav is None:
                     xi_nav = np.random.default_rng(nav_seed).standard_normal((8, S))
