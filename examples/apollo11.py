@@ -210,12 +210,16 @@ def lincov_report(name, lc, d, params, tf, outdir=None, figure=None):
         fig.savefig(os.path.join(outdir, figure or "lincov_%s.png" % name.replace(" ", "_")), dpi=300)
 
 
-def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=False, corridor=False, outdir=None, lincov=False):
+def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=False, corridor=False, outdir=None, lincov=False,
+          nav_tau=None, knowledge_tau=None):
     """The trimmed solution under the same dispersions, open loop and steering back to the nominal with a cutoff on the state.
     The cutoff channel stretches the last step only, T / K = 2.2 s here: 50 N of 15 kN over a 435 s burn is 1.4 s (1-sigma) of burn
     time, so the stretch is allowed +-2 steps; at stretch_max = 0.5 it sits on its bound for most samples.
     corridor: every flight flown with its per-node history, and the lines of corridor_report for each.
-    lincov: the open and the closed loop flown once more with their history, beside linear_corridor's band (lincov_report)."""
+    lincov: the open and the closed loop flown once more with their history, beside linear_corridor's band (lincov_report).
+    nav_tau, knowledge_tau (seconds; with feedforward, corridor and lincov): the navigation bias as a stationary first-order
+    Gauss-Markov process of that correlation time and the thrust estimate converging from its 10 N with that time constant
+    (steady sigma 0): the sampled and the linear altitude band side by side, next to those of the frozen bias."""
     from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, guidance_gains, linear_corridor, trim_batch
     res = m.result
     kw = dict(scheme=scheme, formulation=m._formulation)
@@ -254,6 +258,22 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
         if corridor:
             corridor_report("thrust known", known, res.params, t.tf[0], outdir)
             corridor_report("known to 10 N", nav, res.params, t.tf[0], outdir)
+        if corridor and lincov and (nav_tau is not None or knowledge_tau is not None):
+            # the same errors, time-varying: the bias a stationary process, the thrust estimate converging to the truth
+            nkw = dict(guidance=gf, knowledge_sigma=10.0, nav_sigma=NAV_BIAS, nav_tau=nav_tau, knowledge_tau=knowledge_tau,
+                       knowledge_steady_sigma=None if knowledge_tau is None else 0.0)
+            lkw = dict(param_sigma=thrust, control_sigma=1e-3, **kw)
+            drift = disperse_batch(res.params, t.blob, res.nt, keep_samples=True, **nkw, **dkw)
+            print("time-varying navigation error: nav_tau %s s, knowledge_tau %s s" % (nav_tau, knowledge_tau))
+            print("flown altitude 1-sigma (m)   frozen bias   time-varying")
+            for name, q in (("periapsis", 7), ("apoapsis", 8)):
+                print("%-24s %15.2f %14.2f" % (name, nav.std[0, q], drift.std[0, q]))
+            lincov_report("frozen bias", linear_corridor(res.params, t.blob, res.nt, guidance=gf, knowledge_sigma=10.0, nav_sigma=NAV_BIAS, **lkw),
+                          nav, res.params, t.tf[0], outdir)
+            lincov_report("time-varying", linear_corridor(res.params, t.blob, res.nt, **nkw, **lkw), drift, res.params, t.tf[0], outdir)
+            for name, d_, lc_ in (("frozen bias", nav, linear_corridor(res.params, t.blob, res.nt, guidance=gf, knowledge_sigma=10.0, nav_sigma=NAV_BIAS, history=res.nt - 1, **lkw)),
+                                  ("time-varying", drift, linear_corridor(res.params, t.blob, res.nt, history=res.nt - 1, **nkw, **lkw))):
+                print("%s: closed-loop 1-sigma altitude at burnout: linear +-%.2f m; Monte Carlo +-%.2f m" % (name, lc_.std[0, -1, 7], d_.history.std[0, -1, 7]))
     if lincov:
         lkw = dict(param_sigma=thrust, control_sigma=1e-3, **kw)
         hkw = dict(dkw, history=True)
@@ -303,12 +323,16 @@ if __name__ == "__main__":
     ap.add_argument("--guide", action="store_true", help="trim, compute LQ feedback gains and fly 1024 dispersed samples open loop and closed loop; prints both 1-sigmas of the flown apsides")
     ap.add_argument("--feedforward", action="store_true", help="with --guide: also fly the same draws with the thrust feed-forward, once with the thrust known exactly and once known to 10 N (1-sigma) under a navigation bias of 1-sigma %g (scaled; %.1f m) on both positions and %g (scaled; %.1f cm/s) on both velocities" % (NAV_BIAS[0], NAV_BIAS[0] * ORBIT["periapsis"], NAV_BIAS[2], NAV_BIAS[2] * ORBIT["periapsis"] * 100))
     ap.add_argument("--corridor", action="store_true", help="with --disperse or --guide: reduce the samples at every node as well (disperse_batch(history=True)); prints, per flight flown, the widest 1-sigma altitude band, the lowest altitude any sample reached, the largest excursion of the angle beyond its bounds and the step with the most clipped commands, and writes corridor.png (with --guide: of the closed loop; the other flights as corridor_<flight>.png)")
+    ap.add_argument("--nav-tau", type=float, default=None, metavar="SECONDS", help="with --guide --feedforward --corridor --lincov: the navigation bias as a stationary first-order Gauss-Markov process of this correlation time; prints the sampled and the linear altitude band beside those of the frozen bias")
+    ap.add_argument("--knowledge-tau", type=float, default=None, metavar="SECONDS", help="with --guide --feedforward --corridor --lincov: the 10 N error of the thrust estimate decays with this time constant")
     ap.add_argument("--lincov", action="store_true", help="with --guide: the linear covariance corridor (linear_corridor) of the open and the closed loop beside their Monte Carlo history; prints both 1-sigma altitude bands at the node where the sampled one is widest, and writes lincov.png (closed loop) and lincov_open_loop.png")
     a = ap.parse_args()
     if a.corridor and not (a.disperse or a.guide):
         ap.error("--corridor needs --disperse or --guide")
     if a.lincov and not a.guide:
         ap.error("--lincov needs --guide")
+    if (a.nav_tau is not None or a.knowledge_tau is not None) and not (a.guide and a.feedforward and a.corridor and a.lincov):
+        ap.error("--nav-tau and --knowledge-tau need --guide --feedforward --corridor --lincov")
     figdir = None if a.no_plots else a.outdir
     model, variables, v_ins = build()
     if a.no_dcost:
@@ -324,6 +348,7 @@ if __name__ == "__main__":
     if a.disperse:
         disperse(model, a.scheme, corridor=a.corridor, outdir=figdir)
     if a.guide:
-        guide(model, a.scheme, feedforward=a.feedforward, corridor=a.corridor, outdir=figdir, lincov=a.lincov)
+        guide(model, a.scheme, feedforward=a.feedforward, corridor=a.corridor, outdir=figdir, lincov=a.lincov, nav_tau=a.nav_tau,
+              knowledge_tau=a.knowledge_tau)
     if not a.no_plots:
         plots(model, variables, a.outdir)

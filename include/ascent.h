@@ -602,6 +602,61 @@ int ascent_covariance_history_batch(const ascent_params *p, int64_t batch, const
                                     const double *sigma_nav_or_null, int32_t node_stride, double *nominal_out, double *cov_out,
                                     double *jac_hist_out_or_null, int device_id, void *hip_stream_or_null, int ptr_is_device);
 
+/* Time-varying navigation error: ascent_disperse_history_batch and ascent_covariance_history_batch with the eight knowledge
+ * channels a (0..6 the state-knowledge error in scaled units, 7 the error of theta-hat) as first-order Gauss-Markov sequences per
+ * sample instead of one bias per flight:
+ *   n_a,0 = sigma_nav[a] * xi_nav[a][s]                       (the navigated call's draw; applied where sigma_nav[a] != 0)
+ *   n_a,k = phi_a * n_a,k-1 + q_a * omega[a][k-1][s]          k = 1 .. K
+ * Step k (node k-1 -> k) steers on dz_{k-1} + nu_k, nu_k = n_{0..6,k}, with theta-hat_k = w . dp + n_{7,k}; the cutoff stretch of
+ *   step K uses the same nu_K and theta-hat_K.  The command law, the clip, the execution error, the validity rules and the
+ *   reductions are ascent_disperse_navigated_batch's.  q_a = sigma * sqrt(1 - phi_a^2) keeps a variance sigma^2 stationary; q_a = 0
+ *   with phi_a < 1 is an estimate that converges geometrically.
+ * nav_phi_or_null and nav_q_or_null [ASCENT_NAV_ROWS][batch], both or neither, only with gain_u; phi in [0, 1], q >= 0.
+ * A channel is frozen where phi_a == 1 and q_a == 0, or where the two arrays are null: it is never updated, its row of the draws
+ *   is never read, and it is computed exactly as in the parent call.  With all eight frozen both calls return the parent's bits
+ *   (with the arrays null they are the parent calls).  A channel that is not frozen is applied where sigma_nav[a] != 0 or
+ *   q_a != 0: with sigma_nav[a] == 0 and q_a != 0 it starts at 0.
+ *
+ * ascent_disperse_drifting_batch: the arguments of ascent_disperse_history_batch, and after sigma_nav_or_null the two arrays and
+ *   xi_drift_or_null [ASCENT_NAV_ROWS][K][samples], sample fastest, element (a, k, s) at ((a*K + k)*samples + s): omega[a][k][s],
+ *   the draw behind step k + 1; required with nav_q, read only in rows whose q_a != 0.  stats_out, samples_out_or_null, hist_out
+ *   and hist_samples_out_or_null exactly as ascent_disperse_history_batch defines them; hist_out is required (node_stride = K for
+ *   the end statistics alone).
+ * ascent_covariance_drifting_batch: the arguments of ascent_covariance_history_batch and the two arrays; outputs and layouts the same.
+ *   Columns 24..31 stay the derivative with respect to n_a,0: their forcing at step k is scaled by phi_a^k, the running product
+ *   multiplied once per step in ascending order.  The omega are independent unit white noise like eps_k, and the noise part is
+ *     N_j = sum_k sigma_u,k^2 m_jk m_jk' + sum_a sum_{k<=j} q_a^2 r_jak r_jak',
+ *   m_jk and r_jak the responses of y_j to a unit eps_k and a unit omega_a,k.  The kernel carries it as a recursion, with
+ *   kappa_k = (K_k, f_k), B_k = -g_k kappa_k' (- gamma_K (k_t, f_t)' on a stretched last step) and Phi_n = diag(phi):
+ *     D_k = Phi_n D_{k-1} Phi_n + diag(q^2)                    (8, diagonal; D_0 = 0)
+ *     C_k = A_k C_{k-1} Phi_n + B_k D_k                         (7 x 8, the covariance of dz_k and n_k; C_0 = 0)
+ *     Q_k = A_k Q_{k-1} A_k' + A_k C_{k-1} Phi_n B_k' + (its transpose) + B_k D_k B_k' + sigma_u,k^2 g_k g_k'
+ *   and rows 7 (altitude), 8 (du_j) and 9 (corr_j = K_j . dz_{j-1} + kappa_j . n_j) pick up the cross terms through
+ *   C_{j-1} Phi_n and D_j.  Q stays exactly symmetric.
+ * Refuse (ASCENT_E_ARG, before the device is looked at, no array touched) what the parent call refuses; nav_phi without nav_q or
+ *   the reverse; either without gain_u; nav_q without xi_drift (the Monte Carlo call); and, with host pointers, a phi outside
+ *   [0, 1], a q < 0 or a non-finite entry of either.  With device pointers the host does not read them: such a problem has every
+ *   sample invalid at every node (n = 0, the statistics NaN, the nominal rows the nominal flight's) and NaN rows of stats_out in
+ *   the Monte Carlo call, NaN rows of cov_out and jac_hist_out at every node in the covariance call; the work stays bounded and the other
+ *   problems of the batch are not affected.  Garbage blobs as in the parent calls.
+ * Host or device pointers; with device pointers and a stream both calls only enqueue (f_fly, f_history_drifting, f_disperse_stats,
+ *   f_history_stats; f_fly, l_lincov_drifting).  Device workspace: the parent call's. */
+int ascent_disperse_drifting_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                                   int32_t substeps, int32_t samples, const double *xi, const double *sigma,
+                                   const double *sigma_u_or_null, const double *gain_u_or_null, const double *gain_t_or_null,
+                                   const double *stretch_max_or_null, const double *ff_u_or_null, const double *ff_t_or_null,
+                                   const double *ff_know_or_null, const double *xi_nav_or_null, const double *sigma_nav_or_null,
+                                   const double *nav_phi_or_null, const double *nav_q_or_null, const double *xi_drift_or_null,
+                                   int32_t node_stride, double *stats_out, double *samples_out_or_null, double *hist_out,
+                                   double *hist_samples_out_or_null, int device_id, void *hip_stream_or_null, int ptr_is_device);
+int ascent_covariance_drifting_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                                     int32_t substeps, const double *sigma, const double *sigma_u_or_null,
+                                     const double *gain_u_or_null, const double *gain_t_or_null, const double *stretch_max_or_null,
+                                     const double *ff_u_or_null, const double *ff_t_or_null, const double *ff_know_or_null,
+                                     const double *sigma_nav_or_null, const double *nav_phi_or_null, const double *nav_q_or_null,
+                                     int32_t node_stride, double *nominal_out, double *cov_out, double *jac_hist_out_or_null,
+                                     int device_id, void *hip_stream_or_null, int ptr_is_device);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

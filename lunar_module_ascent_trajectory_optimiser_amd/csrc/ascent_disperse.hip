@@ -22,6 +22,8 @@
 // f_disperse<FORM, true> / f_history_guided  f_disperse / f_disperse_navigated with the per-node history of
 //          ascent_disperse_history_batch (HIST, an `if constexpr` in the two step loops): at a history node every lane holds its ten
 //          quantities, and the 42 values of the node's record are reduced like the end record -- one barrier per history node.
+// f_history_drifting    f_history_guided with the eight knowledge errors as first-order Gauss-Markov sequences
+//          (ascent_disperse_drifting_batch; guided_body<FORM, 2, true>): per step eight more draws, loaded with the next step's gains.
 // f_history_stats   one lane per (problem, node): the node's partial records added in ascending chunk order, then the 52 rows.
 // The kernels share their head (sample_lane, perturbed_sample) and their tail (end_rows, reduce_partial); only the step loops
 // differ.  One host function, disperse_run, launches whichever kernel the call's kind names.
@@ -340,7 +342,14 @@ __global__ __launch_bounds__(DB) void f_disperse(const ascent_params *__restrict
 // new arguments all null and no trace of them in the code.
 // HIST (f_history_guided): as in f_disperse; quantity 9 is the correction `dot` of the step, exactly 0 where the step has neither
 // gain nor feed-forward, and the clipped flag of the step is the comparison behind nclip.
-template <int FORM, bool NAV, bool HIST>
+// NAV = 2 (f_history_drifting; include/ascent.h: ascent_disperse_drifting_batch): the eight knowledge errors are first-order
+// Gauss-Markov sequences, n_k = phi n_{k-1} + q omega_{k-1}, n_0 the navigated call's draw; step k steers on n_k.  phi and q are
+// wave-uniform and held for the flight; the draws of the next step are loaded with its gains, one 512-byte run per wave and row,
+// and only for rows whose q is not zero.  A channel with phi = 1 and q = 0 is frozen: never updated, its draws never read, its
+// arithmetic the navigated call's.  A phi outside [0, 1] or a q that is negative or not finite makes every sample of the problem NaN.
+struct DriftArgs { const double *phi, *q, *xi; };
+
+template <int FORM, int NAV, bool HIST>
 ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
                          int nwg, long g0, const double *__restrict__ blob,
                          const double *__restrict__ traj, const double *__restrict__ fsum,
@@ -349,7 +358,8 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
                          const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
                          const double *__restrict__ ff_u, const double *__restrict__ ff_t, const double *__restrict__ ff_know,
                          const double *__restrict__ xi_nav, const double *__restrict__ sigma_nav,
-                         double *__restrict__ partial, double *__restrict__ samples_out, const HistArgs &H) {
+                         double *__restrict__ partial, double *__restrict__ samples_out, const HistArgs &H,
+                         const DriftArgs &G = DriftArgs{}) {
   __shared__ double red[DNW][NREC];
   Lane l;
   double cen[NQ], r[NQ];
@@ -375,6 +385,7 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
     for (int i = 0; i < 7; i++) kn[i] = gu[(size_t)i * K * B];
     // the navigation bias (applied where its sigma is not zero) and theta-hat = w . (applied field deviations) + the knowledge error
     double nu[7], th = 0.0, fn = 0.0;
+    [[maybe_unused]] double thw = 0.0;      // NAV = 2: theta-hat without the knowledge error
     bool nav[7];
     if constexpr (NAV) {
       ASC_UNROLL
@@ -393,8 +404,47 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
         }
       }
       const double s7 = sigma_nav ? sigma_nav[(size_t)7 * B + p] : 0.0;
+      if constexpr (NAV == 2) thw = th;
       if (s7 != 0.0) th += s7 * xi_nav[(size_t)7 * NS + s];
       fn = ff_u ? ff_u[p] : 0.0;
+    }
+    // the drifting channels: nu[0..6] and n7 are the errors the coming step steers on (n_1 before the first step), on[a] the draw
+    // behind the step after it.  A frozen channel keeps the values and the theta-hat computed above.
+    [[maybe_unused]] double ph[8], qd[8], on[8], n7 = 0.0;
+    [[maybe_unused]] bool upd[8];
+    [[maybe_unused]] const double *xd = nullptr;
+    if constexpr (NAV == 2) {
+      bool bad = false;
+      xd = G.xi + s;
+      ASC_UNROLL
+      for (int a = 0; a < 8; a++) {
+        ph[a] = G.phi ? G.phi[(size_t)a * B + p] : 1.0;
+        qd[a] = G.q ? G.q[(size_t)a * B + p] : 0.0;
+        bad = bad || !(ph[a] >= 0.0 && ph[a] <= 1.0) || !(qd[a] >= 0.0 && qd[a] <= 1.7976931348623157e308);
+        upd[a] = !(ph[a] == 1.0 && qd[a] == 0.0);
+        on[a] = qd[a] != 0.0 ? xd[(size_t)a * K * NS] : 0.0;
+      }
+      if (upd[7]) {
+        // the draw of channel 7 once more, through an empty asm: a product shared with theta-hat's above would keep that one
+        // from being fused into its addition, and a frozen channel would lose the navigated call's bits
+        const double s7 = sigma_nav ? sigma_nav[(size_t)7 * B + p] : 0.0;
+        double x7 = s7 != 0.0 ? xi_nav[(size_t)7 * NS + s] : 0.0;
+        asm volatile("" : "+v"(x7));
+        n7 = s7 * x7;
+      }
+      ASC_UNROLL
+      for (int a = 0; a < 7; a++) {
+        if (upd[a]) nu[a] = qd[a] != 0.0 ? ph[a] * nu[a] + qd[a] * on[a] : ph[a] * nu[a];
+        nav[a] = nav[a] || qd[a] != 0.0;
+      }
+      if (upd[7]) {
+        n7 = qd[7] != 0.0 ? ph[7] * n7 + qd[7] * on[7] : ph[7] * n7;
+        th = thw + n7;
+      }
+      if (bad) {
+        ASC_UNROLL
+        for (int i = 0; i < 7; i++) z[i] = NAN;
+      }
     }
     double nclip = 0.0, dmax = 0.0, stretch = 0.0;
     for (int k = 0; k < K; k++) {
@@ -444,7 +494,21 @@ ASC_DEV void guided_body(const ascent_params *__restrict__ P, long batch, int K,
       ASC_UNROLL
       for (int i = 0; i < 7; i++) kn[i] = gu[((size_t)i * K + kq) * B];
       if constexpr (NAV) fn = ff_u ? ff_u[(size_t)kq * B + p] : 0.0;
+      if constexpr (NAV == 2) {
+        ASC_UNROLL
+        for (int a = 0; a < 8; a++) on[a] = qd[a] != 0.0 ? xd[((size_t)a * K + kq) * NS] : 0.0;
+      }
       fly_step<FORM>(d, z, u, h, m);
+      if constexpr (NAV == 2) {      // n_{k+2} for the next step (after the last step: not used)
+        ASC_UNROLL
+        for (int a = 0; a < 7; a++) {
+          if (upd[a]) nu[a] = qd[a] != 0.0 ? ph[a] * nu[a] + qd[a] * on[a] : ph[a] * nu[a];
+        }
+        if (upd[7]) {
+          n7 = qd[7] != 0.0 ? ph[7] * n7 + qd[7] * on[7] : ph[7] * n7;
+          th = thw + n7;
+        }
+      }
       if constexpr (HIST) {
         if ((k + 1) % H.stride == 0 || k + 1 == K) {
           const double hq[HQ] = {z[0], z[1], z[2], z[3], z[4], z[5], z[6], altitude_of(z[IX], z[IY], prm.r_peri, prm.R0), u,
@@ -510,6 +574,19 @@ __global__ __launch_bounds__(DB) void f_history_guided(const ascent_params *__re
                                                        HistArgs hist) {
   guided_body<FORM, true, true>(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, xi, sigma, sigma_u, gain_u, gain_t, stretch_max,
                                 nav.ff_u, nav.ff_t, nav.ff_know, nav.xi_nav, nav.sigma_nav, partial, samples_out, hist);
+}
+
+template <int FORM>
+__global__ __launch_bounds__(DB) void f_history_drifting(const ascent_params *__restrict__ P, long batch, int K, int substeps, int samples,
+                                                         int nwg, long g0, const double *__restrict__ blob,
+                                                         const double *__restrict__ traj, const double *__restrict__ fsum,
+                                                         const double *__restrict__ xi, const double *__restrict__ sigma,
+                                                         const double *__restrict__ sigma_u, const double *__restrict__ gain_u,
+                                                         const double *__restrict__ gain_t, const double *__restrict__ stretch_max,
+                                                         NavArgs nav, DriftArgs drift, double *__restrict__ partial,
+                                                         double *__restrict__ samples_out, HistArgs hist) {
+  guided_body<FORM, 2, true>(P, batch, K, substeps, samples, nwg, g0, blob, traj, fsum, xi, sigma, sigma_u, gain_u, gain_t, stretch_max,
+                             nav.ff_u, nav.ff_t, nav.ff_know, nav.xi_nav, nav.sigma_nav, partial, samples_out, hist, drift);
 }
 
 __global__ __launch_bounds__(SW) void f_disperse_stats(long batch, int K, int nwg, const double *__restrict__ traj,
@@ -612,7 +689,12 @@ static void disperse_launch(const Call &c, DisperseKind kind, dim3 grid, dim3 bl
   double *partial = w.rest;
   if (io.hist) {      // the history: the partial records of the nodes follow the end records
     const HistArgs h{io.node_stride, history_nodes(c.K, io.node_stride), partial + (size_t)nwg * NREC * c.batch, io.hist_samples};
-    if (kind == DISPERSE_OPEN)
+    if (io.nav_phi)
+      hipLaunchKernelGGL((f_history_drifting<FORM>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob,
+                         w.traj, w.fsum, io.xi, io.sigma, io.sigma_u, io.gain_u, io.gain_t, io.stretch_max,
+                         NavArgs{io.ff_u, io.ff_t, io.ff_know, io.xi_nav, io.sigma_nav}, DriftArgs{io.nav_phi, io.nav_q, io.xi_drift}, partial,
+                         io.samples_out, h);
+    else if (kind == DISPERSE_OPEN)
       hipLaunchKernelGGL((f_disperse<FORM, true>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, samples, nwg, g0, io.blob,
                          w.traj, w.fsum, io.xi, io.sigma, io.sigma_u, partial, io.samples_out, h);
     else

@@ -22,7 +22,9 @@ enum DisperseKind { DISPERSE_OPEN = 0 /* ascent_disperse_batch */, DISPERSE_GUID
 // navigated: ff_u [K][batch], ff_t [batch], ff_know [16][batch], xi_nav [ASCENT_NAV_ROWS][samples], sigma_nav [ASCENT_NAV_ROWS][batch];
 // stats [ASCENT_DISPERSE_STAT_ROWS][batch], samples_out [9 (open) | ASCENT_GUIDED_SAMPLE_ROWS][samples][batch];
 // the history call (hist not null; samples_out then always ASCENT_GUIDED_SAMPLE_ROWS): node_stride, hist
-// [ASCENT_HISTORY_ROWS][NJ][batch], hist_samples [ASCENT_HISTORY_QUANTITIES][NJ][samples][batch].
+// [ASCENT_HISTORY_ROWS][NJ][batch], hist_samples [ASCENT_HISTORY_QUANTITIES][NJ][samples][batch];
+// the drifting call (ascent_disperse_drifting_batch; nav_phi not null, with hist and gain_u): nav_phi and nav_q
+// [ASCENT_NAV_ROWS][batch], xi_drift [ASCENT_NAV_ROWS][K][samples].
 struct DisperseIO {
   const double *blob, *xi, *sigma, *sigma_u;
   const double *gain_u, *gain_t, *stretch_max;
@@ -30,11 +32,13 @@ struct DisperseIO {
   double *stats, *samples_out;
   int node_stride;
   double *hist, *hist_samples;
+  const double *nav_phi, *nav_q, *xi_drift;
 };
 
 // io: device pointers, ws of disperse_ws_bytes.  Options already checked by the caller.  Only enqueues on c.stream: f_fly, the
 // kind's kernel -- f_disperse, f_disperse_guided or f_disperse_navigated, one launch per 2^22 workgroups -- and f_disperse_stats.
-// With io.hist: f_disperse<FORM, true> (open) or f_history_guided (guided and navigated alike) in the kernel's place, and f_history_stats last.
+// With io.hist: f_disperse<FORM, true> (open), f_history_guided (guided and navigated alike) or, with io.nav_phi, f_history_drifting
+// in the kernel's place, and f_history_stats last.
 // Returns ASCENT_OK / ASCENT_E_HIP.
 int disperse_run(const Call &c, DisperseKind kind, int substeps, int samples, const DisperseIO &io, double *ws);
 

@@ -266,6 +266,344 @@ __global__ __launch_bounds__(JB) void l_lincov(const ascent_params *__restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// l_lincov_drifting (include/ascent.h: ascent_covariance_drifting_batch): l_lincov with the eight knowledge errors as first-order
+// Gauss-Markov sequences n_k = Phi_n n_{k-1} + q omega_{k-1}, Phi_n = diag(phi).  The columns nu and theta-hat of X stay the
+// derivative with respect to n_0: their forcing at step k is scaled by the running product phi^k.  theta-hat = w . dp + n_7 then
+// has two responses, so X gains a 24th column: the response to the constant part w . dp, forced by f_k unscaled, which the
+// parameter columns take their (theta-hat column) w_c from; with phi_7 = 1 it has the bits of the column theta-hat.  The driving noise enters
+// the noise part beside Q: D_k = Phi_n D_{k-1} Phi_n + diag(q^2) (8, diagonal), C_k = A_k C_{k-1} Phi_n + B_k D_k (7 x 8, the
+// covariance of dz_k and n_k), Q_k = A_k Q_{k-1} A_k' + M + M' + B_k D_k B_k' + sigma_u,k^2 g_k g_k', M = A_k C_{k-1} Phi_n B_k',
+// B_k = -g_k kappa_k' (- gamma_K (k_t, f_t)' on a stretched last step), kappa_k = (K_k, f_k).
+// The workgroup stays l_lincov's 256 threads (compiled with a fifth wavefront for C, 320 threads, the kernel was held to 256
+// registers and used 580 bytes of scratch), so the lane map is new, with Q on the 28 entries of its upper triangle.  Still one phase and one barrier per step, no global load:
+//   lanes 0..167    X (7 x 24) as l_lincov, the forcing of the columns nu and theta-hat times phi^k
+//   lanes 168..223  entry (i, a) of C; the eight lanes of row 0 are the helpers as well, now the whole Cov(dz_k, corr_k) (7) and
+//                   Var(corr_k): l_lincov's A Q K and K' Q K plus the terms through C_{k-1} Phi_n and D_k, and each carries
+//                   phi^k and D_k of one channel
+//   lanes 228..255  entry (i, j), i <= j, of Q: both halves as l_lincov forms them, the terms of C and D formed once and added
+//                   to both, the average stored to (i, j) and (j, i), so Q stays exactly symmetric
+// C, D and phi^k are in LDS in two copies by the parity of the step, like X and Q; a lane that needs D_k forms it from D_{k-1}.
+// With every channel frozen (phi = 1, q = 0) the terms of C and D are not formed at all, and phi^k = 1 leaves every product
+// alone: the bits of l_lincov.  A phi outside [0, 1] or a q that is negative or not finite gives NaN rows at every node.
+constexpr int XCD = XC + 1, XND = 7 * XCD, X_TW = XC;      // X with the column of theta-hat's constant part
+constexpr int T_C = XND, T_QU = 228;                       // first lane of C and of the upper triangle of Q
+static_assert(T_C + 56 <= T_QU && T_QU + 28 == JB, "lane map of the drifting sweep");
+
+struct DriftCov { const double *phi, *q; };
+
+// D_k of a channel from D_{k-1}; not contracted, so that every lane that forms it has the same bits
+ASC_DEV double drift_var(double phi, double dold, double q2) {
+#pragma clang fp contract(off)
+  return (phi * dold) * phi + q2;
+}
+
+// what the Q lanes and the helpers share of the drifting terms: c1 = C_{k-1} Phi_n kappa, c2 = C_{k-1} Phi_n (k_t, f_t) (7 each),
+// skk = kappa' D_k kappa, skt = kappa' D_k (k_t, f_t), stt = (k_t, f_t)' D_k (k_t, f_t); c2, skt and stt only on a stretched last step
+struct DriftTerms { double c1[7], c2[7], skk, skt, stt; };
+
+ASC_DEV void drift_terms(const double *Co, const double *Do, const double *phs, const double *q2s, const double *kv, const double *kts,
+                         bool last, DriftTerms &T) {
+  double kp[8], tp[8];
+  T.skk = T.skt = T.stt = 0.0;
+  ASC_UNROLL
+  for (int a = 0; a < 8; a++) {
+    const double ka = kv[a], ta = last ? kts[a] : 0.0, dk = drift_var(phs[a], Do[a], q2s[a]);      // (kv[7] is f_k: ST_F = 7)
+    kp[a] = phs[a] * ka;
+    tp[a] = phs[a] * ta;
+    T.skk += (ka * ka) * dk;
+    T.skt += (ka * ta) * dk;
+    T.stt += (ta * ta) * dk;
+  }
+  ASC_UNROLL
+  for (int l = 0; l < 7; l++) {
+    double a1 = 0.0, a2 = 0.0;
+    ASC_UNROLL
+    for (int a = 0; a < 8; a++) {
+      a1 += Co[l * 8 + a] * kp[a];
+      a2 += Co[l * 8 + a] * tp[a];
+    }
+    T.c1[l] = a1;
+    T.c2[l] = a2;
+  }
+}
+
+template <int FORM>
+__global__ __launch_bounds__(JB) void l_lincov_drifting(const ascent_params *__restrict__ P, long batch, int K, int substeps,
+                                                        const double *__restrict__ blob, const double *__restrict__ traj, LincovArgs A,
+                                                        DriftCov G) {
+  static_assert(ST_F == 7, "kappa_k = (K_k, f_k) is the head of a staged step");
+  __shared__ double rec[CH * REC];
+  __shared__ double Xs[2][XND], Qs[2][49], nks[2][8], stp[CH][ST], nod[CH][7], cors[XCD], Ss[HQ * LC], sgs[LC], kts[8], wks[16];
+  __shared__ double Cs[2][56], Ds[2][8], pws[2][8], phs[8], q2s[8];
+  __shared__ int flags[2];                   // any channel drifting; any phi or q out of range
+  const long p = blockIdx.x;
+  const size_t B = (size_t)batch;
+  const int t = threadIdx.x, g = t >> 4, col = t & (NCOL - 1);
+  const int nt = K + 1;
+  const double *b = blob + p, *tr = traj + p;
+  const ascent_params prm = P[p];
+  const Der d = derive(prm);
+  const double tf = b[(size_t)(21 * K + S_TH) * B];
+  const double dt = (tf * d.T) / K;
+  const int m = flight_substeps(dt, substeps);
+  const double hs = dt / m;
+  const double smax = A.gain_t && A.stretch_max ? A.stretch_max[p] : 0.0;
+  const bool stretch = smax > 0.0;
+
+  if (t < XND) Xs[0][t] = t / XCD == t % XCD ? 1.0 : 0.0;
+  if (t < 49) Qs[0][t] = 0.0;
+  if (t < LC) sgs[t] = t < ASCENT_DISPERSE_COLS ? A.sigma[(size_t)t * B + p]
+                                                : A.sigma_nav ? A.sigma_nav[(size_t)(t - ASCENT_DISPERSE_COLS) * B + p] : 0.0;
+  if (t < 7) kts[t] = stretch ? A.gain_t[(size_t)t * B + p] : 0.0;
+  if (t == 7) kts[7] = stretch && A.ff_t ? A.ff_t[p] : 0.0;
+  if (t < 16) wks[t] = A.ff_know ? A.ff_know[(size_t)t * B + p] : 0.0;
+  if (t >= T_C && t < T_C + 56) Cs[0][t - T_C] = 0.0;
+  if (t >= T_C && t < T_C + 8) {
+    const int a = t - T_C;
+    const double ph = G.phi ? G.phi[(size_t)a * B + p] : 1.0, q = G.q ? G.q[(size_t)a * B + p] : 0.0;
+    phs[a] = ph;
+    q2s[a] = q * q;
+    Ds[0][a] = 0.0;
+    pws[0][a] = 1.0;
+  }
+  if (t == JB - 1) {                         // the two flags, by one lane in ascending channel order
+    int drift = 0, bad = 0;
+    for (int a = 0; a < 8; a++) {
+      const double ph = G.phi ? G.phi[(size_t)a * B + p] : 1.0, q = G.q ? G.q[(size_t)a * B + p] : 0.0;
+      drift |= !(ph == 1.0 && q == 0.0);
+      bad |= !(ph >= 0.0 && ph <= 1.0) || !(q >= 0.0 && q <= 1.7976931348623157e308);
+    }
+    flags[0] = drift;
+    flags[1] = bad;
+  }
+
+  const int nch = (K + CH - 1) / CH;
+  for (int c = 0; c < nch; c++) {
+    const int k = c * CH + g + 1;             // this group's step: node k-1 -> k
+    if (k <= K) {
+      double z[7], dz[7];
+      load_node(tr, B, nt, k - 1, z);
+      const double u = b[(size_t)(7 * K + k - 1) * B];
+      if (col < 7) {
+        stp[g][col] = A.gain_u ? A.gain_u[((size_t)col * K + k - 1) * B + p] : 0.0;
+      } else if (col == ST_F) {
+        stp[g][ST_F] = A.ff_u ? A.ff_u[(size_t)(k - 1) * B + p] : 0.0;
+      } else if (col == ST_SU2) {
+        const double su = A.sigma_u ? A.sigma_u[(size_t)(k - 1) * B + p] : 0.0;
+        stp[g][ST_SU2] = su * su;
+      } else if (col == ST_U) {
+        stp[g][ST_U] = u;
+      } else if (col == NCOL - 1) {           // the nominal node the step ends at, f_fly's
+        double zk[7];
+        load_node(tr, B, nt, k, zk);
+        ASC_UNROLL
+        for (int i = 0; i < 7; i++) nod[g][i] = zk[i];
+      }
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) dz[i] = col == i ? 1.0 : 0.0;
+      fly_step_tangent<FORM>(d, z, dz, u, hs, m, col);
+      ASC_UNROLL
+      for (int i = 0; i < 7; i++) rec[g * REC + i * NCOL + col] = dz[i];
+    }
+    __syncthreads();
+    const bool drift = flags[0] != 0, ok = finite1(tf) && flags[1] == 0;
+    const int top = K - c * CH < CH ? K - c * CH : CH;
+    for (int s = 0; s < top; s++) {
+      const int kk = c * CH + s, par = kk & 1;            // step kk + 1 reads copy par and writes the other
+      const double *R = rec + s * REC, *kv = stp[s], *Xo = Xs[par], *Qo = Qs[par], *Co = Cs[par], *Do = Ds[par];
+      const bool last = stretch && kk + 1 == K;
+      if (t < XND) {
+        const int xi = t / XCD, xc = t - xi * XCD;
+        const int ch = xc >= X_NU && xc <= X_TH ? xc - X_NU : 0;
+        const double pw = pws[par][ch] * phs[ch];          // phi^k of the column's channel (used by the columns nu and theta-hat only)
+        double x[7], corr = 0.0, a = 0.0;
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) x[l] = Xo[l * XCD + xc];
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) corr += kv[l] * x[l];
+        if (xc >= X_NU && xc < X_TH) corr += kv[xc - X_NU] * pw;
+        if (xc == X_TH) corr += kv[ST_F] * pw;
+        if (xc == X_TW) corr += kv[ST_F];
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) a += R[xi * NCOL + l] * x[l];
+        a -= R[xi * NCOL + C_U] * corr;
+        if (xc >= X_COEF && xc < X_NU) a += R[xi * NCOL + C_DT + (xc - X_COEF)];
+        if (last) {
+          double tau = 0.0;
+          ASC_UNROLL
+          for (int l = 0; l < 7; l++) tau -= kts[l] * x[l];
+          if (xc >= X_NU && xc < X_TH) tau -= kts[xc - X_NU] * pw;
+          if (xc == X_TH) tau -= kts[7] * pw;
+          if (xc == X_TW) tau -= kts[7];
+          a += (dt * R[xi * NCOL + C_DT]) * tau;
+        }
+        Xs[par ^ 1][t] = a;
+        if (xi == 0) cors[xc] = corr;
+      } else if (t >= T_QU) {
+        int qi = 0, qj = t - T_QU;
+        while (qj >= 7 - qi) { qj -= 7 - qi; qi++; }
+        qj += qi;                             // entry (qi, qj), qi <= qj
+        double ai[7], aj[7], nij = 0.0, nji = 0.0;
+        closed_row(R, kv, kts, last, dt, qi, ai);
+        closed_row(R, kv, kts, last, dt, qj, aj);
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) {
+          double wi = 0.0, wj = 0.0;
+          ASC_UNROLL
+          for (int mm = 0; mm < 7; mm++) {
+            const double ql = Qo[l * 7 + mm];
+            wj += ql * aj[mm];
+            wi += ql * ai[mm];
+          }
+          nij += ai[l] * wj;
+          nji += aj[l] * wi;
+        }
+        const double su2 = kv[ST_SU2];
+        const double gg = su2 != 0.0 ? su2 * (R[qi * NCOL + C_U] * R[qj * NCOL + C_U]) : 0.0;
+        double hij = nij + gg, hji = nji + gg;
+        if (drift) {                          // M + M' + B D B' of the entry
+          DriftTerms T;
+          drift_terms(Co, Do, phs, q2s, kv, kts, last, T);
+          const int lo = qi, hi = qj;
+          double l1 = 0.0, l2 = 0.0, h1 = 0.0, h2 = 0.0;
+          ASC_UNROLL
+          for (int l = 0; l < 7; l++) {
+            l1 += ai[l] * T.c1[l];
+            l2 += ai[l] * T.c2[l];
+            h1 += aj[l] * T.c1[l];
+            h2 += aj[l] * T.c2[l];
+          }
+          const double gl = R[lo * NCOL + C_U], gh = R[hi * NCOL + C_U];
+          double e = T.skk * (gl * gh) - (l1 * gh + h1 * gl);
+          if (last) {
+            const double tl = dt * R[lo * NCOL + C_DT], th = dt * R[hi * NCOL + C_DT];
+            e += T.skt * (gl * th + tl * gh) + T.stt * (tl * th) - (l2 * th + h2 * tl);
+          }
+          hij += e;
+          hji += e;
+        }
+        const double qn = 0.5 * (hij + hji);
+        Qs[par ^ 1][qi * 7 + qj] = qn;
+        Qs[par ^ 1][qj * 7 + qi] = qn;
+      } else if (t >= T_C && t < T_C + 56) {
+        const int q = t - T_C, ci = q >> 3, ca = q & 7;
+        double v = 0.0;
+        if (drift) {
+          double ar[7], ac = 0.0;
+          closed_row(R, kv, kts, last, dt, ci, ar);
+          ASC_UNROLL
+          for (int l = 0; l < 7; l++) ac += ar[l] * Co[l * 8 + ca];
+          double bia = -R[ci * NCOL + C_U] * kv[ca];
+          if (last) bia -= (dt * R[ci * NCOL + C_DT]) * kts[ca];
+          v = ac * phs[ca] + bia * drift_var(phs[ca], Do[ca], q2s[ca]);
+        }
+        Cs[par ^ 1][q] = v;
+      }
+      if (t >= T_C && t < T_C + 8) {          // the helpers: the lanes of row 0 of C
+        const int q = t - T_C;
+        double v[7], ar[7], a = 0.0;
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) {
+          double w = 0.0;
+          ASC_UNROLL
+          for (int mm = 0; mm < 7; mm++) w += Qo[l * 7 + mm] * kv[mm];
+          v[l] = w;
+        }
+        closed_row(R, kv, kts, last, dt, q < 7 ? q : 0, ar);
+        ASC_UNROLL
+        for (int l = 0; l < 7; l++) a += (q < 7 ? ar[l] : kv[l]) * v[l];
+        if (drift) {
+          DriftTerms T;
+          drift_terms(Co, Do, phs, q2s, kv, kts, last, T);
+          double ac1 = 0.0, k1 = 0.0, k2 = 0.0;
+          ASC_UNROLL
+          for (int l = 0; l < 7; l++) {
+            ac1 += ar[l] * T.c1[l];
+            k1 += kv[l] * T.c1[l];
+            k2 += kv[l] * T.c2[l];
+          }
+          if (q < 7) {
+            double e = ac1 - R[q * NCOL + C_U] * (k1 + T.skk);
+            if (last) e -= (dt * R[q * NCOL + C_DT]) * (k2 + T.skt);
+            a += e;
+          } else {
+            a += 2.0 * k1 + T.skk;
+          }
+        }
+        nks[par][q] = a;
+        pws[par ^ 1][q] = pws[par][q] * phs[q];
+        Ds[par ^ 1][q] = drift_var(phs[q], Do[q], q2s[q]);
+      }
+      __syncthreads();
+      const int j = kk + 1;
+      if (j % A.stride == 0 || j == K) {                  // a history node (uniform)
+        const int i = (j + A.stride - 1) / A.stride - 1;
+        const double *Xn = Xs[par ^ 1], *Qn = Qs[par ^ 1], *zn = nod[s];
+        const double S = prm.r_peri;
+        const double Xp = zn[IX] * S, Yp = zn[IY] * S + prm.R0, rr = sqrt(Xp * Xp + Yp * Yp);
+        const double ex = Xp / rr, ey = Yp / rr, gax = S * ex, gay = S * ey;
+        if (t < HQ) {
+          double cp[XCD], o[LC];
+          ASC_UNROLL
+          for (int cc = 0; cc < XCD; cc++) {
+            const double xr = Xn[(t < 7 ? t : 0) * XCD + cc], al = gax * Xn[IX * XCD + cc] + gay * Xn[IY * XCD + cc], cr = cors[cc];
+            cp[cc] = t < 7 ? xr : t == 7 ? al : t == 8 ? -cr : cr;
+          }
+          const ApsisDirect dir = {0.0, 0.0, t == 7 ? ey - 1.0 : 0.0, t == 7 ? zn[IX] * ex + zn[IY] * ey : 0.0};
+          jac_columns<FORM>(prm, d, tf, K, cp, cp + X_COEF, dir, o);
+          if (A.ff_know) {
+            ASC_UNROLL
+            for (int cc = 0; cc < 16; cc++) o[7 + cc] += cp[X_TW] * wks[cc];
+          }
+          ASC_UNROLL
+          for (int a = 0; a < ASCENT_NAV_ROWS; a++) o[ASCENT_DISPERSE_COLS + a] = cp[X_NU + a];
+          if (!ok) {                          // no final time, or a phi or q out of range: NaN rows, the structurally zero columns included
+            ASC_UNROLL
+            for (int cc = 0; cc < LC; cc++) o[cc] = NAN;
+          }
+          ASC_UNROLL
+          for (int cc = 0; cc < LC; cc++) {
+            Ss[t * LC + cc] = o[cc];
+            if (A.jac) A.jac[(((size_t)t * LC + cc) * A.nj + i) * B + p] = o[cc];
+          }
+          const double nom = t < 7 ? zn[t] : t == 7 ? nominal_altitude(zn[IX], zn[IY], prm.r_peri, prm.R0) : t == 8 ? kv[ST_U] : 0.0;
+          A.nominal[((size_t)t * A.nj + i) * B + p] = nom;
+        }
+        __syncthreads();
+        if (t < NCOV) {
+          int a = 0, rem = t;
+          while (rem >= HQ - a) { rem -= HQ - a; a++; }
+          const int bq = a + rem;             // entry (a, bq), a <= bq
+          double acc = 0.0;
+          for (int cc = 0; cc < LC; cc++) {
+            const double sg = sgs[cc];
+            if (sg != 0.0) acc += (Ss[a * LC + cc] * Ss[bq * LC + cc]) * (sg * sg);
+          }
+          // the noise part as in l_lincov: the helpers already hold the covariances with corr_j
+          const double *nk = nks[par];
+          const double su2 = kv[ST_SU2];
+          const int ar = a < 7 ? a : 0;
+          const double qa = gax * Qn[ar * 7 + IX] + gay * Qn[ar * 7 + IY];
+          const double n8 = (su2 != 0.0 ? su2 * R[ar * NCOL + C_U] : 0.0) - nk[ar];
+          const double n8x = (su2 != 0.0 ? su2 * R[IX * NCOL + C_U] : 0.0) - nk[IX], n8y = (su2 != 0.0 ? su2 * R[IY * NCOL + C_U] : 0.0) - nk[IY];
+          double n;
+          if (bq < 7) n = Qn[a * 7 + bq];
+          else if (a < 7) n = bq == 7 ? qa : bq == 8 ? n8 : nk[a];
+          else if (a == 7)
+            n = bq == 7 ? gax * (gax * Qn[IX * 7 + IX] + gay * Qn[IX * 7 + IY]) + gay * (gax * Qn[IY * 7 + IX] + gay * Qn[IY * 7 + IY])
+                : bq == 8 ? gax * n8x + gay * n8y : gax * nk[IX] + gay * nk[IY];
+          else if (a == 8) n = bq == 8 ? nk[7] + su2 : -nk[7];
+          else n = nk[7];
+          acc += n;
+          A.cov[((size_t)t * A.nj + i) * B + p] = ok ? acc : NAN;
+        }
+      }
+    }
+    __syncthreads();                          // the records and the staged steps are rewritten by the next chunk
+  }
+}
+
 }  // namespace
 
 size_t lincov_ws_bytes(int K, long batch) { return flight_ws_bytes(K, batch); }
@@ -276,7 +614,11 @@ int lincov_run(const Call &c, int substeps, const LincovIO &io, double *ws) {
   const LincovArgs a{io.sigma, io.sigma_u, io.gain_u, io.gain_t, io.stretch_max, io.ff_u, io.ff_t, io.ff_know, io.sigma_nav,
                      io.node_stride, history_nodes(c.K, io.node_stride), io.nominal, io.cov, io.jac};
   const dim3 grid((unsigned)c.batch), block(JB);
-  if (c.form == 1) hipLaunchKernelGGL((l_lincov<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, io.blob, w.traj, a);
+  if (io.nav_phi) {
+    const DriftCov g{io.nav_phi, io.nav_q};
+    if (c.form == 1) hipLaunchKernelGGL((l_lincov_drifting<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, io.blob, w.traj, a, g);
+    else hipLaunchKernelGGL((l_lincov_drifting<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, io.blob, w.traj, a, g);
+  } else if (c.form == 1) hipLaunchKernelGGL((l_lincov<1>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, io.blob, w.traj, a);
   else hipLaunchKernelGGL((l_lincov<0>), grid, block, 0, c.stream, c.dp, c.batch, c.K, substeps, io.blob, w.traj, a);
   ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;

@@ -21,10 +21,11 @@ struct LincovIO {
   const double *ff_u, *ff_t, *ff_know, *sigma_nav;
   int node_stride;
   double *nominal, *cov, *jac;
+  const double *nav_phi, *nav_q;      // ascent_covariance_drifting_batch: [ASCENT_NAV_ROWS][batch] each, both or neither
 };
 
 // io: device pointers, ws of lincov_ws_bytes.  Options already checked by the caller.  Only enqueues two kernels on c.stream:
-// f_fly, then l_lincov.  Returns ASCENT_OK / ASCENT_E_HIP.
+// f_fly, then l_lincov (with io.nav_phi: l_lincov_drifting).  Returns ASCENT_OK / ASCENT_E_HIP.
 int lincov_run(const Call &c, int substeps, const LincovIO &io, double *ws);
 
 }  // namespace ascent

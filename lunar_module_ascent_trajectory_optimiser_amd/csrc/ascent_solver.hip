@@ -860,11 +860,27 @@ int check_history_nodes(const ascent_opts *o, int32_t node_stride, const double 
   return 0;
 }
 
+// The refusals ascent_disperse_drifting_batch and ascent_covariance_drifting_batch add to their parents': phi and q together and
+// with gain_u, the draws (monte_carlo) with q, and with host pointers every phi in [0, 1] and every q >= 0 and finite
+int check_drift(const double *nav_phi, const double *nav_q, const double *xi_drift, bool monte_carlo, const double *gain_u, int64_t batch,
+                int ptr_is_device) {
+  if ((nav_phi != nullptr) != (nav_q != nullptr)) { snprintf(g_err, sizeof g_err, "nav_phi and nav_q come together"); return ASCENT_E_ARG; }
+  if (nav_phi && !gain_u) { snprintf(g_err, sizeof g_err, "nav_phi and nav_q need gain_u"); return ASCENT_E_ARG; }
+  if (monte_carlo && nav_q && !xi_drift) { snprintf(g_err, sizeof g_err, "nav_q needs xi_drift"); return ASCENT_E_ARG; }
+  if (nav_phi && !ptr_is_device) {
+    for (int64_t i = 0; i < ASCENT_NAV_ROWS * batch; i++) {
+      if (!(nav_phi[i] >= 0.0 && nav_phi[i] <= 1.0)) { snprintf(g_err, sizeof g_err, "nav_phi outside [0, 1] (channel %d, problem %lld)", (int)(i / batch), (long long)(i % batch)); return ASCENT_E_ARG; }
+      if (!(nav_q[i] >= 0.0 && std::isfinite(nav_q[i]))) { snprintf(g_err, sizeof g_err, "nav_q negative or not finite (channel %d, problem %lld)", (int)(i / batch), (long long)(i % batch)); return ASCENT_E_ARG; }
+    }
+  }
+  return 0;
+}
+
 // ascent_disperse_batch, ascent_disperse_guided_batch and ascent_disperse_navigated_batch: io holds the caller's pointers.
 // history: ascent_disperse_history_batch, the kind picked from gain_u by the entry point; its own refusals stand after the
 // refusals the three share, each of which keeps its place and its text.
 int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, int32_t samples, DisperseKind kind,
-                  DisperseIO io, int device_id, void *stream_, int ptr_is_device, bool history = false) {
+                  DisperseIO io, int device_id, void *stream_, int ptr_is_device, bool history = false, bool drifting = false) {
   BlobCall b(p, batch, o, io.blob, stream_, ptr_is_device);
   int rc = b.options();
   if (rc) return rc;
@@ -878,7 +894,9 @@ int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, i
     if (!io.hist) { snprintf(g_err, sizeof g_err, "null hist_out"); return ASCENT_E_ARG; }
     if ((rc = check_history_nodes(o, io.node_stride, io.gain_u, io.gain_t || io.stretch_max || io.ff_u || io.ff_t || io.ff_know || io.xi_nav || io.sigma_nav))) return rc;
   }
-  if ((rc = b.solvable()) || (rc = b.open(device_id, disperse_ws_bytes(o->n_nodes - 1, (long)batch, samples, history ? io.node_stride : 0)))) return rc;
+  if ((rc = b.solvable())) return rc;
+  if (drifting && (rc = check_drift(io.nav_phi, io.nav_q, io.xi_drift, true, io.gain_u, batch, ptr_is_device))) return rc;
+  if ((rc = b.open(device_id, disperse_ws_bytes(o->n_nodes - 1, (long)batch, samples, history ? io.node_stride : 0)))) return rc;
   Staging &st = b.st;
   const size_t K = (size_t)b.K, B = (size_t)batch, S = (size_t)samples;
   io.blob = b.blob;
@@ -893,6 +911,9 @@ int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, i
   io.ff_know = st.in(io.ff_know, 16 * B);
   io.xi_nav = st.in(io.xi_nav, ASCENT_NAV_ROWS * S);
   io.sigma_nav = st.in(io.sigma_nav, ASCENT_NAV_ROWS * B);
+  io.nav_phi = st.in(io.nav_phi, ASCENT_NAV_ROWS * B);
+  io.nav_q = st.in(io.nav_q, ASCENT_NAV_ROWS * B);
+  io.xi_drift = st.in(io.nav_q ? io.xi_drift : nullptr, ASCENT_NAV_ROWS * K * S);
   io.stats = st.out(io.stats, ASCENT_DISPERSE_STAT_ROWS * B);
   io.samples_out = st.out(io.samples_out, (kind == DISPERSE_OPEN && !history ? ASCENT_DISPERSE_ROWS : ASCENT_GUIDED_SAMPLE_ROWS) * S * B);
   if (history) {
@@ -906,14 +927,16 @@ int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, i
 
 // ascent_covariance_history_batch: io holds the caller's pointers.  The order of the refusals is disperse_call's.
 int lincov_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, LincovIO io, int device_id, void *stream_,
-                int ptr_is_device) {
+                int ptr_is_device, bool drifting = false) {
   BlobCall b(p, batch, o, io.blob, stream_, ptr_is_device);
   int rc = b.options();
   if (rc) return rc;
   if (!io.blob || !io.sigma || !io.nominal || !io.cov) { snprintf(g_err, sizeof g_err, "null solution blob, sigma, nominal_out or cov_out"); return ASCENT_E_ARG; }
   if ((rc = check_ff_know(io.ff_know, io.ff_u)) || (rc = check_substeps(substeps))) return rc;
   if ((rc = check_history_nodes(o, io.node_stride, io.gain_u, io.gain_t || io.stretch_max || io.ff_u || io.ff_t || io.ff_know || io.sigma_nav))) return rc;
-  if ((rc = b.solvable()) || (rc = b.open(device_id, lincov_ws_bytes(o->n_nodes - 1, (long)batch)))) return rc;
+  if ((rc = b.solvable())) return rc;
+  if (drifting && (rc = check_drift(io.nav_phi, io.nav_q, nullptr, false, io.gain_u, batch, ptr_is_device))) return rc;
+  if ((rc = b.open(device_id, lincov_ws_bytes(o->n_nodes - 1, (long)batch)))) return rc;
   Staging &st = b.st;
   const size_t K = (size_t)b.K, B = (size_t)batch, NJ = (size_t)history_nodes(b.K, io.node_stride);
   io.blob = b.blob;
@@ -926,6 +949,8 @@ int lincov_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int
   io.ff_t = st.in(io.ff_t, B);
   io.ff_know = st.in(io.ff_know, 16 * B);
   io.sigma_nav = st.in(io.sigma_nav, ASCENT_NAV_ROWS * B);
+  io.nav_phi = st.in(io.nav_phi, ASCENT_NAV_ROWS * B);
+  io.nav_q = st.in(io.nav_q, ASCENT_NAV_ROWS * B);
   io.nominal = st.out(io.nominal, ASCENT_HISTORY_QUANTITIES * NJ * B);
   io.cov = st.out(io.cov, ASCENT_LINCOV_COV_ROWS * NJ * B);
   io.jac = st.out(io.jac, (size_t)ASCENT_HISTORY_QUANTITIES * ASCENT_LINCOV_COLS * NJ * B);
@@ -1096,6 +1121,39 @@ int ascent_covariance_history_batch(const ascent_params *p, int64_t batch, const
   io.ff_u = ff_u; io.ff_t = ff_t; io.ff_know = ff_know; io.sigma_nav = sigma_nav;
   io.node_stride = node_stride; io.nominal = nominal_out; io.cov = cov_out; io.jac = jac_hist_out;
   return lincov_call(p, batch, o, substeps, io, device_id, stream_, ptr_is_device);
+}
+
+int ascent_disperse_drifting_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                                   int32_t samples, const double *xi, const double *sigma, const double *sigma_u, const double *gain_u,
+                                   const double *gain_t, const double *stretch_max, const double *ff_u, const double *ff_t,
+                                   const double *ff_know, const double *xi_nav, const double *sigma_nav, const double *nav_phi,
+                                   const double *nav_q, const double *xi_drift, int32_t node_stride, double *stats_out,
+                                   double *samples_out, double *hist_out, double *hist_samples_out, int device_id, void *stream_,
+                                   int ptr_is_device) {
+  DisperseIO io{};
+  io.blob = sol_blob; io.xi = xi; io.sigma = sigma; io.sigma_u = sigma_u;
+  io.gain_u = gain_u; io.gain_t = gain_t; io.stretch_max = stretch_max;
+  io.ff_u = ff_u; io.ff_t = ff_t; io.ff_know = ff_know; io.xi_nav = xi_nav; io.sigma_nav = sigma_nav;
+  io.nav_phi = nav_phi; io.nav_q = nav_q; io.xi_drift = xi_drift;
+  io.stats = stats_out; io.samples_out = samples_out;
+  io.node_stride = node_stride; io.hist = hist_out; io.hist_samples = hist_samples_out;
+  return disperse_call(p, batch, o, substeps, samples, gain_u ? DISPERSE_NAVIGATED : DISPERSE_OPEN, io, device_id, stream_, ptr_is_device, true,
+                       true);
+}
+
+int ascent_covariance_drifting_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                                     const double *sigma, const double *sigma_u, const double *gain_u, const double *gain_t,
+                                     const double *stretch_max, const double *ff_u, const double *ff_t, const double *ff_know,
+                                     const double *sigma_nav, const double *nav_phi, const double *nav_q, int32_t node_stride,
+                                     double *nominal_out, double *cov_out, double *jac_hist_out, int device_id, void *stream_,
+                                     int ptr_is_device) {
+  LincovIO io{};
+  io.blob = sol_blob; io.sigma = sigma; io.sigma_u = sigma_u;
+  io.gain_u = gain_u; io.gain_t = gain_t; io.stretch_max = stretch_max;
+  io.ff_u = ff_u; io.ff_t = ff_t; io.ff_know = ff_know; io.sigma_nav = sigma_nav;
+  io.nav_phi = nav_phi; io.nav_q = nav_q;
+  io.node_stride = node_stride; io.nominal = nominal_out; io.cov = cov_out; io.jac = jac_hist_out;
+  return lincov_call(p, batch, o, substeps, io, device_id, stream_, ptr_is_device, true);
 }
 
 int ascent_kkt_step(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,

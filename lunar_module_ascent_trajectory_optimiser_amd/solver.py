@@ -156,6 +156,9 @@ class DispersionResult:
     effort: np.ndarray | None = None    # (batch, samples, 3) guided flights with keep_samples: EFFORT_ROWS
     xi_nav: np.ndarray | None = None    # (8, samples) the navigation draws (ascent_disperse_navigated_batch), shared by every problem
     nav_sigma: np.ndarray | None = None     # (batch, 8): 7 state-knowledge biases (scaled units), the error of theta-hat
+    xi_drift: np.ndarray | None = None      # (8, K, samples) the driving draws of the drifting knowledge errors (nav_tau, knowledge_tau)
+    nav_phi: np.ndarray | None = None       # (batch, 8) their per-step decay exp(-dt / tau); 1 where frozen
+    nav_q: np.ndarray | None = None         # (batch, 8) their per-step drive steady * sqrt(1 - phi^2); 0 where frozen
     history: "DispersionHistory | None" = None      # disperse_batch(history=...): the statistics at the nodes on the way
 
     @property
@@ -573,6 +576,34 @@ def _nav_sigma_rows(nav_sigma, knowledge_sigma, B):
     return np.concatenate([_sigma_rows(nav_sigma, 7, B, "nav_sigma"), ks], axis=1)
 
 
+def _nav_drift(nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma, nav_s, dt, B):
+    """phi and q (B, 8) of the drifting knowledge channels (include/ascent.h: ascent_disperse_drifting_batch), or (None, None)
+    where no time constant is given: phi = exp(-dt / tau), q = steady * sqrt(1 - phi^2), per problem with its own step dt (B,)
+    in seconds.  tau None or inf, or a dt that is not finite: frozen, exactly (1, 0).  steady None: the channel's initial sigma of nav_s (B, 8) -- stationary."""
+    if nav_tau is None and knowledge_tau is None:
+        if nav_steady_sigma is not None or knowledge_steady_sigma is not None:
+            raise ValueError("nav_steady_sigma and knowledge_steady_sigma need nav_tau or knowledge_tau")
+        return None, None
+    tau = np.concatenate([_sigma_rows(np.inf if nav_tau is None else nav_tau, 7, B, "nav_tau"),
+                          _sigma_rows(np.asarray(np.inf if knowledge_tau is None else knowledge_tau, dtype=np.float64)[..., None], 1, B,
+                                      "knowledge_tau")], axis=1)
+    if not np.all(tau > 0):
+        raise ValueError("nav_tau and knowledge_tau must be positive (inf or None: frozen)")
+    steady = np.zeros((B, 8)) if nav_s is None else nav_s.copy()
+    if nav_steady_sigma is not None:
+        steady[:, :7] = _sigma_rows(nav_steady_sigma, 7, B, "nav_steady_sigma")
+    if knowledge_steady_sigma is not None:
+        steady[:, 7:] = _sigma_rows(np.asarray(knowledge_steady_sigma, dtype=np.float64)[..., None], 1, B, "knowledge_steady_sigma")
+    if not np.all(steady >= 0):
+        raise ValueError("nav_steady_sigma and knowledge_steady_sigma must not be negative")
+    dt = np.broadcast_to(np.asarray(dt, dtype=np.float64)[:, None], tau.shape)
+    frozen = np.isinf(tau) | ~(np.isfinite(dt) & (dt >= 0))      # a blob without a final time: frozen; the kernels treat that problem as the parent calls do
+    with np.errstate(divide="ignore", over="ignore"):
+        phi = np.where(frozen, 1.0, np.exp(-np.where(frozen, 0.0, dt) / np.where(frozen, 1.0, tau)))
+    q = np.where(frozen, 0.0, steady * np.sqrt(1.0 - phi * phi))
+    return np.ascontiguousarray(phi), np.ascontiguousarray(q)
+
+
 LINCOV_COLS = tuple(f"z0_{n}" for n in HISTORY_ROWS[:7]) + PARAM_FIELDS + ("tf",) + tuple(f"nav_{n}" for n in HISTORY_ROWS[:7]) + (
     "knowledge",)
 
@@ -596,13 +627,17 @@ class LinearCorridor:
 def linear_corridor(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, control_sigma=None, tf_sigma=None, z0_sigma=None,
                     guidance: GuidanceResult | None = None, nav_sigma=None, knowledge_sigma=None, history=True,
                     want_jacobian: bool = True, scheme=0, formulation=0, terminal=0, move_penalty: bool = False, substeps: int = 0,
-                    device: int = 0) -> LinearCorridor:
+                    device: int = 0, nav_tau=None, knowledge_tau=None, nav_steady_sigma=None,
+                    knowledge_steady_sigma=None) -> LinearCorridor:
     """Linear covariance analysis (include/ascent.h: ascent_covariance_history_batch): the flight disperse_batch(history=...)
     samples, linearised about the nominal flight and swept forward once per problem -- clips ignored, the execution errors of
     control_sigma independent white noise.  The sigmas broadcast as disperse_batch's and `guidance` is taken as there: None the
     open loop, a GuidanceResult the guided flight, with its feed-forward where it carries one; nav_sigma and knowledge_sigma
     need guidance.  history: True, or a node stride in 1 .. K.  Returns a LinearCorridor; jacobian None unless want_jacobian.
-    terminal 2 is accepted."""
+    terminal 2 is accepted.
+    nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma: the time-varying navigation error of disperse_batch, taken
+    as there (include/ascent.h: ascent_covariance_drifting_batch); the nav columns of the jacobian stay the derivative with
+    respect to the initial errors.  Without them the call is ascent_covariance_history_batch, exactly as before."""
     L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     stride = 1 if history is True else int(history) if history is not False and history is not None else 0
     if not 1 <= stride <= K:
@@ -610,19 +645,32 @@ def linear_corridor(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, 
     _, _, _, _, sig, sig_u = _dispersion_sigmas(z0_sigma, param_sigma, tf_sigma, control_sigma, K, B)
     if guidance is None and (nav_sigma is not None or knowledge_sigma is not None):
         raise ValueError("nav_sigma and knowledge_sigma need guidance")
-    gu = gt = sm = fu = ft = fk = sn = None
+    drifting = any(v is not None for v in (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma))
+    if guidance is None and drifting:
+        raise ValueError("nav_tau, knowledge_tau, nav_steady_sigma and knowledge_steady_sigma need guidance")
+    gu = gt = sm = fu = ft = fk = sn = phi = q = None
     if guidance is not None:
         gu, gt, sm = _feedback_arrays(guidance, K, B)
         fu, ft, fk = _feedforward_arrays(guidance, K, B)
+        nav_s = None
         if nav_sigma is not None or knowledge_sigma is not None:
-            sn = np.ascontiguousarray(_nav_sigma_rows(nav_sigma, knowledge_sigma, B).T)
+            nav_s = _nav_sigma_rows(nav_sigma, knowledge_sigma, B)
+            sn = np.ascontiguousarray(nav_s.T)
+        if drifting:
+            phi, q = _nav_drift(nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma, nav_s, blob[21 * K] * P[:, 11] / K, B)
     nodes = history_nodes(K, stride)
     NJ = len(nodes)
     nom, cov = np.empty((10, NJ, B)), np.empty((55, NJ, B))
     jac = np.empty((10, len(LINCOV_COLS), NJ, B)) if want_jacobian else None
-    _lib.check(L.ascent_covariance_history_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(sig), _ptr(sig_u), _ptr(gu),
-                                                 _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(sn), stride, _ptr(nom), _ptr(cov),
-                                                 _ptr(jac), device, None, 0))
+    if phi is not None:
+        phi_c, q_c = np.ascontiguousarray(phi.T), np.ascontiguousarray(q.T)
+        _lib.check(L.ascent_covariance_drifting_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(sig), _ptr(sig_u), _ptr(gu),
+                                                      _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(sn), _ptr(phi_c), _ptr(q_c),
+                                                      stride, _ptr(nom), _ptr(cov), _ptr(jac), device, None, 0))
+    else:
+        _lib.check(L.ascent_covariance_history_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(sig), _ptr(sig_u), _ptr(gu),
+                                                     _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(sn), stride, _ptr(nom), _ptr(cov),
+                                                     _ptr(jac), device, None, 0))
     full = np.empty((B, NJ, 10, 10))
     iu = np.triu_indices(10)
     full[:, :, iu[0], iu[1]] = cov.transpose(2, 1, 0)
@@ -635,7 +683,8 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
                    samples: int = 256, seed: int = 0, xi=None, keep_samples: bool = False, scheme=0, formulation=0, terminal=0,
                    move_penalty: bool = False, substeps: int = 0, device: int = 0, guidance: GuidanceResult | None = None,
                    nav_sigma=None, knowledge_sigma=None, xi_nav=None, nav_seed: int = 1, history=False,
-                   keep_history_samples: bool = False) -> DispersionResult:
+                   keep_history_samples: bool = False, nav_tau=None, knowledge_tau=None, nav_steady_sigma=None,
+                   knowledge_steady_sigma=None, xi_drift=None, drift_seed: int = 2) -> DispersionResult:
     """Monte Carlo dispersion (include/ascent.h: ascent_disperse_batch): every blob's control flown `samples` times on the
     device as fly_batch flies it, with the initial state, the 16 parameter fields, t_f and every control perturbed by
     sigma * xi, and the nine end quantities reduced on the device to count, mean, covariance and extrema.  The blob is shared
@@ -654,7 +703,15 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     history: True, or a node stride in 1 .. K: the same flight through ascent_disperse_history_batch, and `history` of the result a
     DispersionHistory of every stride-th node and the last; everything else of the result has the bits of the call without it.
     keep_history_samples: also every sample's ten quantities at those nodes (the one array of size samples x K).  False: the
-    entry points above, exactly as without the keyword."""
+    entry points above, exactly as without the keyword.
+    Time-varying navigation error (include/ascent.h: ascent_disperse_drifting_batch; needs guidance): nav_tau, seconds, a scalar,
+    (7,) or (batch, 7), and knowledge_tau, a scalar or (batch,), make each knowledge error a first-order Gauss-Markov sequence with
+    that correlation time, phi = exp(-dt / tau) per step of dt = t_f T_scale / K seconds; None or inf: frozen, the bias per flight
+    of the navigated call.  nav_steady_sigma and knowledge_steady_sigma: the stationary 1-sigma the channel relaxes to, q = steady
+    sqrt(1 - phi^2); None: the channel's initial sigma (a stationary process), 0: pure decay.  xi_drift (8, K, samples): the
+    driving draws, None draws np.random.default_rng(drift_seed).standard_normal((8, K, samples)).  The result keeps xi_drift,
+    nav_phi and nav_q.  Without `history` the call runs with stride K and the result's history is None.  Without these keywords
+    the calls are exactly those above."""
     L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     stride = 0
     if history is not False and history is not None:
@@ -670,6 +727,18 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
         raise ValueError(f"xi must have shape (24 + K, samples) = ({24 + K}, samples)")
     S = xi.shape[1]
     zs, ps, ts, us, sig, sig_u = _dispersion_sigmas(z0_sigma, param_sigma, tf_sigma, control_sigma, K, B)
+    ffu = getattr(guidance, "ff_u", None)
+    navigated = ffu is not None or nav_sigma is not None or knowledge_sigma is not None
+    if navigated and guidance is None:
+        raise ValueError("nav_sigma and knowledge_sigma need guidance")
+    nav_s = None
+    drifting = any(v is not None for v in (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma, xi_drift))
+    if drifting:
+        if guidance is None:
+            raise ValueError("nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma and xi_drift need guidance")
+        return _disperse_drifting(L, P, B, K, blob, o, int(substeps), device, xi, (zs, ps, ts, us, sig, sig_u), guidance, nav_sigma,
+                                  knowledge_sigma, xi_nav, nav_seed, nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma,
+                                  xi_drift, drift_seed, stride, keep_samples, keep_history_samples)
     stats = np.empty((82, B))
     smp = np.empty((9 if guidance is None and not stride else 12, S, B)) if keep_samples else None
     hist = hsmp = None
@@ -682,11 +751,6 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
         _lib.check(L.ascent_disperse_history_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
                                                    *[_ptr(x) for x in a], stride, _ptr(stats), _ptr(smp), _ptr(hist), _ptr(hsmp),
                                                    device, None, 0))
-    ffu = getattr(guidance, "ff_u", None)
-    navigated = ffu is not None or nav_sigma is not None or knowledge_sigma is not None
-    if navigated and guidance is None:
-        raise ValueError("nav_sigma and knowledge_sigma need guidance")
-    nav_s = None
     if guidance is None and stride:
         with_history(*[None] * 8)
     elif guidance is None:
@@ -719,18 +783,68 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
                                                              _ptr(gu), _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(xi_nav), _ptr(sn),
                                                              _ptr(stats), _ptr(smp), device, None, 0))
     st = stats.T
-    hres = None
-    if stride:
-        h = hist.transpose(2, 1, 0)      # (batch, NJ, 52)
-        hres = DispersionHistory(history_nodes(K, stride), h[:, :, 0].astype(np.int64), np.ascontiguousarray(h[:, :, 1:11]),
-                                 np.ascontiguousarray(h[:, :, 11:21]), np.ascontiguousarray(h[:, :, 21:31]),
-                                 np.ascontiguousarray(h[:, :, 31:41]), np.ascontiguousarray(h[:, :, 41:51]), h[:, :, 51].astype(np.int64),
-                                 None if hsmp is None else np.ascontiguousarray(hsmp.transpose(3, 2, 1, 0)))
+    hres = _history_result(K, stride, hist, hsmp) if stride else None
     return DispersionResult(st[:, 0].astype(np.int64), np.ascontiguousarray(st[:, 1:10]), np.ascontiguousarray(st[:, 10:19]),
                             _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
                             None if smp is None else np.ascontiguousarray(smp[:9].transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us,
                             None if smp is None or guidance is None else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)),
-                            xi_nav if nav_s is not None else None, nav_s, hres)
+                            xi_nav if nav_s is not None else None, nav_s, history=hres)
+
+
+def _history_result(K, stride, hist, hsmp):
+    """DispersionHistory from hist_out [52][NJ][batch] and hist_samples_out [10][NJ][samples][batch] or None"""
+    h = hist.transpose(2, 1, 0)      # (batch, NJ, 52)
+    return DispersionHistory(history_nodes(K, stride), h[:, :, 0].astype(np.int64), np.ascontiguousarray(h[:, :, 1:11]),
+                             np.ascontiguousarray(h[:, :, 11:21]), np.ascontiguousarray(h[:, :, 21:31]),
+                             np.ascontiguousarray(h[:, :, 31:41]), np.ascontiguousarray(h[:, :, 41:51]), h[:, :, 51].astype(np.int64),
+                             None if hsmp is None else np.ascontiguousarray(hsmp.transpose(3, 2, 1, 0)))
+
+
+def _disperse_drifting(L, P, B, K, blob, o, substeps, device, xi, sigmas, guidance, nav_sigma, knowledge_sigma, xi_nav, nav_seed, nav_tau,
+                       knowledge_tau, nav_steady_sigma, knowledge_steady_sigma, xi_drift, drift_seed, stride, keep_samples,
+                       keep_history_samples):
+    """disperse_batch with the time-varying navigation error: one call of ascent_disperse_drifting_batch"""
+    zs, ps, ts, us, sig, sig_u = sigmas
+    S = xi.shape[1]
+    gu, gt, sm = _feedback_arrays(guidance, K, B)
+    fu, ft, fk = _feedforward_arrays(guidance, K, B)
+    nav_s = sn = None
+    if nav_sigma is not None or knowledge_sigma is not None:
+        nav_s = _nav_sigma_rows(nav_sigma, knowledge_sigma, B)
+        sn = np.ascontiguousarray(nav_s.T)
+        if xi_nav is None:
+            xi_nav = np.random.default_rng(nav_seed).standard_normal((8, S))
+        xi_nav = np.ascontiguousarray(xi_nav, dtype=np.float64)
+        if xi_nav.shape != (8, S):
+            raise ValueError(f"xi_nav must have shape (8, samples) = {(8, S)}")
+    else:
+        xi_nav = None
+    phi, q = _nav_drift(nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma, nav_s, blob[21 * K] * P[:, 11] / K, B)
+    if phi is None:
+        raise ValueError("xi_drift needs nav_tau or knowledge_tau")
+    if xi_drift is None:
+        xi_drift = np.random.default_rng(drift_seed).standard_normal((8, K, S))
+    xi_drift = np.ascontiguousarray(xi_drift, dtype=np.float64)
+    if xi_drift.shape != (8, K, S):
+        raise ValueError(f"xi_drift must have shape (8, K, samples) = {(8, K, S)}")
+    call_stride = stride if stride else K
+    NJ = len(history_nodes(K, call_stride))
+    stats = np.empty((82, B))
+    smp = np.empty((12, S, B)) if keep_samples else None
+    hist = np.empty((52, NJ, B))
+    hsmp = np.empty((10, NJ, S, B)) if keep_history_samples else None
+    phi_c, q_c = np.ascontiguousarray(phi.T), np.ascontiguousarray(q.T)
+    _lib.check(L.ascent_disperse_drifting_batch(_ptr(P), B, C.byref(o), _ptr(blob), substeps, S, _ptr(xi), _ptr(sig), _ptr(sig_u), _ptr(gu),
+                                                _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(xi_nav), _ptr(sn), _ptr(phi_c),
+                                                _ptr(q_c), _ptr(xi_drift), call_stride, _ptr(stats), _ptr(smp), _ptr(hist), _ptr(hsmp),
+                                                device, None, 0))
+    st = stats.T
+    return DispersionResult(st[:, 0].astype(np.int64), np.ascontiguousarray(st[:, 1:10]), np.ascontiguousarray(st[:, 10:19]),
+                            _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
+                            None if smp is None else np.ascontiguousarray(smp[:9].transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us,
+                            None if smp is None else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)),
+                            xi_nav if nav_s is not None else None, nav_s, xi_drift, phi, q,
+                            history=_history_result(K, stride, hist, hsmp) if stride else None)
 
 
 def guidance_gains(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,
