@@ -678,6 +678,8 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
     state = (int)sc[X_STATE];
     if (__any(state == ST_FACTOR)) {
       const bool act = state == ST_FACTOR;
+      const int roleB = phase_local(role), grpB = phase_local(grp);      // the factor phase's lane constants: derived here, not round-loop invariants
+      const int cbaseB = WIDE ? 0 : grpB * 16;
       const Scal s = lds_scal(sc, X_S);
       const double mu = sc[X_MU], dw = sc[X_DW];
       const double *it = w + (size_t)((int)sc[X_CUR] * NIT) * Kp;
@@ -695,27 +697,27 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
         ASC_UNROLL
         for (int i = 0; i < NS; i++) {
           int row = S_H; double sgn = 0.0;
-          if (role < 7) {
+          if (roleB < 7) {
             ASC_UNROLL
             for (int c = 0; c < 7; c++)
-              if (c == role && hmap[i] >= 0 && hmap[c] >= 0) { row = S_H + hrow[hmap[i]][hmap[c]]; sgn = 1.0; }
-          } else if (MP && role == 7) { if (i == 7) { row = S_SC; sgn = 1.0; } }
-          else if (role == RL) { row = S_RZ + i; sgn = -1.0; }
-          else if (role == RL + 1) { row = S_GT + i; sgn = -1.0; }
+              if (c == roleB && hmap[i] >= 0 && hmap[c] >= 0) { row = S_H + hrow[hmap[i]][hmap[c]]; sgn = 1.0; }
+          } else if (MP && roleB == 7) { if (i == 7) { row = S_SC; sgn = 1.0; } }
+          else if (roleB == RL) { row = S_RZ + i; sgn = -1.0; }
+          else if (roleB == RL + 1) { row = S_GT + i; sgn = -1.0; }
           grow[i] = row * LDW;
           gsgn[i] = sgn;
         }
       }
-      const double bsc = role == RL ? -mu : 0.0;
-      const int rowA = (role < 8 ? S_G + role : role < 12 ? S_E + role - 8
-                        : MP ? (role == 12 ? S_SC + 1 : role == 13 ? S_SC + 2 : S_SC)
-                        : (role == 12 ? S_SC : role == 13 ? S_SC + 1 : role == 14 ? S_SC + 4 : S_SC + 2)) * LDW;
-      const int rowB = (role < 7 ? S_C + role
-                        : MP ? (role < 13 ? S_F + role - 7 : role == 15 ? S_C + 7 : S_SC)
-                        : (role < 14 ? S_F + role - 7 : role == 14 ? S_SC + 3 : S_SC)) * LDW;
-      const int rowK = (role < NS + 3 ? role : NS + 3) * LDW;      // out rows 0 .. NS-1 kap, NS .. NS+2 k0, NS+3 dummy / pivot
-      const bool colr = role < NS;
-      const int drow = role == RL ? 0 : role == RL + 1 ? 1 : 2;           // what a lane subtracts after the pivot: P c, P rc or nothing
+      const double bsc = roleB == RL ? -mu : 0.0;
+      const int rowA = (roleB < 8 ? S_G + roleB : roleB < 12 ? S_E + roleB - 8
+                        : MP ? (roleB == 12 ? S_SC + 1 : roleB == 13 ? S_SC + 2 : S_SC)
+                        : (roleB == 12 ? S_SC : roleB == 13 ? S_SC + 1 : roleB == 14 ? S_SC + 4 : S_SC + 2)) * LDW;
+      const int rowB = (roleB < 7 ? S_C + roleB
+                        : MP ? (roleB < 13 ? S_F + roleB - 7 : roleB == 15 ? S_C + 7 : S_SC)
+                        : (roleB < 14 ? S_F + roleB - 7 : roleB == 14 ? S_SC + 3 : S_SC)) * LDW;
+      const int rowK = (roleB < NS + 3 ? roleB : NS + 3) * LDW;      // out rows 0 .. NS-1 kap, NS .. NS+2 k0, NS+3 dummy / pivot
+      const bool colr = roleB < NS;
+      const int drow = roleB == RL ? 0 : roleB == RL + 1 ? 1 : 2;           // what a lane subtracts after the pivot: P c, P rc or nothing
       double a[NS];
       ASC_UNROLL
       for (int i = 0; i < NS; i++) a[i] = 0.0;
@@ -743,11 +745,12 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
         for (int i = 0; i < 7; i++) {
           double v = 0.0;
           ASC_UNROLL
-          for (int c = 0; c < 7; c++) v = role == c ? Qt[sid(i, c)] : v;
-          if (i < 4) { v = role == RL ? -r0[i] : v; v = role == RL + 2 ? -tm.e3g[i] : v; }
+          for (int c = 0; c < 7; c++) v = roleB == c ? Qt[sid(i, c)] : v;
+          if (i < 4) { v = roleB == RL ? -r0[i] : v; v = roleB == RL + 2 ? -tm.e3g[i] : v; }
           a[i] = v;
         }
       }
+      const bool any_dw = __builtin_amdgcn_ballot_w64(dw != 0.0) != 0;      // wavefront-uniform (a scalar): is any NLP of the wavefront regularised
       const bool probe_rows = sc[X_PROBE] == 2.0;      // parity probe of the node evaluation: dump the stage rows, no sweep
       for (int c = nch - 1; c >= 0; c--) {
         // ---- node-parallel: the blocks of the 16 nodes of this chunk -------------------------------------------------
@@ -827,7 +830,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
           for (int jj = CHN - 1; jj >= 0; jj--) {
             const int k = c * CHN + jj;
             if (k >= K) continue;
-            const int cj = cbase + jj;
+            const int cj = cbaseB + jj;
             double gq[NS];
             ASC_UNROLL
             for (int i = 0; i < NS; i++) gq[i] = stage[grow[i] + cj];
@@ -843,7 +846,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
                                    bcast16<12>(gB), MP ? hT * d.mrate : bcast16<13>(gB)};
             if (FORM == 1 && k < K - 1) {     // step k+1 does not see angle_k: drop its row and column
               a[IA] = 0.0;
-              if (role == IA) {
+              if (roleB == IA) {
                 ASC_UNROLL
                 for (int i = 0; i < NS; i++) a[i] = 0.0;
               }
@@ -855,11 +858,11 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
               for (int i = 0; i < 7; i++) a[i] += cs * t[i];
               if (colr) {
                 ASC_UNROLL
-                for (int i = 0; i < NS; i++) lds_t[grp][role][i] = a[i];
+                for (int i = 0; i < NS; i++) lds_t[grpB][roleB][i] = a[i];
                 wsync();
                 double r[NS];
                 ASC_UNROLL
-                for (int l2 = 0; l2 < NS; l2++) r[l2] = lds_t[grp][l2][role];
+                for (int l2 = 0; l2 < NS; l2++) r[l2] = lds_t[grpB][l2][roleB];
                 fzt_lambda(G, r, t);
                 ASC_UNROLL
                 for (int i = 0; i < 7; i++) a[i] = r[i] + cs * t[i];
@@ -873,9 +876,11 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
               a[IA] += bsc * bza;
               a[IM] += bsc * bzm;
             }
-            if (dw != 0.0) {
-              ASC_UNROLL
-              for (int i = 0; i < NS; i++) a[i] += role == i ? dw : 0.0;
+            if (__builtin_expect(any_dw, 0)) {
+              if (dw != 0.0) {
+                ASC_UNROLL
+                for (int i = 0; i < NS; i++) a[i] += roleB == i ? dw : 0.0;
+              }
             }
             // (MP: the extended step Jacobian is [[A, -bu e_b], [0, 1]], b the defect row the control enters: its inverse transpose acts as
             //  A^-T on the states and adds bu times that row's component to the control's entry)
@@ -884,11 +889,11 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             if constexpr (MP) b[7] = a[7] + bu * b[IB];
             if (colr) {       // N <- A^-T N A^-1: the columns, transposed through LDS (in order within a wavefront), the columns again
               ASC_UNROLL
-              for (int i = 0; i < NS; i++) lds_t[grp][role][i] = b[i];
+              for (int i = 0; i < NS; i++) lds_t[grpB][roleB][i] = b[i];
               wsync();
               double t[NS];
               ASC_UNROLL
-              for (int l2 = 0; l2 < NS; l2++) t[l2] = lds_t[grp][l2][role];
+              for (int l2 = 0; l2 < NS; l2++) t[l2] = lds_t[grpB][l2][roleB];
               solveAT<FORM>(G, E, cs, t, b);
               if constexpr (MP) b[7] = t[7] + bu * b[IB];
             }
@@ -904,16 +909,16 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             }
             const double iD = rcp(D);
             if constexpr (MP) {
-              const double rsel = role == RL ? ru0 : 0.0;
+              const double rsel = roleB == RL ? ru0 : 0.0;
               coef = (b[7] - rsel) * iD;
             } else {
               const double ru = ru0 + mu * bur, gu = FORM == 1 ? 0.0 : ru0 * ith;
-              const double rsel = role == 7 ? ru : role == 8 ? gu : 0.0;
+              const double rsel = roleB == 7 ? ru : roleB == 8 ? gu : 0.0;
               coef = (bu * b[IB] - rsel) * iD;
             }
             ASC_UNROLL
             for (int i = 0; i < NS; i++) a[i] = b[i] - mw[i] * coef;
-            outb[rowK + cj] = role < NS + 3 ? coef : D;      // rows 0 .. NS-1 kap, NS .. NS+2 k0, NS+3: the pivot (for the flush below)
+            outb[rowK + cj] = roleB < NS + 3 ? coef : D;      // rows 0 .. NS-1 kap, NS .. NS+2 k0, NS+3: the pivot (for the flush below)
             if (colr) {
               double d0 = 0.0, d1 = 0.0;
               ASC_UNROLL
@@ -921,14 +926,14 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
                 d0 -= a[i] * cc[i];
                 if (i < 7) d1 += a[i] * rc1[i];
               }
-              lds_d[grp][0][role] = d0;
-              lds_d[grp][1][role] = d1;
+              lds_d[grpB][0][roleB] = d0;
+              lds_d[grpB][1][roleB] = d1;
             }
             wsync();
             {     // right-hand-side lanes: a <- a - P c (the column lanes read zeros and keep their a; their U, V are never used)
               double prc[NS];
               ASC_UNROLL
-              for (int i = 0; i < NS; i++) prc[i] = lds_d[grp][drow][i];
+              for (int i = 0; i < NS; i++) prc[i] = lds_d[grpB][drow][i];
               double uu = 0.0, vv = 0.0;
               ASC_UNROLL
               for (int i = 0; i < NS; i++) {

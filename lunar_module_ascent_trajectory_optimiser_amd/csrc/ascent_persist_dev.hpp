@@ -78,6 +78,14 @@ struct OneHot {
     return r;
   }
 };
+// A phase's own copy of a lane constant (role, grp, ...).  p_solve derives LDS addresses, row selections and masks from the lane's index;
+// derived from the kernel's copy they are invariants of the round loop: the compiler computes them once, parks them in AGPRs or scratch
+// for the whole kernel and fetches them back inside every serial step.  The empty asm makes the copy opaque, so that what a phase derives
+// from it is computed at the top of that phase and lives in VGPRs for that phase alone.  The value is unchanged.  DESIGN.md 4a-live.
+ASC_DEV int phase_local(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
 ASC_DEV void wsync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
