@@ -604,6 +604,40 @@ def _nav_drift(nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma,
     return np.ascontiguousarray(phi), np.ascontiguousarray(q)
 
 
+def _guidance_arrays(P, blob, K, B, guidance, nav_sigma, knowledge_sigma, drift=(None,) * 4, S=None, xi_nav=None, nav_seed=1):
+    """A guidance law and its navigation error as the C ABI takes them, None where there is none: law = [gain_u, gain_t,
+    stretch_max, ff_u, ff_t, ff_know], sigma_nav [8][B] beside nav_s (B, 8), and phi and q (B, 8) of the time constants drift =
+    (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma) (_nav_drift).  S: the samples of a Monte Carlo call, which
+    takes xi_nav (8, S) with a navigation error -- None draws np.random.default_rng(nav_seed) -- and None without one."""
+    law = [*_feedback_arrays(guidance, K, B), *_feedforward_arrays(guidance, K, B)]
+    nav_s = sn = None
+    if nav_sigma is not None or knowledge_sigma is not None:
+        nav_s = _nav_sigma_rows(nav_sigma, knowledge_sigma, B)
+        sn = np.ascontiguousarray(nav_s.T)
+        if S is not None:
+            if xi_nav is None:
+                xi_nav = np.random.default_rng(nav_seed).standard_normal((8, S))
+            xi_nav = np.ascontiguousarray(xi_nav, dtype=np.float64)
+            if xi_nav.shape != (8, S):
+                raise ValueError(f"xi_nav must have shape (8, samples) = {(8, S)}")
+    else:
+        xi_nav = None
+    phi = q = None
+    if any(v is not None for v in drift):
+        phi, q = _nav_drift(*drift, nav_s, blob[21 * K] * P[:, 11] / K, B)
+    return law, sn, nav_s, xi_nav, phi, q
+
+
+def _dispersion_result(stats, smp, effort, xi, sigmas, xi_nav, nav_s, *drift, history=None):
+    """DispersionResult from stats_out [82][batch] and samples_out [9 or 12][samples][batch] or None; effort: rows 9.. are EFFORT_ROWS"""
+    st, (zs, ps, ts, us) = stats.T, sigmas[:4]
+    return DispersionResult(st[:, 0].astype(np.int64), np.ascontiguousarray(st[:, 1:10]), np.ascontiguousarray(st[:, 10:19]),
+                            _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
+                            None if smp is None else np.ascontiguousarray(smp[:9].transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us,
+                            None if smp is None or not effort else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)),
+                            xi_nav if nav_s is not None else None, nav_s, *drift, history=history)
+
+
 LINCOV_COLS = tuple(f"z0_{n}" for n in HISTORY_ROWS[:7]) + PARAM_FIELDS + ("tf",) + tuple(f"nav_{n}" for n in HISTORY_ROWS[:7]) + (
     "knowledge",)
 
@@ -648,29 +682,21 @@ def linear_corridor(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, 
     drifting = any(v is not None for v in (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma))
     if guidance is None and drifting:
         raise ValueError("nav_tau, knowledge_tau, nav_steady_sigma and knowledge_steady_sigma need guidance")
-    gu = gt = sm = fu = ft = fk = sn = phi = q = None
+    law, sn, phi, q = [None] * 6, None, None, None
     if guidance is not None:
-        gu, gt, sm = _feedback_arrays(guidance, K, B)
-        fu, ft, fk = _feedforward_arrays(guidance, K, B)
-        nav_s = None
-        if nav_sigma is not None or knowledge_sigma is not None:
-            nav_s = _nav_sigma_rows(nav_sigma, knowledge_sigma, B)
-            sn = np.ascontiguousarray(nav_s.T)
-        if drifting:
-            phi, q = _nav_drift(nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma, nav_s, blob[21 * K] * P[:, 11] / K, B)
+        law, sn, _, _, phi, q = _guidance_arrays(P, blob, K, B, guidance, nav_sigma, knowledge_sigma,
+                                                 (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma))
     nodes = history_nodes(K, stride)
     NJ = len(nodes)
     nom, cov = np.empty((10, NJ, B)), np.empty((55, NJ, B))
     jac = np.empty((10, len(LINCOV_COLS), NJ, B)) if want_jacobian else None
+    head = (_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(sig), _ptr(sig_u), *[_ptr(x) for x in law], _ptr(sn))
+    tail = (stride, _ptr(nom), _ptr(cov), _ptr(jac), device, None, 0)
     if phi is not None:
         phi_c, q_c = np.ascontiguousarray(phi.T), np.ascontiguousarray(q.T)
-        _lib.check(L.ascent_covariance_drifting_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(sig), _ptr(sig_u), _ptr(gu),
-                                                      _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(sn), _ptr(phi_c), _ptr(q_c),
-                                                      stride, _ptr(nom), _ptr(cov), _ptr(jac), device, None, 0))
+        _lib.check(L.ascent_covariance_drifting_batch(*head, _ptr(phi_c), _ptr(q_c), *tail))
     else:
-        _lib.check(L.ascent_covariance_history_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(sig), _ptr(sig_u), _ptr(gu),
-                                                     _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(sn), stride, _ptr(nom), _ptr(cov),
-                                                     _ptr(jac), device, None, 0))
+        _lib.check(L.ascent_covariance_history_batch(*head, *tail))
     full = np.empty((B, NJ, 10, 10))
     iu = np.triu_indices(10)
     full[:, :, iu[0], iu[1]] = cov.transpose(2, 1, 0)
@@ -732,11 +758,12 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     if navigated and guidance is None:
         raise ValueError("nav_sigma and knowledge_sigma need guidance")
     nav_s = None
+    sigmas = (zs, ps, ts, us, sig, sig_u)
     drifting = any(v is not None for v in (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma, xi_drift))
     if drifting:
         if guidance is None:
             raise ValueError("nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma and xi_drift need guidance")
-        return _disperse_drifting(L, P, B, K, blob, o, int(substeps), device, xi, (zs, ps, ts, us, sig, sig_u), guidance, nav_sigma,
+        return _disperse_drifting(L, P, B, K, blob, o, int(substeps), device, xi, sigmas, guidance, nav_sigma,
                                   knowledge_sigma, xi_nav, nav_seed, nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma,
                                   xi_drift, drift_seed, stride, keep_samples, keep_history_samples)
     stats = np.empty((82, B))
@@ -757,38 +784,19 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
         _lib.check(L.ascent_disperse_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
                                            _ptr(stats), _ptr(smp), device, None, 0))
     else:
-        gu, gt, sm = _feedback_arrays(guidance, K, B)
-        if not navigated and stride:
-            with_history(gu, gt, sm, None, None, None, None, None)
+        law, sn, nav_s, xi_nav, _, _ = _guidance_arrays(P, blob, K, B, guidance, nav_sigma, knowledge_sigma, S=S, xi_nav=xi_nav,
+                                                        nav_seed=nav_seed)
+        if stride:
+            with_history(*law, xi_nav, sn)
         elif not navigated:
             _lib.check(L.ascent_disperse_guided_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
-                                                      _ptr(gu), _ptr(gt), _ptr(sm), _ptr(stats), _ptr(smp), device, None, 0))
+                                                      *[_ptr(x) for x in law[:3]], _ptr(stats), _ptr(smp), device, None, 0))
         else:
-            fu, ft, fk = _feedforward_arrays(guidance, K, B)
-            sn = None
-            if nav_sigma is not None or knowledge_sigma is not None:
-                nav_s = _nav_sigma_rows(nav_sigma, knowledge_sigma, B)
-                sn = np.ascontiguousarray(nav_s.T)
-                if xi_nav is None:
-                    xi_nav = np.random.default_rng(nav_seed).standard_normal((8, S))
-                xi_nav = np.ascontiguousarray(xi_nav, dtype=np.float64)
-                if xi_nav.shape != (8, S):
-                    raise ValueError(f"xi_nav must have shape (8, samples) = {(8, S)}")
-            else:
-                xi_nav = None
-            if stride:
-                with_history(gu, gt, sm, fu, ft, fk, xi_nav, sn)
-            else:
-                _lib.check(L.ascent_disperse_navigated_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
-                                                             _ptr(gu), _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(xi_nav), _ptr(sn),
-                                                             _ptr(stats), _ptr(smp), device, None, 0))
-    st = stats.T
-    hres = _history_result(K, stride, hist, hsmp) if stride else None
-    return DispersionResult(st[:, 0].astype(np.int64), np.ascontiguousarray(st[:, 1:10]), np.ascontiguousarray(st[:, 10:19]),
-                            _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
-                            None if smp is None else np.ascontiguousarray(smp[:9].transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us,
-                            None if smp is None or guidance is None else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)),
-                            xi_nav if nav_s is not None else None, nav_s, history=hres)
+            _lib.check(L.ascent_disperse_navigated_batch(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), S, _ptr(xi), _ptr(sig), _ptr(sig_u),
+                                                         *[_ptr(x) for x in law], _ptr(xi_nav), _ptr(sn), _ptr(stats), _ptr(smp),
+                                                         device, None, 0))
+    return _dispersion_result(stats, smp, guidance is not None, xi, sigmas, xi_nav, nav_s,
+                              history=_history_result(K, stride, hist, hsmp) if stride else None)
 
 
 def _history_result(K, stride, hist, hsmp):
@@ -804,22 +812,10 @@ def _disperse_drifting(L, P, B, K, blob, o, substeps, device, xi, sigmas, guidan
                        knowledge_tau, nav_steady_sigma, knowledge_steady_sigma, xi_drift, drift_seed, stride, keep_samples,
                        keep_history_samples):
     """disperse_batch with the time-varying navigation error: one call of ascent_disperse_drifting_batch"""
-    zs, ps, ts, us, sig, sig_u = sigmas
+    sig, sig_u = sigmas[4:]
     S = xi.shape[1]
-    gu, gt, sm = _feedback_arrays(guidance, K, B)
-    fu, ft, fk = _feedforward_arrays(guidance, K, B)
-    nav_s = sn = None
-    if nav_sigma is not None or knowledge_sigma is not None:
-        nav_s = _nav_sigma_rows(nav_sigma, knowledge_sigma, B)
-        sn = np.ascontiguousarray(nav_s.T)
-        if xi_nav is None:
-            xi_nav = np.random.default_rng(nav_seed).standard_normal((8, S))
-        xi_nav = np.ascontiguousarray(xi_nav, dtype=np.float64)
-        if xi_nav.shape != (8, S):
-            raise ValueError(f"xi_nav must have shape (8, samples) = {(8, S)}")
-    else:
-        xi_nav = None
-    phi, q = _nav_drift(nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma, nav_s, blob[21 * K] * P[:, 11] / K, B)
+    law, sn, nav_s, xi_nav, phi, q = _guidance_arrays(P, blob, K, B, guidance, nav_sigma, knowledge_sigma,
+                                                      (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma), S, xi_nav, nav_seed)
     if phi is None:
         raise ValueError("xi_drift needs nav_tau or knowledge_tau")
     if xi_drift is None:
@@ -834,17 +830,11 @@ def _disperse_drifting(L, P, B, K, blob, o, substeps, device, xi, sigmas, guidan
     hist = np.empty((52, NJ, B))
     hsmp = np.empty((10, NJ, S, B)) if keep_history_samples else None
     phi_c, q_c = np.ascontiguousarray(phi.T), np.ascontiguousarray(q.T)
-    _lib.check(L.ascent_disperse_drifting_batch(_ptr(P), B, C.byref(o), _ptr(blob), substeps, S, _ptr(xi), _ptr(sig), _ptr(sig_u), _ptr(gu),
-                                                _ptr(gt), _ptr(sm), _ptr(fu), _ptr(ft), _ptr(fk), _ptr(xi_nav), _ptr(sn), _ptr(phi_c),
-                                                _ptr(q_c), _ptr(xi_drift), call_stride, _ptr(stats), _ptr(smp), _ptr(hist), _ptr(hsmp),
-                                                device, None, 0))
-    st = stats.T
-    return DispersionResult(st[:, 0].astype(np.int64), np.ascontiguousarray(st[:, 1:10]), np.ascontiguousarray(st[:, 10:19]),
-                            _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
-                            None if smp is None else np.ascontiguousarray(smp[:9].transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us,
-                            None if smp is None else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)),
-                            xi_nav if nav_s is not None else None, nav_s, xi_drift, phi, q,
-                            history=_history_result(K, stride, hist, hsmp) if stride else None)
+    _lib.check(L.ascent_disperse_drifting_batch(_ptr(P), B, C.byref(o), _ptr(blob), substeps, S, _ptr(xi), _ptr(sig), _ptr(sig_u),
+                                                *[_ptr(x) for x in law], _ptr(xi_nav), _ptr(sn), _ptr(phi_c), _ptr(q_c), _ptr(xi_drift),
+                                                call_stride, _ptr(stats), _ptr(smp), _ptr(hist), _ptr(hsmp), device, None, 0))
+    return _dispersion_result(stats, smp, True, xi, sigmas, xi_nav, nav_s, xi_drift, phi, q,
+                              history=_history_result(K, stride, hist, hsmp) if stride else None)
 
 
 def guidance_gains(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,

@@ -1,4 +1,4 @@
-"""Every output array of the nine calls on a solution blob, as raw bytes, for comparing two builds of the library bit for bit.
+"""Every output array of the thirteen calls on a solution blob, as raw bytes, for comparing two builds of the library bit for bit.
 
     python scripts/analysis_dump.py --out FILE.npz              (on the GPU, once in each tree)
     python scripts/analysis_dump.py --compare A.npz B.npz --json profiles/analysis_refactor_parity.json    (anywhere)
@@ -10,6 +10,11 @@ sensitivity, flight, flight Jacobian, trim, gains and feed-forward gains (thrust
 0 and 0.5), and the three dispersions at 70 samples (two wavefronts, the second partly filled) and 300 (two workgroups per
 problem), with and without control sigmas, feed-forward, knowledge row and navigation sigmas.  Output buffers start as 7.25, so
 an element a build does not write compares equal only if the other build does not write it either.
+
+The four corridor calls (corridors): the two covariance calls at strides 1, 4 and K, open loop | feedback only | feedback with
+feed-forward, ff_know and sigma_nav, stretch_max 0 and 0.5 (the stretched last step), sigma_u given and null, jac_hist_out given
+and null; the drifting one with nav_phi / nav_q null, all frozen and the channel mix of tests/test_gpu_navdrift.py, and through
+device pointers one problem with phi = 2.  The two Monte Carlo history calls run at 70 samples only, as the control.
 """
 from __future__ import annotations
 
@@ -26,6 +31,9 @@ sys.path.insert(0, ROOT)
 
 B = 5
 FILL = 7.25
+# the channel mix of tests/test_gpu_navdrift.py: stationary | decaying | frozen | zero-start random walk | phi = 0 | zero-start | frozen | stationary
+PHI = np.array([0.9, 0.5, 1.0, 1.0, 0.0, 0.97, 1.0, 0.7])
+DRIVE = np.array([np.sqrt(1 - 0.81), 0.0, 0.0, 0.3, 1.0, 0.2, 0.0, np.sqrt(1 - 0.49)])
 
 
 class Caller:
@@ -64,6 +72,48 @@ def out(*shape):
     return np.full(shape, FILL)
 
 
+def corridors(call, keep, po, sub, K, dev, gains, xi, xn, om, sigma, sigma_u, sigma_nav, ff_know):
+    """ascent_covariance_history_batch, ascent_covariance_drifting_batch and, at 70 samples, the two Monte Carlo history calls"""
+    S = xi.shape[1]
+    mix_phi, mix_q = np.ascontiguousarray(np.tile(PHI, (B, 1)).T), np.ascontiguousarray(sigma_nav * DRIVE[:, None])
+    drifts = {"null": (None, None), "frozen": (np.ones((8, B)), np.zeros((8, B))), "mix": (mix_phi, mix_q)}
+    if dev:                                                   # with host pointers a phi outside [0, 1] is refused
+        bad = mix_phi.copy()
+        bad[0, 1] = 2.0
+        drifts["phi2"] = (bad, mix_q)
+    laws = {"open": [None] * 7}
+    for smax in (0.0, 0.5):
+        gu, gt, fu, ft, sx = gains[smax]
+        laws[f"fb_s{smax}"] = [gu, gt, sx, None, None, None, None]
+        laws[f"ff_s{smax}"] = [gu, gt, sx, fu, ft, ff_know, sigma_nav]
+    for stride in (1, 4, K):
+        NJ = (K + stride - 1) // stride
+        for law, a in laws.items():
+            for su in (1, 0):
+                u = sigma_u if su else None
+                for jac_on in (1, 0):
+                    name = f"n{stride}_{law}_u{su}_j{jac_on}"
+                    nom, cov, jac = out(10, NJ, B), out(55, NJ, B), out(10, 32, NJ, B) if jac_on else None
+                    call("ascent_covariance_history_batch", *po, sub, sigma, u, *a, stride, nom, cov, jac)
+                    keep(f"lincov_{name}", nominal=nom, cov=cov, **({"jac": jac} if jac_on else {}))
+                    for dn, (ph, qq) in drifts.items() if law != "open" else ():
+                        nom, cov, jac = out(10, NJ, B), out(55, NJ, B), out(10, 32, NJ, B) if jac_on else None
+                        call("ascent_covariance_drifting_batch", *po, sub, sigma, u, *a, ph, qq, stride, nom, cov, jac)
+                        keep(f"lincov_drift_{dn}_{name}", nominal=nom, cov=cov, **({"jac": jac} if jac_on else {}))
+    for stride in (4, K):
+        NJ = (K + stride - 1) // stride
+        for law, a in laws.items():
+            mc = a[:6] + [xn if a[6] is not None else None, a[6]]
+            st, sp, hi, hs = out(82, B), out(12, S, B), out(52, NJ, B), out(10, NJ, S, B)
+            call("ascent_disperse_history_batch", *po, sub, S, xi, sigma, sigma_u, *mc, stride, st, sp, hi, hs)
+            keep(f"history_n{stride}_{law}", stats=st, samples=sp, hist=hi, hist_samples=hs)
+            for dn, (ph, qq) in drifts.items() if law != "open" else ():
+                st, sp, hi, hs = out(82, B), out(12, S, B), out(52, NJ, B), out(10, NJ, S, B)
+                call("ascent_disperse_drifting_batch", *po, sub, S, xi, sigma, sigma_u, *mc, ph, qq, om if ph is not None else None, stride,
+                     st, sp, hi, hs)
+                keep(f"history_drift_{dn}_n{stride}_{law}", stats=st, samples=sp, hist=hi, hist_samples=hs)
+
+
 def dump(path):
     import lunar_module_ascent_trajectory_optimiser_amd as A
     from lunar_module_ascent_trajectory_optimiser_amd import _lib
@@ -93,6 +143,7 @@ def dump(path):
             ff_know = ff_dir.copy()
             xis = {S: rng.standard_normal((24 + K, S)) for S in (70, 300)}
             xin = {S: rng.standard_normal((8, S)) for S in (70, 300)}
+            om = rng.standard_normal((8, K, 70))
             for sub in (0, 2):
                 for dev in (0, 1):
                     call = Caller(L, dev)
@@ -160,6 +211,7 @@ def dump(path):
                                 st = out(82, B)       # zero gains and nothing new: the guided and navigated kernels on the open-loop flight
                                 call("ascent_disperse_guided_batch", *po, sub, S, x, sigma, u, np.zeros((7, K, B)), None, None, st, None)
                                 keep(f"guided_zero_S{S}_u{su}_s{smax}", stats=st)
+                    corridors(call, keep, po, sub, K, dev, gains, xis[70], xin[70], om, sigma, sigma_u, sigma_nav, ff_know)
     np.savez_compressed(path, **res)
     print(f"{len(res)} arrays -> {path}")
 
@@ -170,9 +222,15 @@ def compare(a, b, json_path):
     rows = {n: ("equal" if n in x.files and n in y.files and x[n].shape == y[n].shape and np.array_equal(x[n], y[n], equal_nan=True) else "differ")
             for n in names}
     bad = [n for n, v in rows.items() if v != "equal"]
-    doc = {"_comment": "scripts/analysis_dump.py --compare: the uint64 views of every output array of the nine calls on a solution blob, "
-                       "the parent commit's library against this tree's, both run on the same MI355X",
-           "arrays": len(names), "differ": len(bad), "result": rows}
+    groups = {}                                               # per grid, formulation, substeps and pointer kind: arrays, of them differing
+    for n, v in rows.items():
+        g = groups.setdefault(n.split("/")[0], [0, 0])
+        g[0] += 1
+        g[1] += v != "equal"
+    doc = {"_comment": "scripts/analysis_dump.py --compare: the uint64 views of every output array of the thirteen calls on a solution blob, "
+                       "the parent commit's library against this tree's, both run on the same MI355X; per group [arrays, differing], "
+                       "and the names of the arrays that differ",
+           "arrays": len(names), "differ": len(bad), "groups": groups, "differing": bad}
     if json_path:
         with open(json_path, "w") as f:
             json.dump(doc, f, indent=1)
