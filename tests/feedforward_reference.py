@@ -8,13 +8,9 @@ flight_reference.rhs.  Nothing here comes from the kernels.  `dtype` switches a 
 longdouble, as in guidance_reference."""
 from __future__ import annotations
 
-import math
-
 import numpy as np
 
-import dispersion_reference as dr
 import flight_jacobian_reference as jr
-import flight_reference as fr
 import guidance_reference as gr
 
 NAV_ROWS = 8
@@ -131,69 +127,6 @@ def closed_loop_jacobian(rec, G, know, p16, formulation=0):
     return dict(jac=jac, jac_u=jac_u, jac_nav=jac_nav)
 
 
-def fly_navigated(p, z0, us, noise, tf, m, nodes, gain_u, gain_t, smax, ff_u, ff_t, theta_hat, nu, nu_on, formulation=0, dtype=np.float64):
-    """One navigated flight, arguments as guidance_reference.fly_guided plus ff_u (K,) or None, ff_t or None, theta_hat, nu (7,)
-    and nu_on (7,) bool: where the bias is applied.  -> (rows (9,), effort (4,): clipped steps, max |K . dz + f theta-hat|, stretch,
-    and the smallest distance of an unclipped command from the clip)"""
-    rhs = gr._rhs(dtype)
-    p = [float(v) for v in p] if dtype is np.float64 else np.asarray(p, dtype=np.float64).astype(dtype)
-    K = len(us)
-    z = np.array(z0, dtype=dtype)
-    th = dtype(theta_hat)
-    nclip, dmax, stretch, margin = 0.0, 0.0, 0.0, math.inf
-    with np.errstate(all="ignore"):
-        dt = (dtype(tf) * p[11]) / K
-        try:
-            for k in range(K):
-                dz = z - np.asarray(nodes[k], dtype=dtype)
-                for i in range(7):
-                    if nu_on[i]:
-                        dz[i] = dz[i] + dtype(nu[i])
-                kk = np.asarray(gain_u[k], dtype=dtype)
-                fk = dtype(0) if ff_u is None else dtype(ff_u[k])
-                uc = dtype(us[k])
-                if np.any(kk != 0) or fk != 0:
-                    dot = dtype(0)
-                    for i in range(7):
-                        dot = dot + kk[i] * dz[i]
-                    w = uc - dot
-                    if fk != 0:
-                        w = w - fk * th
-                        dot = dot + fk * th
-                    uc = min(dtype(1), max(dtype(-1), w)) if math.isfinite(dot) else dtype(np.nan)
-                    nclip += 1.0 if uc != w else 0.0
-                    margin = min(margin, abs(abs(float(w)) - 1.0)) if math.isfinite(w) else 0.0
-                    dmax = math.nan if (math.isnan(dot) or math.isnan(dmax)) else max(dmax, abs(float(dot)))
-                u = uc + dtype(noise[k]) if noise[k] != 0 else uc
-                h = dt / m
-                if k == K - 1 and gain_t is not None and smax > 0:
-                    dtau = dtype(0)
-                    for i in range(7):
-                        dtau = dtau - dtype(gain_t[i]) * dz[i]
-                    if ff_t is not None and ff_t != 0:
-                        dtau = dtau - dtype(ff_t) * th
-                    st = min(dtype(smax), max(dtype(-smax), dtau)) if math.isfinite(dtau) else dtype(np.nan)
-                    stretch = float(st)
-                    h = (dt * (1 + st)) / m
-                u = float(u) if dtype is np.float64 else u
-                if formulation == 1:
-                    z[4], z[5] = 0.5 * p[12] * (u + 1.0), 0.0
-                for _ in range(m):
-                    k1 = rhs(p, z, u, formulation)
-                    k2 = rhs(p, z + 0.5 * h * k1, u, formulation)
-                    k3 = rhs(p, z + 0.5 * h * k2, u, formulation)
-                    k4 = rhs(p, z + h * k3, u, formulation)
-                    z = z + h / 6.0 * (k1 + 2.0 * (k2 + k3) + k4)
-            if dtype is np.float64:
-                peri, apo = fr.apsides(p, *z[:4])
-            else:
-                pa, aa = jr.apsides(p[:, None], z[:, None])
-                peri, apo = pa[0], (aa[0] if np.isfinite(aa[0]) else np.inf)
-        except (ValueError, ZeroDivisionError, OverflowError):
-            return np.full(9, np.nan), np.array([nclip, dmax, stretch, margin])
-    return np.concatenate([z, [peri, apo]]).astype(dtype), np.array([nclip, dmax, stretch, margin])
-
-
 def beliefs(xi, sigma, know, xi_nav, sigma_nav):
     """-> (theta_hat (samples,), nu (samples, 7), nu_on (7,)) by the rules of the header: a draw counts where its sigma is non-zero"""
     xi, sigma = np.asarray(xi, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
@@ -218,29 +151,9 @@ def disperse_navigated(p16, blob, nt, xi, sigma, sigma_u, gain_u, gain_t=None, s
                        sigma_nav=None, formulation=0, substeps=0, dtype=np.float64):
     """-> dict(samples (samples, 9), effort (samples, 4), stats (82,), nominal (9,), m, nodes): guidance_reference.disperse_guided
     with the feed-forward and the navigation errors of ascent_disperse_navigated_batch"""
-    p16 = np.asarray(p16, dtype=np.float64)
-    K = nt - 1
-    _, us, tf = fr.blob_parts(np.asarray(blob, dtype=np.float64), nt)
-    xi, sigma = np.asarray(xi, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
-    m = fr.substeps_of((tf * p16[11]) / K, substeps)
-    S = xi.shape[1]
-    nodes = gr.nominal_nodes(p16, us, tf, m, formulation, dtype)
-    nominal, _ = gr.fly_guided(p16, np.zeros(7), us, np.zeros(K), tf, m, nodes, np.zeros((K, 7)), None, 0.0, formulation, dtype)
     th, nu, on = beliefs(xi, sigma, know, xi_nav, sigma_nav)
-    rows, eff = np.empty((S, 9), dtype=dtype), np.empty((S, 4))
-    noise = np.zeros((K, S))
-    if sigma_u is not None:
-        su = np.asarray(sigma_u, dtype=np.float64)
-        noise[su != 0.0] = su[su != 0.0, None] * xi[dr.NCOL:dr.NCOL + K][su != 0.0]
-    for s in range(S):
-        p, z0, _, t = dr.perturbed(p16, us, tf, xi, sigma, None, s)
-        if math.isfinite(t):
-            rows[s], eff[s] = fly_navigated(p, z0, us, noise[:, s], t, m, nodes, gain_u, gain_t, smax, ff_u, ff_t, th[s], nu[s], on,
-                                            formulation, dtype)
-        else:
-            rows[s], eff[s] = np.nan, np.nan
-    r64 = rows.astype(np.float64)
-    return dict(samples=rows, effort=eff, stats=dr.statistics(nominal.astype(np.float64), r64), nominal=nominal, m=m, nodes=nodes)
+    return gr.dispersion_result(*gr.fly_samples(p16, blob, nt, xi, sigma, sigma_u, (gain_u, gain_t, smax, ff_u, ff_t), th, nu, on, formulation,
+                                                substeps, dtype), dtype)
 
 
 def simulate_linear(rec, G, direction, dz0, theta, theta_hat=None, ff_u=None, ff_t=None):

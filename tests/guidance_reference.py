@@ -3,13 +3,24 @@ problem.
 
 Step records by the complex step on flight_jacobian_reference.step -- Phi_k = dz_k/dz_{k-1}, g_k = dz_k/du_k, the derivative
 with respect to the 16 SI fields and the scaled t_f -- about the reference's own nominal flight; the Riccati recursion of the
-header in dense numpy; the closed-loop Jacobian as the product of the closed-loop step maps; and the guided flight as a loop
-of its own over flight_reference.rhs.  Nothing here comes from the kernels.  `dtype` switches the whole computation (nominal
-flight, records, recursion; the guided flight) between float64 and numpy's longdouble: the difference of the two runs measures
-what double precision loses on the case at hand, and the GPU tests derive their bounds from it.
+header in dense numpy; the closed-loop Jacobian as the product of the closed-loop step maps; and the closed-loop flight as a
+loop of its own over flight_reference.rhs.  Nothing here comes from the kernels.  `dtype` switches the whole computation
+(nominal flight, records, recursion; the closed-loop flight) between float64 and numpy's longdouble: the difference of the two
+runs measures what double precision loses on the case at hand, and the GPU tests derive their bounds from it.
+
+The closed-loop flight is written once, in fly, for the four sample drivers: disperse_guided here,
+feedforward_reference.disperse_navigated, history_reference.history and navdrift_reference.history_drifting all go through
+fly_samples and differ in the beliefs they form and the statistics they take.  Where the tests find two of them equal bit for
+bit (guided against navigated end rows, frozen drifting channels against the history) they pin that plumbing and nothing
+else: it is one law flown twice.  The independent evidence for the law is dispersion_reference.fly_rows, an open-loop flight
+built directly on flight_reference that shares nothing with fly; the two "...agrees_with_the_closed_loop_jacobian_to_second_order"
+tests; and the central differences of the flight in test_lincov_reference (test_jacobian_is_the_central_difference_of_the_flight)
+and test_navdrift_reference (test_impulse_response_is_the_central_difference_of_the_flight), which judge it against the
+linearisations derived from the step records.
 """
 from __future__ import annotations
 
+import collections
 import math
 
 import numpy as np
@@ -20,6 +31,7 @@ import flight_reference as fr
 
 H = 1e-30
 GUIDE_ROWS = 5
+NQ = 10                        # quantities per node: the state, the altitude, the executed control, the correction
 NREC = 7 + 16 + 1 + 1          # perturbed copies of a step: z_{k-1} (7), the 16 fields, t_f, u_k
 
 
@@ -177,38 +189,69 @@ def _rhs(dtype):
     return lambda p, z, u, formulation: jr.rhs(np.asarray(p, dtype=dtype), z, dtype(u), formulation)
 
 
-def fly_guided(p, z0, us, noise, tf, m, nodes, gain_u, gain_t, smax, formulation=0, dtype=np.float64):
-    """One guided flight: p the sample's 16 fields, z0 (7,), us (K,) the nominal controls, noise (K,) the execution errors
-    (sigma_u xi), tf the sample's scaled t_f, m held, nodes (K + 1, 7) the nominal flight the feedback refers to, gain_u (K, 7),
-    gain_t (7,) or None, smax.  -> (rows (9,), effort (4,): clipped steps, max |K . dz|, stretch, and -- the reference's own -- the
-    smallest distance of an unclipped command from the clip, | |u_k - K . dz| - 1 | (inf where no row steers))"""
+def altitude(p, x, y):
+    """metres above R0 of a scaled position, the radius relation of flight_reference.apsides: p[9] = r_peri, p[2] = R0"""
+    X, Y = x * p[9], y * p[9] + p[2]
+    return np.sqrt(X * X + Y * Y) - p[2]
+
+
+# What one flight leaves behind: hist (K, 10) of dtype, row k - 1 the ten quantities of node k (NaN from the step that failed on);
+# clipped (K,) bool and margin (K,), the distance of the step's command from the clip (inf where the step has neither gain nor
+# feed-forward); corr (K,), the correction of every step that was begun (hist[:, 9] holds it only for the steps that ended);
+# stretch, the applied cutoff stretch; p, the fields as the flight read them; error, the exception of math.* that ended it, or None.
+Flight = collections.namedtuple("Flight", "hist clipped margin corr stretch p error")
+
+
+def fly(p, z0, us, noise, tf, m, nodes, gain_u=None, gain_t=None, smax=0.0, ff_u=None, ff_t=None, theta_hat=0.0, nu=None, nu_on=None,
+        formulation=0, dtype=np.float64):
+    """One closed-loop flight, the command law of include/ascent.h: p the sample's 16 fields, z0 (7,), us (K,) the nominal controls,
+    noise (K,) the execution errors (sigma_u xi), tf the sample's scaled t_f, m held, nodes (K + 1, 7) the nominal flight the
+    feedback refers to (None: there is no law), gain_u (K, 7) or None for the open loop, gain_t (7,) or None, smax, ff_u (K,) or
+    None, ff_t or None, theta_hat a scalar or (K,), nu (7,) or (K, 7) and nu_on (7,) bool: where the bias is applied; row k - 1 of a
+    per-step theta_hat or nu is what step k steers on (the cutoff stretch of step K uses row K - 1 as well).  -> Flight"""
     rhs = _rhs(dtype)
     p = [float(v) for v in p] if dtype is np.float64 else np.asarray(p, dtype=np.float64).astype(dtype)
     K = len(us)
     z = np.array(z0, dtype=dtype)
-    nclip, dmax, stretch, margin = 0.0, 0.0, 0.0, math.inf
+    theta_hat = 0.0 if theta_hat is None else theta_hat
+    hist, clipped, margin = np.full((K, NQ), np.nan, dtype=dtype), np.zeros(K, dtype=bool), np.full(K, math.inf)
+    corrs, stretch, error = np.zeros(K, dtype=dtype), 0.0, None
     with np.errstate(all="ignore"):
         dt = (dtype(tf) * p[11]) / K
         try:
             for k in range(K):
-                dz = z - np.asarray(nodes[k], dtype=dtype)
-                kk = np.asarray(gain_u[k], dtype=dtype)
+                th = dtype(theta_hat if np.ndim(theta_hat) == 0 else theta_hat[k])
+                if nodes is not None:
+                    dz = z - np.asarray(nodes[k], dtype=dtype)
+                if nu_on is not None:
+                    nuk = nu if np.ndim(nu) == 1 else nu[k]
+                    for i in range(7):
+                        if nu_on[i]:
+                            dz[i] = dz[i] + dtype(nuk[i])
+                kk = np.zeros(7, dtype=dtype) if gain_u is None else np.asarray(gain_u[k], dtype=dtype)
+                fk = dtype(0) if ff_u is None else dtype(ff_u[k])
                 uc = dtype(us[k])
-                if np.any(kk != 0):
+                corr = dtype(0)
+                if np.any(kk != 0) or fk != 0:
                     dot = dtype(0)
                     for i in range(7):
                         dot = dot + kk[i] * dz[i]
                     w = uc - dot
+                    if fk != 0:
+                        w = w - fk * th
+                        dot = dot + fk * th
                     uc = min(dtype(1), max(dtype(-1), w)) if math.isfinite(dot) else dtype(np.nan)
-                    nclip += 1.0 if uc != w else 0.0
-                    margin = min(margin, abs(abs(float(w)) - 1.0)) if math.isfinite(w) else 0.0
-                    dmax = math.nan if (math.isnan(dot) or math.isnan(dmax)) else max(dmax, abs(float(dot)))
+                    clipped[k] = bool(uc != w)
+                    margin[k] = abs(abs(float(w)) - 1.0) if math.isfinite(w) else 0.0
+                    corr = corrs[k] = dot
                 u = uc + dtype(noise[k]) if noise[k] != 0 else uc
                 h = dt / m
                 if k == K - 1 and gain_t is not None and smax > 0:
                     dtau = dtype(0)
                     for i in range(7):
                         dtau = dtau - dtype(gain_t[i]) * dz[i]
+                    if ff_t is not None and ff_t != 0:
+                        dtau = dtau - dtype(ff_t) * th
                     st = min(dtype(smax), max(dtype(-smax), dtau)) if math.isfinite(dtau) else dtype(np.nan)
                     stretch = float(st)
                     h = (dt * (1 + st)) / m
@@ -221,67 +264,104 @@ def fly_guided(p, z0, us, noise, tf, m, nodes, gain_u, gain_t, smax, formulation
                     k3 = rhs(p, z + 0.5 * h * k2, u, formulation)
                     k4 = rhs(p, z + h * k3, u, formulation)
                     z = z + h / 6.0 * (k1 + 2.0 * (k2 + k3) + k4)
+                hist[k, :7] = z
+                hist[k, 7], hist[k, 8], hist[k, 9] = altitude(p, z[0], z[1]), u, corr
+        except (ValueError, ZeroDivisionError, OverflowError) as e:       # math.* on a non-finite state: the rest stays NaN
+            error = e
+    return Flight(hist, clipped, margin, corrs, stretch, p, error)
+
+
+def end_rows(f):
+    """(9,): the flown end state and its apsides -- flight_reference.apsides in float64, flight_jacobian_reference.apsides in
+    longdouble --, NaN where math.* gave up in the flight or here"""
+    dtype = f.hist.dtype.type
+    z = f.hist[-1, :7]
+    if f.error is not None:
+        return np.full(9, np.nan)
+    with np.errstate(all="ignore"):
+        try:
             if dtype is np.float64:
-                peri, apo = fr.apsides(p, *z[:4])
+                peri, apo = fr.apsides(f.p, *z[:4])
             else:
-                pa, aa = jr.apsides(p[:, None], z[:, None])
+                pa, aa = jr.apsides(f.p[:, None], z[:, None])
                 peri, apo = pa[0], (aa[0] if np.isfinite(aa[0]) else np.inf)
         except (ValueError, ZeroDivisionError, OverflowError):
-            return np.full(9, np.nan), np.array([nclip, dmax, stretch, margin])
-    return np.concatenate([z, [peri, apo]]).astype(dtype), np.array([nclip, dmax, stretch, margin])
+            return np.full(9, np.nan)
+    return np.concatenate([z, [peri, apo]]).astype(dtype)
 
 
-def disperse_guided(p16, blob, nt, xi, sigma, sigma_u, gain_u, gain_t=None, smax=0.0, formulation=0, substeps=0, dtype=np.float64):
-    """-> dict(samples (samples, 9), effort (samples, 4), stats (82,), nominal (9,), m, nodes): one problem, arguments as
-    dispersion_reference.disperse plus the feedback.  The nominal flight the feedback refers to is flown here with the same loop."""
+def effort(f):
+    """(4,): clipped steps, max |K . dz + f theta-hat| (NaN once a correction is NaN), stretch, and -- the reference's own -- the
+    smallest distance of a command from the clip, | |u_k - K . dz - f theta-hat| - 1 | (0 for a command that is not finite, inf
+    where no row steers); of a flight that math.* ended, what had accumulated when it did"""
+    with np.errstate(all="ignore"):
+        c = np.abs(f.corr.astype(np.float64))
+    return np.array([float(np.count_nonzero(f.clipped)), math.nan if np.isnan(c).any() else c.max(), f.stretch, f.margin.min()])
+
+
+def _nominal(p16, us, tf, m, formulation, dtype):
+    """the nominal flight: zero start, no law, no noise; an exception of math.* is passed on"""
+    f = fly(p16, np.zeros(7), us, np.zeros(len(us)), tf, m, None, formulation=formulation, dtype=dtype)
+    if f.error is not None:
+        raise f.error
+    return f
+
+
+def nominal_nodes(p16, us, tf, m, formulation=0, dtype=np.float64):
+    """(K + 1, 7): the states of the nominal flight at the nodes 0 .. K"""
+    return np.concatenate([np.zeros((1, 7), dtype=dtype), _nominal(p16, us, tf, m, formulation, dtype).hist[:, :7]])
+
+
+def fly_samples(p16, blob, nt, xi, sigma, sigma_u, law, theta_hat=None, nu=None, nu_on=None, formulation=0, substeps=0,
+                dtype=np.float64, finite_tf=False):
+    """What the four sample drivers share: the blob's parts and the held m, the nominal flight and its nodes, the execution errors
+    sigma_u xi, and one flight per sample of dispersion_reference.perturbed under law = (gain_u, gain_t, smax, ff_u, ff_t),
+    steering on theta_hat[s] and nu[s] where nu_on.  -> (m, nodes, nominal, flights): Flights, None for a sample
+    whose t_f is not finite; finite_tf: nodes, nominal and flights are None where the blob's own t_f is not finite."""
     p16 = np.asarray(p16, dtype=np.float64)
     K = nt - 1
     _, us, tf = fr.blob_parts(np.asarray(blob, dtype=np.float64), nt)
     xi, sigma = np.asarray(xi, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
     m = fr.substeps_of((tf * p16[11]) / K, substeps)
     S = xi.shape[1]
-    if not math.isfinite(tf):
-        rows = np.full((S, 9), np.nan)
-        return dict(samples=rows, effort=np.full((S, 4), np.nan), stats=dr.statistics(np.full(9, np.nan), rows), nominal=np.full(9, np.nan), m=m)
-    nodes = nominal_nodes(p16, us, tf, m, formulation, dtype)
-    zero = np.zeros((K, 7))
-    nominal, _ = fly_guided(p16, np.zeros(7), us, np.zeros(K), tf, m, nodes, zero, None, 0.0, formulation, dtype)
-    rows, eff = np.empty((S, 9), dtype=dtype), np.empty((S, 4))
+    if finite_tf and not math.isfinite(tf):
+        return m, None, None, None
+    nominal = _nominal(p16, us, tf, m, formulation, dtype)
+    nodes = np.concatenate([np.zeros((1, 7), dtype=dtype), nominal.hist[:, :7]])
+    theta_hat = np.zeros(S) if theta_hat is None else theta_hat
+    nu = np.zeros((S, 7)) if nu is None else nu
     noise = np.zeros((K, S))          # the execution errors sigma_u xi, applied where sigma_u is non-zero
     if sigma_u is not None:
         su = np.asarray(sigma_u, dtype=np.float64)
         noise[su != 0.0] = su[su != 0.0, None] * xi[dr.NCOL:dr.NCOL + K][su != 0.0]
+    flights = []
     for s in range(S):
         p, z0, _, t = dr.perturbed(p16, us, tf, xi, sigma, None, s)
-        if math.isfinite(t):
-            rows[s], eff[s] = fly_guided(p, z0, us, noise[:, s], t, m, nodes, gain_u, gain_t, smax, formulation, dtype)
-        else:
-            rows[s], eff[s] = np.nan, np.nan
-    r64 = rows.astype(np.float64)
-    return dict(samples=rows, effort=eff, stats=dr.statistics(nominal.astype(np.float64), r64), nominal=nominal, m=m, nodes=nodes)
+        flights.append(fly(p, z0, us, noise[:, s], t, m, nodes, *law, theta_hat[s], nu[s], nu_on,
+                           formulation, dtype) if math.isfinite(t) else None)
+    return m, nodes, nominal, flights
 
 
-def nominal_nodes(p16, us, tf, m, formulation=0, dtype=np.float64):
-    """(K + 1, 7): the states of the nominal flight at the nodes 0 .. K, flown by fly_guided's own arithmetic"""
-    rhs = _rhs(dtype)
-    p = [float(v) for v in p16] if dtype is np.float64 else np.asarray(p16, dtype=np.float64).astype(dtype)
-    K = len(us)
-    z = np.zeros(7, dtype=dtype)
-    out = [z.copy()]
-    with np.errstate(all="ignore"):
-        h = ((dtype(tf) * p[11]) / K) / m
-        for k in range(K):
-            u = float(us[k]) if dtype is np.float64 else dtype(us[k])
-            if formulation == 1:
-                z[4], z[5] = 0.5 * p[12] * (u + 1.0), 0.0
-            for _ in range(m):
-                k1 = rhs(p, z, u, formulation)
-                k2 = rhs(p, z + 0.5 * h * k1, u, formulation)
-                k3 = rhs(p, z + 0.5 * h * k2, u, formulation)
-                k4 = rhs(p, z + h * k3, u, formulation)
-                z = z + h / 6.0 * (k1 + 2.0 * (k2 + k3) + k4)
-            out.append(z.copy())
-    return np.array(out)
+def dispersion_result(m, nodes, nominal, flights, dtype):
+    """the dict of disperse_guided and feedforward_reference.disperse_navigated from fly_samples' flights"""
+    rows, eff = np.full((len(flights), 9), np.nan, dtype=dtype), np.full((len(flights), 4), np.nan)
+    for s, f in enumerate(flights):
+        if f is not None:
+            rows[s], eff[s] = end_rows(f), effort(f)
+    nominal = end_rows(nominal)
+    return dict(samples=rows, effort=eff, stats=dr.statistics(nominal.astype(np.float64), rows.astype(np.float64)), nominal=nominal, m=m,
+                nodes=nodes)
+
+
+def disperse_guided(p16, blob, nt, xi, sigma, sigma_u, gain_u, gain_t=None, smax=0.0, formulation=0, substeps=0, dtype=np.float64):
+    """-> dict(samples (samples, 9), effort (samples, 4), stats (82,), nominal (9,), m, nodes): one problem, arguments as
+    dispersion_reference.disperse plus the feedback.  The nominal flight the feedback refers to is flown here with the same loop."""
+    m, nodes, nominal, flights = fly_samples(p16, blob, nt, xi, sigma, sigma_u, (gain_u, gain_t, smax, None, None), formulation=formulation,
+                                             substeps=substeps, dtype=dtype, finite_tf=True)
+    if flights is None:
+        rows = np.full((np.shape(xi)[1], 9), np.nan)
+        return dict(samples=rows, effort=np.full((len(rows), 4), np.nan), stats=dr.statistics(np.full(9, np.nan), rows), nominal=np.full(9, np.nan), m=m)
+    return dispersion_result(m, nodes, nominal, flights, dtype)
 
 
 def simulate_linear(rec, gain_u, gain_t, dz0):

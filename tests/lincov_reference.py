@@ -34,14 +34,10 @@ def altitude_gradient(p16, z, dtype=np.float64):
     return ga, direct
 
 
-def corridor(p16, blob, nt, sigma, sigma_u=None, gain_u=None, gain_t=None, smax=0.0, ff_u=None, ff_t=None, know=None, sigma_nav=None,
-             formulation=0, substeps=0, dtype=np.float64, rec=None):
-    """-> dict(S (K, 10, 32) d y_j / d c, cov (K, 10, 10), noise (K, 10, 10) the part N_j of cov, Q (K + 1, 7, 7), nominal (K, 10),
-    rec): every node 1 .. K (row j - 1 is node j).  sigma (24,), sigma_u (K,) or None, gain_u (K, 7) or None for the open loop,
-    gain_t (7,), smax, ff_u (K,), ff_t, know (16,), sigma_nav (8,) or None, as history_reference.history takes them."""
-    if rec is None:
-        rec = gr.records(p16, blob, nt, formulation, substeps, dtype)
-    K = nt - 1
+def law_arrays(K, sigma, sigma_u, gain_u, gain_t, smax, ff_u, ff_t, sigma_nav, dtype):
+    """The law and the sigmas as the recursions take them, absent parts as zeros: -> (Ku (K, 7), fu (K,), stretch: whether step K
+    stretches the cutoff, kt (7,), ft, su2 (K,) = sigma_u^2, var (32,): the variances of the 32 constants).  Without gain_u there
+    is no law at all: no feed-forward and no stretch either."""
     f = lambda a: np.asarray(a, dtype=np.float64).astype(dtype)
     Ku = np.zeros((K, 7), dtype=dtype) if gain_u is None else f(gain_u)
     fu = np.zeros(K, dtype=dtype) if ff_u is None or gain_u is None else f(ff_u)
@@ -50,9 +46,21 @@ def corridor(p16, blob, nt, sigma, sigma_u=None, gain_u=None, gain_t=None, smax=
     ft = dtype(ff_t) if stretch and ff_t is not None else dtype(0)
     su2 = np.zeros(K, dtype=dtype) if sigma_u is None else f(sigma_u) ** 2
     var = np.concatenate([f(sigma), np.zeros(8, dtype=dtype) if sigma_nav is None else f(sigma_nav)]) ** 2
+    return Ku, fu, stretch, kt, ft, su2, var
+
+
+def corridor(p16, blob, nt, sigma, sigma_u=None, gain_u=None, gain_t=None, smax=0.0, ff_u=None, ff_t=None, know=None, sigma_nav=None,
+             formulation=0, substeps=0, dtype=np.float64, rec=None):
+    """-> dict(S (K, 10, 32) d y_j / d c, cov (K, 10, 10), noise (K, 10, 10) the part N_j of cov, Q (K + 1, 7, 7), nominal (K, 10),
+    rec): every node 1 .. K (row j - 1 is node j).  sigma (24,), sigma_u (K,) or None, gain_u (K, 7) or None for the open loop,
+    gain_t (7,), smax, ff_u (K,), ff_t, know (16,), sigma_nav (8,) or None, as history_reference.history takes them."""
+    if rec is None:
+        rec = gr.records(p16, blob, nt, formulation, substeps, dtype)
+    K = nt - 1
+    Ku, fu, stretch, kt, ft, su2, var = law_arrays(K, sigma, sigma_u, gain_u, gain_t, smax, ff_u, ff_t, sigma_nav, dtype)
     th = np.zeros(NC, dtype=dtype)                        # theta-hat = w . dp + e
     if know is not None:
-        th[C_P:C_TF] = f(know)
+        th[C_P:C_TF] = np.asarray(know, dtype=np.float64).astype(dtype)
     th[C_E] = 1
     N = np.zeros((7, NC), dtype=dtype)                    # the knowledge bias as the feedback sees it
     N[np.arange(7), C_NU + np.arange(7)] = 1

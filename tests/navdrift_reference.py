@@ -2,20 +2,16 @@
 ascent_covariance_drifting_batch) for one problem.
 
 The eight knowledge channels are first-order Gauss-Markov sequences n_k = phi n_{k-1} + q omega_{k-1}; step k steers on n_k.
-fly_drifting is history_reference.fly_history's loop with the per-step nu_k and theta-hat_k.  corridor_drifting is
+history_drifting hands guidance_reference.fly a nu_k and a theta-hat_k per step.  corridor_drifting is
 lincov_reference.corridor's Jacobian recursion with the forcing of the columns 24..31 scaled by phi^k, and the part of the noise
 that the driving draws add is formed by superposition: one linear run of the step recursion per unit impulse of eps_k and of
 omega_a,k on guidance_reference.records, then sum var * outer(response, response).  The covariances C and D of the kernel's
 recursion are never formed.  Nothing here comes from the kernels.  `dtype` switches float64 and numpy's longdouble."""
 from __future__ import annotations
 
-import math
-
 import numpy as np
 
-import dispersion_reference as dr
 import feedforward_reference as ffr
-import flight_reference as fr
 import guidance_reference as gr
 import history_reference as hr
 import lincov_reference as lr
@@ -54,98 +50,19 @@ def sequences(K, xi_nav, sigma_nav, phi, q, omega, dtype=np.float64):
     return n, applied
 
 
-def fly_drifting(p, z0, us, noise, tf, m, nodes, gain_u=None, gain_t=None, smax=0.0, ff_u=None, ff_t=None, theta_hat=None, nu=None,
-                 nu_on=None, formulation=0, dtype=np.float64):
-    """history_reference.fly_history with theta_hat (K,) and nu (K, 7): row k - 1 is what step k steers on (the cutoff stretch of
-    step K uses row K - 1 as well).  -> (hist (K, 10), clipped (K,), margin (K,)) as there."""
-    rhs = gr._rhs(dtype)
-    p = [float(v) for v in p] if dtype is np.float64 else np.asarray(p, dtype=np.float64).astype(dtype)
-    K = len(us)
-    z = np.array(z0, dtype=dtype)
-    hist, clipped, margin = np.full((K, NQ), np.nan, dtype=dtype), np.zeros(K, dtype=bool), np.full(K, math.inf)
-    with np.errstate(all="ignore"):
-        dt = (dtype(tf) * p[11]) / K
-        try:
-            for k in range(K):
-                th = dtype(0) if theta_hat is None else dtype(theta_hat[k])
-                dz = z - np.asarray(nodes[k], dtype=dtype)
-                if nu_on is not None:
-                    for i in range(7):
-                        if nu_on[i]:
-                            dz[i] = dz[i] + dtype(nu[k][i])
-                kk = np.zeros(7, dtype=dtype) if gain_u is None else np.asarray(gain_u[k], dtype=dtype)
-                fk = dtype(0) if ff_u is None else dtype(ff_u[k])
-                uc = dtype(us[k])
-                corr = dtype(0)
-                if np.any(kk != 0) or fk != 0:
-                    dot = dtype(0)
-                    for i in range(7):
-                        dot = dot + kk[i] * dz[i]
-                    w = uc - dot
-                    if fk != 0:
-                        w = w - fk * th
-                        dot = dot + fk * th
-                    uc = min(dtype(1), max(dtype(-1), w)) if math.isfinite(dot) else dtype(np.nan)
-                    clipped[k] = bool(uc != w)
-                    margin[k] = abs(abs(float(w)) - 1.0) if math.isfinite(w) else 0.0
-                    corr = dot
-                u = uc + dtype(noise[k]) if noise[k] != 0 else uc
-                h = dt / m
-                if k == K - 1 and gain_t is not None and smax > 0:
-                    dtau = dtype(0)
-                    for i in range(7):
-                        dtau = dtau - dtype(gain_t[i]) * dz[i]
-                    if ff_t is not None and ff_t != 0:
-                        dtau = dtau - dtype(ff_t) * th
-                    st = min(dtype(smax), max(dtype(-smax), dtau)) if math.isfinite(dtau) else dtype(np.nan)
-                    h = (dt * (1 + st)) / m
-                u = float(u) if dtype is np.float64 else u
-                if formulation == 1:
-                    z[4], z[5] = 0.5 * p[12] * (u + 1.0), 0.0
-                for _ in range(m):
-                    k1 = rhs(p, z, u, formulation)
-                    k2 = rhs(p, z + 0.5 * h * k1, u, formulation)
-                    k3 = rhs(p, z + 0.5 * h * k2, u, formulation)
-                    k4 = rhs(p, z + h * k3, u, formulation)
-                    z = z + h / 6.0 * (k1 + 2.0 * (k2 + k3) + k4)
-                hist[k, :7] = z
-                hist[k, 7], hist[k, 8], hist[k, 9] = hr.altitude(p, z[0], z[1]), u, corr
-        except (ValueError, ZeroDivisionError, OverflowError):       # math.* on a non-finite state: the rest stays NaN
-            pass
-    return hist, clipped, margin
-
-
 def history_drifting(p16, blob, nt, xi, sigma, sigma_u, gain_u, gain_t=None, smax=0.0, ff_u=None, ff_t=None, know=None, xi_nav=None,
                      sigma_nav=None, phi=None, q=None, omega=None, formulation=0, substeps=0, dtype=np.float64):
     """history_reference.history with the drifting channels phi, q (8,) and their draws omega (8, K, samples): -> the same dict.
     The blob's t_f must be finite."""
-    p16 = np.asarray(p16, dtype=np.float64)
-    K = nt - 1
-    _, us, tf = fr.blob_parts(np.asarray(blob, dtype=np.float64), nt)
-    xi, sigma = np.asarray(xi, dtype=np.float64), np.asarray(sigma, dtype=np.float64)
-    m = fr.substeps_of((tf * p16[11]) / K, substeps)
-    S = xi.shape[1]
-    smp, clip, marg = np.full((S, K, NQ), np.nan, dtype=dtype), np.zeros((S, K), dtype=bool), np.full((S, K), math.inf)
-    nodes = gr.nominal_nodes(p16, us, tf, m, formulation, dtype)
-    nominal, _, _ = hr.fly_history(p16, np.zeros(7), us, np.zeros(K), tf, m, nodes, formulation=formulation, dtype=dtype)
+    K, S = nt - 1, np.shape(xi)[1]
     th_all, _, _ = ffr.beliefs(xi, sigma, know, xi_nav, sigma_nav)          # a frozen channel 7: the navigated call's theta-hat
     no7 = None if sigma_nav is None else np.concatenate([np.asarray(sigma_nav, dtype=np.float64)[:7], [0.0]])
     th_w, _, _ = ffr.beliefs(xi, sigma, know, xi_nav, no7)                  # w . dp alone
     n, on = sequences(K, xi_nav, sigma_nav, phi, q, omega if omega is not None else np.zeros((NA, K, S)), dtype)
-    fz7 = frozen(phi, q)[7]
-    noise = np.zeros((K, S))
-    if sigma_u is not None:
-        su = np.asarray(sigma_u, dtype=np.float64)
-        noise[su != 0.0] = su[su != 0.0, None] * xi[dr.NCOL:dr.NCOL + K][su != 0.0]
-    for s in range(S):
-        p, z0, _, t = dr.perturbed(p16, us, tf, xi, sigma, None, s)
-        if math.isfinite(t):
-            th = np.full(K, th_all[s], dtype=dtype) if fz7 else dtype(th_w[s]) + n[s, 1:, 7]
-            smp[s], clip[s], marg[s] = fly_drifting(p, z0, us, noise[:, s], t, m, nodes, gain_u, gain_t, smax, ff_u, ff_t, th,
-                                                    n[s, 1:, :7], on[:7], formulation, dtype)
-    nominal = np.asarray(nominal, dtype=np.float64)
-    return dict(samples=smp, clipped=clip, margin=marg, nominal=nominal, stats=hr.statistics(nominal, smp.astype(np.float64), clip), m=m,
-                nodes=nodes, n=n)
+    th = np.broadcast_to(th_all.astype(dtype)[:, None], (S, K)) if frozen(phi, q)[7] else th_w.astype(dtype)[:, None] + n[:, 1:, 7]
+    m, nodes, nominal, flights = gr.fly_samples(p16, blob, nt, xi, sigma, sigma_u, (gain_u, gain_t, smax, ff_u, ff_t), th, n[:, 1:, :7], on[:7],
+                                                formulation, substeps, dtype)
+    return dict(hr.history_result(m, nodes, nominal.hist, flights, dtype, K), n=n)
 
 
 def corridor_drifting(p16, blob, nt, sigma, sigma_u=None, gain_u=None, gain_t=None, smax=0.0, ff_u=None, ff_t=None, know=None,
@@ -162,13 +79,7 @@ def corridor_drifting(p16, blob, nt, sigma, sigma_u=None, gain_u=None, gain_t=No
     f = lambda a: np.asarray(a, dtype=np.float64).astype(dtype)
     ph = np.ones(NA, dtype=dtype) if phi is None else f(phi)
     q2 = np.zeros(NA, dtype=dtype) if q is None else f(q) ** 2
-    Ku = np.zeros((K, 7), dtype=dtype) if gain_u is None else f(gain_u)
-    fu = np.zeros(K, dtype=dtype) if ff_u is None or gain_u is None else f(ff_u)
-    stretch = gain_u is not None and gain_t is not None and smax > 0
-    kt = f(gain_t) if stretch else np.zeros(7, dtype=dtype)
-    ft = dtype(ff_t) if stretch and ff_t is not None else dtype(0)
-    su2 = np.zeros(K, dtype=dtype) if sigma_u is None else f(sigma_u) ** 2
-    var = np.concatenate([f(sigma), np.zeros(8, dtype=dtype) if sigma_nav is None else f(sigma_nav)]) ** 2
+    Ku, fu, stretch, kt, ft, su2, var = lr.law_arrays(K, sigma, sigma_u, gain_u, gain_t, smax, ff_u, ff_t, sigma_nav, dtype)
     thw = np.zeros(NC, dtype=dtype)
     if know is not None:
         thw[lr.C_P:lr.C_TF] = f(know)

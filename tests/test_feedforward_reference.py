@@ -11,7 +11,7 @@ import dispersion_reference as dr
 import feedforward_reference as ffr
 import flight_reference as fr
 import guidance_reference as gr
-from test_guidance_reference import _blob, _p16, _prototype_case
+from reference_cases import blob as _blob, p16 as _p16, prototype_case as _prototype_case
 
 E_FT = np.eye(16)[3]           # the direction of the tests: theta is newtons of thrust
 

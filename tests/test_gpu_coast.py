@@ -11,14 +11,13 @@ collected in PARITY["ratios"]; with ASCENT_COAST_PARITY_OUT=<file> it is written
 test of the documented maximum."""
 import ctypes as C
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
 
 import coast_reference as cr
 import flight_reference as fr
+from gpu_cases import parity_writer
 
 pytestmark = pytest.mark.gpu
 
@@ -27,16 +26,7 @@ NODES = 4                       # nodes 1 .. 4 of every arc: a quarter, a half, 
 CASES = cr.case_matrix()
 PARITY = {"ratios": {}, "info": {}}
 E_ARG = -1
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_COAST_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(PARITY, f, indent=1, sort_keys=True)
+_write_parity = parity_writer("ASCENT_COAST_PARITY_OUT", PARITY, sort_keys=True)
 
 
 def _record(check, ratio):

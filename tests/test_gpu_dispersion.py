@@ -6,7 +6,6 @@ The differences seen are collected in PARITY; with ASCENT_DISPERSION_PARITY_OUT=
 module is done (profiles/dispersion_parity.json is such a file)."""
 import ctypes as C
 import functools
-import json
 import os
 
 import numpy as np
@@ -15,75 +14,21 @@ import pytest
 import dispersion_reference as dr
 import flight_jacobian_reference as jr
 import flight_reference as fr
+from gpu_cases import (REL, SAMPLE_BOUND, check_statistics as _check_statistics, parity_writer, points as _points,
+                       sample_error as _sample_error, sigmas as _sigmas, solved as _solved, synthetic as _synthetic, xi as _xi)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARITY = {"samples_vs_reference": {}, "statistics_vs_numpy": {}, "covariance_vs_reference": {}, "covariance_vs_linear": {}}
 CASES = [(nt, scheme, form) for nt in (18, 34) for scheme, form in ((0, 0), (1, 0), (2, 0), (0, 1))]
-REL = 1e-3                 # relative sigma of the parameters the flight reads; absolute sigma of z_0, t_f (scaled) and every control
-SAMPLE_BOUND = 1e-10       # tests/test_gpu_flight.py's bound for the same arithmetic: scaled units; times r_peri for the altitudes
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_DISPERSION_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(PARITY, f, indent=1)
-
-
-def _points(n=2):
-    """the nominal point and sweep corners (config 3), tf_ub = 1.2"""
-    from lunar_module_ascent_trajectory_optimiser_amd import AscentParams, sweep_isp_drymass
-    nom = AscentParams(tf_ub=1.2).as_row()
-    sw = sweep_isp_drymass()
-    return np.vstack([nom, sw[0], sw[4095], sw[63], sw[4032]])[:n].copy()
-
-
-@functools.lru_cache(maxsize=None)
-def _solved(nt, scheme, form, n=2):
-    """(P, blob): solved once per case and shared; never written to"""
-    from lunar_module_ascent_trajectory_optimiser_amd import solve_batch
-    P = _points(n)
-    r = solve_batch(P, nt, tol=1e-10, max_iter=500, want_blob=True, scheme=scheme, formulation=form)
-    assert (r.status == 0).all(), r.status
-    P.setflags(write=False)
-    r.blob.setflags(write=False)
-    return P, r.blob
-
-
-def _synthetic():
-    """the nt = 3 blob of the flight Jacobian's smallest-grid test"""
-    return _points(1), fr.make_blob(np.zeros((2, 7)), np.array([0.4, -0.7]), 0.05)[:, None]
-
-
-def _sigmas(P, rel=REL, tf_rel=None, blob=None):
-    """keyword arguments of disperse_batch: all four groups non-zero"""
-    sig = np.array([dr.relative_sigma(p, rel) for p in P])
-    tf = sig[:, 23] if tf_rel is None else tf_rel * blob[-10]
-    return dict(z0_sigma=sig[:, :7].copy(), param_sigma=sig[:, 7:23].copy(), tf_sigma=np.array(tf), control_sigma=rel)
-
-
-def _xi(K, samples, seed=11):
-    return np.random.default_rng(seed).standard_normal((24 + K, samples))
+_write_parity = parity_writer("ASCENT_DISPERSION_PARITY_OUT", PARITY)
 
 
 def _reference(P, blob, nt, xi, kw, form, substeps, j):
     K = nt - 1
     sigma = np.concatenate([kw["z0_sigma"][j], kw["param_sigma"][j], [kw["tf_sigma"][j]]])
     return dr.disperse(P[j], blob[:, j], nt, xi, sigma, np.full(K, kw["control_sigma"]), form, substeps)
-
-
-def _sample_error(dev, ref, S):
-    """largest difference of (samples, 9) rows in units of the bound's scale; rows that are not finite must agree as they are"""
-    fin = np.isfinite(ref)
-    assert np.array_equal(fin, np.isfinite(dev)) and np.array_equal(ref[~fin], dev[~fin], equal_nan=True)
-    d = np.where(fin, np.abs(np.where(fin, dev, 0.0) - np.where(fin, ref, 0.0)), 0.0)
-    d[:, 7:] /= S
-    return d.max()
 
 
 def _check_samples(name, P, blob, nt, form, scheme, substeps, kw, samples=65):
@@ -129,37 +74,6 @@ def test_samples_match_reference_with_held_substeps():
     own = [fr.substeps_of((blob[21 * K, 0] + kw["tf_sigma"][0] * xi[23, s]) * P[0, 11] / K) for s in range(65)]
     assert any(o != m for o in own)
     _check_samples("nt18_scheme0_form0_substeps0_tf5pct", P, blob, nt, 0, 0, 0, kw)
-
-
-def _numpy_stats(samples):
-    """count, mean, unbiased covariance, min, max over the valid rows of (samples, 9)"""
-    v = samples[np.isfinite(samples).all(axis=1)]
-    n = len(v)
-    nan9 = np.full(9, np.nan)
-    return (n, v.mean(axis=0) if n else nan9, np.atleast_2d(np.cov(v.T)) if n >= 2 else np.full((9, 9), np.nan),
-            v.min(axis=0) if n else nan9, v.max(axis=0) if n else nan9)
-
-
-def _check_statistics(d, j, samples=None):
-    """problem j of a DispersionResult against numpy on (its own) samples: the error in units of the bound 1e-11 range_i
-    (range_i range_j for the covariance); extrema and count exact"""
-    n, mean, cov, lo, hi = _numpy_stats(d.samples[j] if samples is None else samples)
-    assert d.n_valid[j] == n
-    assert np.array_equal(d.min[j], lo, equal_nan=True) and np.array_equal(d.max[j], hi, equal_nan=True)
-    if n == 0:
-        assert np.isnan(d.mean[j]).all() and np.isnan(d.cov[j]).all()
-        return 0.0
-    rng = hi - lo
-    em = np.abs(d.mean[j] - mean)
-    assert np.all(em <= 1e-11 * rng), (em, rng)
-    worst = float(np.max(np.divide(em, rng, out=np.zeros(9), where=rng > 0)))
-    if n < 2:
-        assert np.isnan(d.cov[j]).all()
-        return worst
-    ec, rr = np.abs(d.cov[j] - cov), np.outer(rng, rng)
-    assert np.all(ec <= 1e-11 * rr), (ec, rr)
-    assert np.array_equal(d.cov[j], d.cov[j].T)
-    return max(worst, float(np.max(np.divide(ec, rr, out=np.zeros((9, 9)), where=rr > 0))))
 
 
 @pytest.mark.parametrize("samples", [1, 2, 63, 64, 65, 129, 192, 193, 257, 300, 1024])
@@ -213,7 +127,7 @@ def test_batch_independence_pointers_and_optional_output():
     from lunar_module_ascent_trajectory_optimiser_amd import _lib, disperse_batch
     from lunar_module_ascent_trajectory_optimiser_amd.solver import _opts
     nt, K, B, S = 34, 33, 5, 300
-    P, blob = _solved(nt, 0, 0, 5)
+    P, blob = _solved(nt, 0, 0, n=5)
     xi = _xi(K, S, 8)
     kw = _sigmas(P)
 

@@ -7,31 +7,21 @@ Bounds that depend on the conditioning of the case are computed here from the re
 longdouble run -- never from the device.  The differences seen are collected in PARITY; with ASCENT_FEEDFORWARD_PARITY_OUT=<file>
 they are written there as JSON when the module is done (profiles/feedforward_parity.json is such a file)."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 
 import feedforward_reference as ffr
 import guidance_reference as gr
-from test_gpu_dispersion import SAMPLE_BOUND, _check_statistics, _sample_error, _sigmas, _xi
-from test_gpu_guidance import CASES, M, _case, _guided, _stats, _weights
+from gpu_cases import (CASES, M, SAMPLE_BOUND, case as _case, check_statistics as _check_statistics, guided as _guided,
+                       parity_writer, sample_error as _sample_error, sigmas as _sigmas, stats as _stats, weights as _weights,
+                       xi as _xi)
 
 pytestmark = pytest.mark.gpu
 
 PARITY = {"feedforward_vs_reference": {}, "navigated_samples_vs_reference": {}, "effectiveness": {}}
 E_FT = np.eye(16)[3]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_FEEDFORWARD_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(PARITY, f, indent=1)
+_write_parity = parity_writer("ASCENT_FEEDFORWARD_PARITY_OUT", PARITY)
 
 
 def _dense(P):

@@ -5,6 +5,7 @@ other, over a whole sweep, and the surfaces built on them.
 The differences seen are collected in PARITY; with ASCENT_FLIGHT_PARITY_OUT=<file> they are written there as JSON when the
 module is done (profiles/flight_parity.json is such a file)."""
 import ctypes as C
+import functools
 import json
 import os
 
@@ -12,38 +13,21 @@ import numpy as np
 import pytest
 
 import flight_reference as fr
+from gpu_cases import parity_writer, points
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DCOST = 1e-4
+_points = functools.partial(points, dcost=DCOST)
 PARITY = {"reference_rk4": {}, "reference_dop853": {}, "fixtures": {}}
 SI_ROWS = [0, 1, 2, 3, 4, 5, 6, 7]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_FLIGHT_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(PARITY, f, indent=1)
+_write_parity = parity_writer("ASCENT_FLIGHT_PARITY_OUT", PARITY)
 
 
 def _lib():
     from lunar_module_ascent_trajectory_optimiser_amd import _lib
     return _lib
-
-
-def _points(n=2):
-    """the nominal point and sweep corners (config 3), tf_ub = 1.2"""
-    from lunar_module_ascent_trajectory_optimiser_amd import AscentParams, sweep_isp_drymass
-    nom = AscentParams(tf_ub=1.2).as_row()
-    sw = sweep_isp_drymass()
-    P = np.vstack([nom, sw[0], sw[4095], sw[63], sw[4032]])[:n].copy()
-    P[:, 15] = DCOST
-    return P
 
 
 def _combos():

@@ -6,51 +6,21 @@ Bounds that depend on the conditioning of the case are computed here from the re
 longdouble run -- never from the device.  The differences seen are collected in PARITY; with ASCENT_GUIDANCE_PARITY_OUT=<file>
 they are written there as JSON when the module is done (profiles/guidance_parity.json is such a file)."""
 import ctypes as C
-import functools
-import json
 import os
 
 import numpy as np
 import pytest
 
 import guidance_reference as gr
-from test_gpu_dispersion import SAMPLE_BOUND, _check_statistics, _sample_error, _sigmas, _solved, _synthetic, _xi
+from gpu_cases import (CASES, M, SAMPLE_BOUND, case as _case, check_statistics as _check_statistics, guided as _guided,
+                       parity_writer, sample_error as _sample_error, sigmas as _sigmas, stats as _stats, weights as _weights,
+                       xi as _xi)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARITY = {"gains_vs_reference": {}, "guided_samples_vs_reference": {}, "effectiveness": {}}
-# (nt, scheme, form): one chunk whose last step is half the grid; a chunk that holds one step (K = 17), every (scheme,
-# formulation) pair; three chunks
-CASES = [(3, 0, 0), (3, 0, 1)] + [(18, s, f) for s, f in ((0, 0), (1, 0), (2, 0), (0, 1))] + [(34, 0, 0)]
-M = 2                      # substeps of the parity tests
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_GUIDANCE_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(PARITY, f, indent=1)
-
-
-@functools.lru_cache(maxsize=None)
-def _case(nt, scheme, form, n=2):
-    """(P, blob): the synthetic blob at nt = 3, else GPU-solved and trimmed to 1e-12; shared, never written to"""
-    from lunar_module_ascent_trajectory_optimiser_amd import trim_batch
-    if nt == 3:
-        return _synthetic()
-    P, blob = _solved(nt, scheme, form, n)
-    t = trim_batch(P, blob, nt, scheme=scheme, formulation=form, substeps=M, rounds=8, tol=1e-12)
-    assert (t.status == 0).all(), t.summary
-    t.blob.setflags(write=False)
-    return P, t.blob
-
-
-def _weights(q, smax=0.5):
-    return dict(cond_weights=(q, q, q), control_weight=1.0, cutoff_weight=1.0, stretch_max=smax)
+_write_parity = parity_writer("ASCENT_GUIDANCE_PARITY_OUT", PARITY)
 
 
 def _row_error(a, b):
@@ -97,11 +67,6 @@ def test_gains_and_closed_loop_jacobian_match_reference(nt, scheme, form):
         assert v["device_error"] <= v["bound"], (k, v)
 
 
-def _guided(P, blob, nt, scheme, form, g, xi, kw, substeps=M, keep=True):
-    from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch
-    return disperse_batch(P, blob, nt, xi=xi, keep_samples=keep, scheme=scheme, formulation=form, substeps=substeps, guidance=g, **kw)
-
-
 @pytest.mark.parametrize("q", [1e6, 1e12])
 @pytest.mark.parametrize("nt,scheme,form,samples", [c + (65,) for c in CASES] + [(3, 0, 0, 1), (18, 0, 0, 257)])
 def test_guided_samples_match_reference_flown_with_the_device_gains(nt, scheme, form, samples, q):
@@ -144,10 +109,6 @@ def test_guided_samples_match_reference_flown_with_the_device_gains(nt, scheme, 
     PARITY["guided_samples_vs_reference"][f"nt{nt}_scheme{scheme}_form{form}_samples{samples}_q{q:g}"] = fig
     for k, v in fig.items():
         assert v["device_error"] <= v["bound"], (k, v)
-
-
-def _stats(d):
-    return np.concatenate([d.n_valid[:, None], d.nominal, d.mean, d.cov.reshape(-1, 81), d.min, d.max], axis=1)
 
 
 @pytest.mark.parametrize("nt,scheme,form", [(3, 0, 0), (3, 0, 1), (18, 0, 0), (18, 2, 0), (18, 0, 1), (34, 0, 0)])

@@ -8,8 +8,6 @@ Bounds that depend on the conditioning of the case are computed here from the re
 longdouble run -- never from the device.  The differences seen are collected in PARITY; with ASCENT_HISTORY_PARITY_OUT=<file>
 they are written there as JSON when the module is done (profiles/history_parity.json is such a file)."""
 import ctypes as C
-import functools
-import json
 import os
 
 import numpy as np
@@ -17,8 +15,8 @@ import pytest
 
 import feedforward_reference as ffr
 import history_reference as hr
-from test_gpu_dispersion import SAMPLE_BOUND
-from test_gpu_guidance import CASES, M, _case, _sigmas, _weights, _xi
+from gpu_cases import (CASES, M, SAMPLE_BOUND, case as _case, gains as _gains, parity_writer, scaled_error as _scaled_error,
+                       sigmas as _sigmas, stats as _stats, weights as _weights, xi as _xi)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,33 +25,12 @@ PARITY = {"history_samples_vs_reference": {}}
 CLIPPED = {}               # case -> the largest row 51 seen where the flags were compared with the reference
 # open loop; guided at q = 1e6 and 1e12; navigated (feed-forward of the thrust, navigation and knowledge errors) at the same two
 KINDS = [("open", 0.0), ("guided", 1e6), ("guided", 1e12), ("navigated", 1e6), ("navigated", 1e12)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_HISTORY_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(PARITY, f, indent=1)
+_write_parity = parity_writer("ASCENT_HISTORY_PARITY_OUT", PARITY)
 
 
 def _nav_kw(P, samples):
     """navigation sigmas 1e-6 (scaled), a knowledge sigma of 1e-3 of the thrust, and their draws"""
     return dict(nav_sigma=np.full(7, 1e-6), knowledge_sigma=1e-3 * P[:, 3], xi_nav=np.random.default_rng(13).standard_normal((8, samples)))
-
-
-@functools.lru_cache(maxsize=None)
-def _gains(nt, scheme, form, kind, q, n=2, substeps=M):
-    from lunar_module_ascent_trajectory_optimiser_amd import guidance_gains
-    if kind == "open":
-        return None
-    P, blob = _case(nt, scheme, form, n)
-    g = guidance_gains(P, blob, nt, scheme=scheme, formulation=form, substeps=substeps, want_jacobian=False,
-                       **(dict(feedforward="Ft") if kind == "navigated" else {}), **_weights(q))
-    assert (g.status == 0).all()
-    return g
 
 
 def _fly(P, blob, nt, scheme, form, kind, g, xi, kw, substeps=M, history=True, keep=True, keep_hist=True):
@@ -64,30 +41,15 @@ def _fly(P, blob, nt, scheme, form, kind, g, xi, kw, substeps=M, history=True, k
                           history=history, keep_history_samples=keep_hist and history is not False, **kw)
 
 
-def _stats(d):
-    return np.concatenate([d.n_valid[:, None], d.nominal, d.mean, d.cov.reshape(-1, 81), d.min, d.max], axis=1)
-
-
 def _hist(h, nodes=None):
     """(batch, NJ, 52) as hist_out holds it, optionally only the named (1-based) nodes"""
     a = np.concatenate([h.n_valid[:, :, None], h.nominal, h.mean, h.var, h.min, h.max, h.clipped[:, :, None]], axis=2)
     return a if nodes is None else a[:, np.searchsorted(h.nodes, nodes)]
 
 
-def _scaled_error(dev, ref, r_peri, scale89):
-    """largest difference of (samples, K, 10) histories in units of the bound's scale: scaled units for the state, r_peri for the
-    altitude, scale89 (K,) for the control and the correction; entries that are not finite must agree as they are"""
-    fin = np.isfinite(ref)
-    assert np.array_equal(fin, np.isfinite(dev)) and np.array_equal(ref[~fin], dev[~fin], equal_nan=True)
-    d = np.where(fin, np.abs(np.where(fin, dev, 0.0) - np.where(fin, ref, 0.0)), 0.0)
-    d[:, :, 7] /= r_peri
-    d[:, :, 8:] /= scale89[None, :, None]
-    return float(d.max()) if d.size else 0.0
-
-
 def _check_history_statistics(d, j):
     """problem j of a DispersionHistory against numpy on its own samples: means within 1e-11 range, variances within 1e-11
-    range^2 (test_gpu_dispersion._check_statistics' bounds); count and extrema exact.  -> the worst error in units of the bound"""
+    range^2 (gpu_cases.check_statistics' bounds); count and extrema exact.  -> the worst error in units of the bound"""
     h = d.history
     worst = 0.0
     for i in range(len(h.nodes)):

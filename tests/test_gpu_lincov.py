@@ -4,7 +4,7 @@ sweeps of the flight Jacobian and the guidance gains at the last node, against c
 samples, the bitwise promises of the header, bounded garbage, the example, and the second-order residual of the Monte Carlo
 variance.
 
-The cases are test_gpu_guidance.CASES, each open loop, guided and navigated at q = 1e6 and 1e12 with the device's own gains,
+The cases are gpu_cases.CASES, each open loop, guided and navigated at q = 1e6 and 1e12 with the device's own gains,
 substeps = 2, two problems.  Every entry is compared in the scale of its row -- scaled units for the state, r_peri for the
 altitude, max(1, |K_j|_1 + |f_j|) for the control and the correction, products of those for the covariance -- and, for the
 Jacobian, per relative step of its column (the field's own size for a parameter column, the thrust for the error of theta-hat,
@@ -13,7 +13,6 @@ float64 run against its longdouble run -- never from the device.  The difference
 ASCENT_LINCOV_PARITY_OUT=<file> they are written there as JSON when the module is done (profiles/lincov_parity.json is such a file)."""
 import ctypes as C
 import functools
-import json
 import math
 import os
 
@@ -23,47 +22,17 @@ import pytest
 import guidance_reference as gr
 import history_reference as hr
 import lincov_reference as lr
-from test_gpu_guidance import CASES, M, _case, _sigmas, _weights, _xi
+from gpu_cases import (CASES, FD_STEPS, FLOOR, M, case as _case, col_scales as _col_scales, gains as _gains,
+                       norm_cov as _norm_cov, norm_jac as _norm_jac, parity_writer, sigmas as _sigmas, weights as _weights,
+                       xi as _xi)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARITY = {"corridor_vs_reference": {}, "forward_vs_adjoint": {}, "corridor_vs_flight_kernel": {}, "second_order_residual": {}}
 KINDS = [("open", 0.0), ("guided", 1e6), ("guided", 1e12), ("navigated", 1e6), ("navigated", 1e12)]
-FLOOR = 1e-10              # the project's bound for this arithmetic (test_gpu_dispersion.SAMPLE_BOUND), in the scales above
 LD = np.longdouble
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_LINCOV_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(PARITY, f, indent=1)
-
-
-@functools.lru_cache(maxsize=None)
-def _gains(nt, scheme, form, kind, q, n=2, jacobian=False):
-    """the device's own gains of a case; navigated: with the feed-forward of the thrust"""
-    from lunar_module_ascent_trajectory_optimiser_amd import guidance_gains
-    if kind == "open":
-        return None
-    P, blob = _case(nt, scheme, form, n)
-    g = guidance_gains(P, blob, nt, scheme=scheme, formulation=form, substeps=M, want_jacobian=jacobian,
-                       **(dict(feedforward="Ft") if kind == "navigated" else {}), **_weights(q))
-    assert (g.status == 0).all()
-    return g
-
-
-def _col_scales(p16):
-    """(32,) the size of a unit relative step of every constant: the field's own (1 where it is zero), the thrust for the error of
-    theta-hat, 1 in scaled units"""
-    s = np.ones(lr.NC)
-    s[lr.C_P:lr.C_TF] = np.where(p16 != 0, np.abs(p16), 1.0)
-    s[lr.C_E] = abs(p16[3])
-    return s
+_write_parity = parity_writer("ASCENT_LINCOV_PARITY_OUT", PARITY)
 
 
 def _unit_sigmas(P, kind, rel=1.0):
@@ -97,14 +66,6 @@ def _all(lc):
     B, NJ = lc.nominal.shape[:2]
     parts = [lc.nominal, lc.cov.reshape(B, NJ, -1)] + ([] if lc.jacobian is None else [lc.jacobian.reshape(B, NJ, -1)])
     return np.concatenate(parts, axis=2)
-
-
-def _norm_jac(S, rows, cols):
-    return np.asarray(S * cols[None, None, :] / rows[:, :, None], dtype=np.float64)
-
-
-def _norm_cov(Cv, rows):
-    return np.asarray(Cv / (rows[:, :, None] * rows[:, None, :]), dtype=np.float64)
 
 
 @functools.lru_cache(maxsize=None)
@@ -214,9 +175,6 @@ def _reference_flight_difference(p16, rec, nodes, law, cs, form, h):
             n[c - lr.NC] = h
         out[:, :, c] = (fly(e, n) - fly(-e, -n)) / (2.0 * h * (cs[c] if c < lr.NC else 1.0))
     return out
-
-
-FD_STEPS = (1e-5, 1e-6, 1e-7, 1e-8, 1e-9, 1e-10, 1e-11)          # relative steps tried; truncation falls and rounding rises along them
 
 
 @pytest.mark.parametrize("kind", ["open", "navigated"])

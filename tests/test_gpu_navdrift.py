@@ -3,7 +3,7 @@ channels give the parent calls' bits, every sample against the CPU reference (te
 device's own gains, the reduction against numpy, the impulse response of the flight kernel against the noise model the covariance
 kernel sums, the covariance kernel against the reference's superposition, the bitwise promises of the header, bounded garbage.
 
-The cases are five of test_gpu_guidance.CASES at q = 1e6 and the K = 17 backward-Euler one at q = 1e12 as well, navigated with
+The cases are five of gpu_cases.CASES at q = 1e6 and the K = 17 backward-Euler one at q = 1e12 as well, navigated with
 the feed-forward of the thrust, substeps = 2, two problems, 300 samples.  The entry points are called through ctypes, because
 phi and q are set directly: a random walk (phi = 1, q > 0) has no time constant.  Bounds that depend on the conditioning of the
 case are computed here from the reference alone -- its float64 run against its longdouble run -- never from the device.  The
@@ -11,8 +11,6 @@ differences seen are collected in PARITY; with ASCENT_NAVDRIFT_PARITY_OUT=<file>
 is done (profiles/navdrift_parity.json is such a file)."""
 import ctypes as C
 import functools
-import json
-import os
 import types
 
 import numpy as np
@@ -21,10 +19,9 @@ import pytest
 import guidance_reference as gr
 import lincov_reference as lr
 import navdrift_reference as nd
-from test_gpu_dispersion import SAMPLE_BOUND
-from test_gpu_guidance import M, _case, _weights, _xi
-from test_gpu_history import _scaled_error
-from test_gpu_lincov import FD_STEPS, FLOOR, _col_scales, _norm_cov, _norm_jac
+from gpu_cases import (FD_STEPS, FLOOR, M, SAMPLE_BOUND, case as _case, col_scales as _col_scales, gains as _gains,
+                       norm_cov as _norm_cov, norm_jac as _norm_jac, parity_writer, ptr as _ptr, same as _same,
+                       scaled_error as _scaled_error, sigmas as _sigmas, weights as _weights, xi as _xi)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,25 +34,7 @@ PHI = np.array([0.9, 0.5, 1.0, 1.0, 0.0, 0.97, 1.0, 0.7])
 START = np.array([1.0, 2.0, 1.0, 0.0, 1.0, 0.0, 0.0, 1.0])          # sigma_nav in units of the case's sigma
 DRIVE = np.array([np.sqrt(1 - 0.81), 0.0, 0.0, 0.3, 1.0, 0.2, 0.0, np.sqrt(1 - 0.49)])
 FROZEN = (PHI == 1.0) & (DRIVE == 0.0)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_NAVDRIFT_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(PARITY, f, indent=1)
-
-
-@functools.lru_cache(maxsize=None)
-def _gains(nt, scheme, form, q, n=2):
-    from lunar_module_ascent_trajectory_optimiser_amd import guidance_gains
-    P, blob = _case(nt, scheme, form, n)
-    g = guidance_gains(P, blob, nt, scheme=scheme, formulation=form, substeps=M, want_jacobian=False, feedforward="Ft", **_weights(q))
-    assert (g.status == 0).all()
-    return g
+_write_parity = parity_writer("ASCENT_NAVDRIFT_PARITY_OUT", PARITY)
 
 
 def _rel(q):
@@ -65,7 +44,6 @@ def _rel(q):
 
 def _inputs(P, nt, q, rel=None, control=True):
     """the sigma arrays of a case as the C ABI takes them: sigma [24][B], sigma_u [K][B], sigma_nav, phi, q [8][B]"""
-    from test_gpu_dispersion import _sigmas
     rel = _rel(q) if rel is None else rel
     B, K = P.shape[0], nt - 1
     kw = _sigmas(P, rel)
@@ -85,10 +63,6 @@ def _draws(K, samples=S):
 def _law_arrays(g, K, B):
     from lunar_module_ascent_trajectory_optimiser_amd.solver import _feedback_arrays, _feedforward_arrays
     return _feedback_arrays(g, K, B) + _feedforward_arrays(g, K, B)
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _mc(P, blob, nt, scheme, form, g, xi, xi_nav, om, inp, stride=1, optional=True, parent=False, drift=True, substeps=M):
@@ -137,17 +111,13 @@ def _lc(P, blob, nt, scheme, form, g, inp, stride=1, jac=True, parent=False, dri
     return out
 
 
-def _same(a, b):
-    return all((a[k] is None and b[k] is None) or np.array_equal(a[k], b[k], equal_nan=True) for k in a)
-
-
 @pytest.mark.parametrize("nt,scheme,form,q", CASES)
 def test_frozen_is_the_parents_bits(nt, scheme, form, q):
     """phi = 1 and q = 0 through the new kernels, and the arrays null, against ascent_disperse_history_batch and
     ascent_covariance_history_batch on the same inputs: every output array, NaN positions included; the draws are all NaN"""
     P, blob = _case(nt, scheme, form)
     K = nt - 1
-    g = _gains(nt, scheme, form, q)
+    g = _gains(nt, scheme, form, "navigated", q)
     inp = _inputs(P, nt, q)
     frozen = dict(inp, phi=np.ones_like(inp["phi"]), q=np.zeros_like(inp["q"]))
     xi, xn, _ = _draws(K)
@@ -209,7 +179,7 @@ def test_samples_match_reference_and_the_reduction_matches_numpy(nt, scheme, for
     from lunar_module_ascent_trajectory_optimiser_amd.solver import _cov_from_upper, _history_result
     P, blob = _case(nt, scheme, form)
     K = nt - 1
-    g = _gains(nt, scheme, form, q)
+    g = _gains(nt, scheme, form, "navigated", q)
     inp = _inputs(P, nt, q)
     xi, xn, om = _draws(K)
     dev = _mc(P, blob, nt, scheme, form, g, xi, xn, om, inp)
@@ -243,14 +213,14 @@ def test_samples_match_reference_and_the_reduction_matches_numpy(nt, scheme, for
 def test_impulse_response_of_the_flight_kernel_is_the_noise_model():
     """nt = 18, q = 1e6, every sigma zero: sample pairs whose xi_drift is +-1 at one (a, k) and zero elsewhere, every channel at the
     first step, the chunk boundary of the covariance sweep (k = 16) and the last step, q_a = h of the channel's scale for every h
-    of test_gpu_lincov.FD_STEPS.  The central difference, the best step taken per entry, against the reference's r_jak (longdouble
-    complex-step records).  Bound: 10 x what the reference's own float64 flight pairs (navdrift_reference.fly_drifting) show by the
+    of gpu_cases.FD_STEPS.  The central difference, the best step taken per entry, against the reference's r_jak (longdouble
+    complex-step records).  Bound: 10 x what the reference's own float64 flight pairs (navdrift_reference.history_drifting) show by the
     same measure, from problem 0.  The flight kernel knows nothing of the covariance kernel: this ties the two noise models."""
     nt, scheme, form, q = 18, 0, 0, 1e6
     K = nt - 1
     P, blob = _case(nt, scheme, form)
     B = P.shape[0]
-    g = _gains(nt, scheme, form, q)
+    g = _gains(nt, scheme, form, "navigated", q)
     pairs = [(a, k) for a in range(8) for k in (1, 16, K)]
     Sx = 2 * len(pairs)
     om = np.zeros((8, K, Sx))
@@ -301,7 +271,7 @@ def _compared(nt, scheme, form, q):
     unit as well.  noise: only sigma_u and the drift on; drift: only the drift on, so that an error in C or D cannot hide behind Q."""
     P, blob = _case(nt, scheme, form)
     B, K = P.shape[0], nt - 1
-    g = _gains(nt, scheme, form, q)
+    g = _gains(nt, scheme, form, "navigated", q)
     cs = np.array([_col_scales(p) for p in P])
     full = dict(sigma=np.ascontiguousarray(cs[:, :24].T), sigma_u=np.ones((K, B)), sigma_nav=np.ascontiguousarray((cs[:, 24:] * START).T),
                 phi=np.ascontiguousarray(np.tile(PHI, (B, 1)).T), q=np.ascontiguousarray((cs[:, 24:] * DRIVE).T))
@@ -439,7 +409,7 @@ def test_bounded_garbage():
     from lunar_module_ascent_trajectory_optimiser_amd.solver import _opts
     nt, K, B, q = 18, 17, 2, 1e6
     P, blob = _case(nt, 0, 0)
-    g = _gains(nt, 0, 0, q)
+    g = _gains(nt, 0, 0, "navigated", q)
     inp = _inputs(P, nt, q)
     xi, xn, om = _draws(K, 70)
     good_mc, good_lc = _mc(P, blob, nt, 0, 0, g, xi, xn, om, inp), _lc(P, blob, nt, 0, 0, g, inp)
@@ -486,7 +456,7 @@ def test_front_end_makes_the_same_call():
     nt, K, q = 18, 17, 1e6
     P, blob = _case(nt, 0, 0)
     B = P.shape[0]
-    g = _gains(nt, 0, 0, q)
+    g = _gains(nt, 0, 0, "navigated", q)
     inp = _inputs(P, nt, q)
     tau = np.array([60.0, 10.0, np.inf, 60.0, 1e-300, 30.0, np.inf])
     steady = np.array([1e-6, 0.0, 0.0, 2e-6, 1e-6, 1e-6, 0.0])

@@ -1,31 +1,24 @@
 """Post-optimal sensitivity dJ*/dp (ascent_param_sensitivity) on the GPU: the kernel against the CPU reference of dL/dp at
 the same blob, against finite differences of GPU solves, over a whole sweep, and the surfaces built on it."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 import sens_reference as sr
+from gpu_cases import points
 
 pytestmark = pytest.mark.gpu
 
 FIELDS = sr.FIELDS
 DCOST = 1e-4
+_points = functools.partial(points, dcost=DCOST)
 
 
 def _lib():
     from lunar_module_ascent_trajectory_optimiser_amd import _lib
     return _lib
-
-
-def _points(n=3):
-    """the nominal point and sweep corners (config 3), tf_ub = 1.2"""
-    from lunar_module_ascent_trajectory_optimiser_amd import AscentParams, sweep_isp_drymass
-    nom = AscentParams(tf_ub=1.2).as_row()
-    sw = sweep_isp_drymass()
-    P = np.vstack([nom, sw[0], sw[4095], sw[63], sw[4032]])[:n].copy()
-    P[:, 15] = DCOST
-    return P
 
 
 def _combos():

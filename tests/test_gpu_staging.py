@@ -6,13 +6,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_cases import ptr as _ptr, same as _same
+
 pytestmark = pytest.mark.gpu
 
 NT, K, B, COAST_NODES = 40, 39, 5, 7
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 @pytest.fixture(scope="module")
@@ -54,10 +52,6 @@ def _calls(L, P, blob, state, o, stream, optional=True):
     run("coast", L.ascent_coast_batch, _ptr(P), B, _ptr(state), COAST_NODES, _ptr(ct), _ptr(ctf), _ptr(aps), 0, stream, 0,
         traj=ct, tf=ctf, apsides=aps)
     return out
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
 
 
 def test_host_pointers_on_a_caller_stream_and_without_optional_outputs(solved):

@@ -14,29 +14,21 @@ Grids: three nodes, the last node of a chunk and one node past it, for each form
 the last and usually partial chunk); batches of 3 and 5 (a ragged last wavefront with four NLPs per wavefront).  The largest
 error / bound ratio of every variant is collected in PARITY; with ASCENT_TERMINAL_STEP_PARITY_OUT=<file> it is written there as JSON
 when the module is done (profiles/terminal_step_parity.json is such a file)."""
-import json
 import os
 
 import numpy as np
 import pytest
 
 import lunar_module_ascent_trajectory_optimiser_amd as A
+from gpu_cases import parity_writer
 from terminal_step_reference import sections
 from test_terminal_step_reference import (CASES, GRIDS, MU, SUFFICIENT_ONLY, WRONG_INERTIA_CASES, WRONG_INERTIA_NT, Case, blob_of, dw_of,
                                           problems, reference)
 
 pytestmark = pytest.mark.gpu
 PARITY = {}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_TERMINAL_STEP_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump({"bound": "1e-8 x max(1, |LU section|max) per blob section", "largest_error_over_bound": PARITY}, f, indent=1, sort_keys=True)
+_write_parity = parity_writer("ASCENT_TERMINAL_STEP_PARITY_OUT",
+                              {"bound": "1e-8 x max(1, |LU section|max) per blob section", "largest_error_over_bound": PARITY}, sort_keys=True)
 
 
 # ---- the variants, spelled out: (kernel, form, scheme, terminal, move penalty, nt, batch)

@@ -6,8 +6,6 @@ Errors are measured per row relative to the row's largest entry, the parameter c
 t_f column as t_f d/dt_f.  The differences seen are collected in PARITY; with ASCENT_TRIM_PARITY_OUT=<file> they are written
 there as JSON when the module is done (profiles/trim_parity.json is such a file)."""
 import ctypes as C
-import functools
-import json
 import os
 
 import numpy as np
@@ -15,6 +13,7 @@ import pytest
 
 import flight_jacobian_reference as jr
 import flight_reference as fr
+from gpu_cases import parity_writer, points as _points, solved as _solved
 
 pytestmark = pytest.mark.gpu
 
@@ -25,42 +24,12 @@ PARITY = {"jacobian_vs_reference": {}, "jacobian_vs_device_differences": {}, "tr
 JAC_BOUND = 1e-9
 TRIM_BOUND = 2.6e-10
 CASES = [(nt, scheme, form, term) for nt in (18, 34, 50) for scheme, form in ((0, 0), (1, 0), (2, 0), (0, 1)) for term in (0, 1)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_parity():
-    yield
-    path = os.environ.get("ASCENT_TRIM_PARITY_OUT")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(PARITY, f, indent=1)
+_write_parity = parity_writer("ASCENT_TRIM_PARITY_OUT", PARITY)
 
 
 def _lib():
     from lunar_module_ascent_trajectory_optimiser_amd import _lib
     return _lib
-
-
-def _points(n=2):
-    """the nominal point and sweep corners (config 3), tf_ub = 1.2"""
-    from lunar_module_ascent_trajectory_optimiser_amd import AscentParams, sweep_isp_drymass
-    nom = AscentParams(tf_ub=1.2).as_row()
-    sw = sweep_isp_drymass()
-    return np.vstack([nom, sw[0], sw[4095], sw[63], sw[4032]])[:n].copy()
-
-
-@functools.lru_cache(maxsize=None)
-def _solved(nt, scheme, form, term, n=2):
-    """(P, blob): solved once per case and shared; never written to.  tol 1e-10: the slack the interior-point method leaves on
-    the terminal inequalities, which the comparison of the flown apsides with the NLP's own sees, is then 1.5e-4 m."""
-    from lunar_module_ascent_trajectory_optimiser_amd import solve_batch
-    P = _points(n)
-    r = solve_batch(P, nt, tol=1e-10, max_iter=500, want_blob=True, scheme=scheme, formulation=form, terminal=term)
-    assert (r.status == 0).all(), r.status
-    P.setflags(write=False)
-    r.blob.setflags(write=False)
-    return P, r.blob
 
 
 def _row_scale(jac, jac_u, p16, tf):

@@ -3,7 +3,6 @@
 Jacobian to second order and for what the feedback is worth on the nominal problem; and the argument refusals of the two
 entry points (include/ascent.h: ascent_guidance_gains, ascent_disperse_guided_batch).  No GPU."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -12,19 +11,7 @@ import dispersion_reference as dr
 import flight_jacobian_reference as jr
 import flight_reference as fr
 import guidance_reference as gr
-from oracle.ascent_numpy import Params
-
-
-def _p16():
-    return np.array([getattr(Params(), f) for f in fr.FIELDS], dtype=np.float64)
-
-
-def _blob(nt=18, seed=4):
-    """an arbitrary bounded control with free and (two) saturated steps"""
-    b = fr.synthetic_exact_blob(_p16(), nt, tf=0.9, seed=seed)
-    K = nt - 1
-    b[7 * K + 3], b[7 * K + K - 2] = 1.0, -1.0
-    return b
+from reference_cases import blob as _blob, p16 as _p16, prototype_case as _prototype_case
 
 
 @pytest.mark.parametrize("form", [0, 1])
@@ -112,20 +99,6 @@ def test_one_guided_sample_agrees_with_the_closed_loop_jacobian_to_second_order(
     ratio = rem[0][big] / rem[1][big]
     print("ratios", ratio)
     assert np.all((ratio >= 3.0) & (ratio <= 5.0))
-
-
-@functools.lru_cache(maxsize=None)
-def _prototype_case():
-    """backward Euler, nt = 50, the C oracle's solution trimmed with numpy to 1e-12 (m = 18), and its records"""
-    from oracle import c_oracle
-    c_oracle.build()
-    nt = 50
-    p16 = c_oracle.pack_params(Params())
-    r = c_oracle.solve_batch(p16[None], nt, 300, 1e-9, want_blob=True)
-    assert r["status"][0] == 0
-    t = jr.trim(p16, r["blob"][0], nt, 0, 0, 0, 8, 1e-12)
-    assert t["summary"][0] == 0
-    return p16, t["blob"], nt, gr.records(p16, t["blob"], nt), gr.records(p16, t["blob"], nt, dtype=np.longdouble)
 
 
 def test_double_precision_loses_digits_as_the_weights_grow():

@@ -12,7 +12,7 @@ import feedforward_reference as ffr
 import flight_reference as fr
 import guidance_reference as gr
 import history_reference as hr
-from test_guidance_reference import _blob, _p16
+from reference_cases import blob as _blob, p16 as _p16
 
 NT, K, M = 18, 17, 2
 

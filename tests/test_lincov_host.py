@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_guidance_reference import _blob
+from reference_cases import blob as _blob
 
 NT, K = 18, 17
 

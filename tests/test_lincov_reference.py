@@ -4,27 +4,13 @@ brute-force sum over the K execution errors taken as K more constants.  No GPU."
 import numpy as np
 import pytest
 
-import feedforward_reference as ffr
 import guidance_reference as gr
 import history_reference as hr
 import lincov_reference as lr
-from test_guidance_reference import _blob, _p16
+from reference_cases import blob as _blob, law as _law, p16 as _p16
 
 NT, K, M = 18, 17, 2
-E_FT = np.eye(16)[3]
 LD = np.longdouble
-
-
-def _law(kind, rec, p16):
-    """keyword arguments of lincov_reference.corridor for a kind of flight; the gains are the reference's own at q = 1e6"""
-    if kind == "open":
-        return {}
-    G = ffr.gains(rec, p16, np.array([1e6, 1e6, 1e6, 1.0, 1.0, 0.5]), E_FT, LD)
-    assert G["summary"][0] == 0
-    kw = dict(gain_u=G["gain_u"].astype(np.float64), gain_t=G["gain_t"].astype(np.float64), smax=0.5)
-    if kind == "navigated":
-        kw.update(ff_u=G["ff_u"].astype(np.float64), ff_t=float(G["ff_t"]), know=E_FT)
-    return kw
 
 
 def _fly(p16, rec, nodes, c, law, form, noise=None):

@@ -5,13 +5,11 @@ superposition the reference forms.  No GPU."""
 import numpy as np
 import pytest
 
-import feedforward_reference as ffr
 import guidance_reference as gr
 import history_reference as hr
 import lincov_reference as lr
 import navdrift_reference as nd
-from test_guidance_reference import _blob, _p16
-from test_lincov_reference import _law
+from reference_cases import blob as _blob, law as _law, p16 as _p16
 
 NT, K, M = 18, 17, 2
 LD = np.longdouble
@@ -141,7 +139,7 @@ def test_recursion_in_q_c_d_is_the_superposition():
 
 
 def test_impulse_response_is_the_central_difference_of_the_flight():
-    """r_jak of the reference against a pair of flights of fly_drifting whose omega_a,k is +-1 and everything else zero, with q_a
+    """r_jak of the reference against a pair of flights of history_drifting whose omega_a,k is +-1 and everything else zero, with q_a
     small enough to stay linear: channel 0 at the first step, channel 7 in the middle, channel 4 at the last step"""
     p16, blob = _p16(), _blob()
     recl = gr.records(p16, blob, NT, 0, M, LD)
