@@ -164,16 +164,47 @@ def corridor_report(name, d, params, tf, outdir=None, figure=None):
         fig.savefig(os.path.join(outdir, figure or "corridor_%s.png" % name.replace(" ", "_")), dpi=300)
 
 
-def disperse(m, scheme, samples=1024, corridor=False, outdir=None):
+QUANTILE_POINTS = (0.00135, 0.5, 0.99865)       # the -3-sigma point, the median and the +3-sigma point of a normal distribution
+PERIAPSIS_LIMIT = 15000.0                       # m: a flown periapsis below it counts as a violation
+
+
+def quantile_keywords():
+    """disperse_batch's keywords for quantile_report: the three points, and the limit on the flown periapsis (column 7)"""
+    lim = np.full((1, 12), np.nan)
+    lim[0, 7] = PERIAPSIS_LIMIT
+    return dict(quantiles=QUANTILE_POINTS, limits=lim)
+
+
+def quantile_report(name, d):
+    """The order statistics of one dispersed flight (disperse_batch(quantiles=..., limits=...)): the 0.135 / 50 / 99.865 % points of
+    the flown apsides, the fraction of samples whose periapsis ends below PERIAPSIS_LIMIT and, with a history, the 0.135 % ..
+    99.865 % altitude band at the node where it is widest."""
+    for what, q in (("periapsis", 7), ("apoapsis", 8)):
+        print("%s: flown %s 0.135 %% / 50 %% / 99.865 %% points: %.1f / %.1f / %.1f m" % ((name, what) + tuple(d.quantiles[0, :, q])))
+    print("%s: flown periapsis below %.0f m: %d of %d valid samples (%.3f %%)"
+          % (name, PERIAPSIS_LIMIT, d.below[0, 0, 7], d.n_valid[0], 100.0 * d.below[0, 0, 7] / max(int(d.n_valid[0]), 1)))
+    if d.history is not None:
+        h, ALT = d.history, 7
+        band = h.quantiles[0, :, 2, ALT] - h.quantiles[0, :, 0, ALT]
+        i = int(np.nanargmax(band))
+        print("%s: widest 0.135 %% .. 99.865 %% altitude band at node %d: %.1f .. %.1f m (median %.1f m, nominal %.1f m)"
+              % (name, h.nodes[i], h.quantiles[0, i, 0, ALT], h.quantiles[0, i, 2, ALT], h.quantiles[0, i, 1, ALT], h.nominal[0, i, ALT]))
+
+
+def disperse(m, scheme, samples=1024, corridor=False, outdir=None, quantiles=False):
     """The trimmed solution under a dispersed thrust and control: Monte Carlo on the device beside the flight Jacobian's linear
-    prediction from the same draws.  corridor: with the per-node history, and its lines (corridor_report)."""
+    prediction from the same draws.  corridor: with the per-node history, and its lines (corridor_report).  quantiles: with the
+    order statistics selected on the device, and their lines (quantile_report)."""
     from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, flight_jacobian, trim_batch
     res = m.result
     kw = dict(scheme=scheme, formulation=m._formulation)
     t = trim_batch(res.params, res.flight_blob(), res.nt, **kw)
     thrust = np.zeros(16)
     thrust[3] = 50.0
+    if quantiles:
+        kw = dict(kw, **quantile_keywords())
     d = disperse_batch(res.params, t.blob, res.nt, param_sigma=thrust, control_sigma=1e-3, samples=samples, history=corridor, **kw)
+    kw = dict(scheme=scheme, formulation=m._formulation)
     lin = np.sqrt(np.diagonal(d.linear_covariance(flight_jacobian(res.params, t.blob, res.nt, **kw)), axis1=1, axis2=2))
     print("dispersion: %d of %d samples valid; thrust 1-sigma 50 N, control 1-sigma 1e-3 per step" % (d.n_valid[0], samples))
     print("flown altitude (m)      nominal   Monte Carlo 1-sigma   linear 1-sigma   mean shift          min          max")
@@ -182,6 +213,8 @@ def disperse(m, scheme, samples=1024, corridor=False, outdir=None):
               % (name, d.nominal[0, q], d.std[0, q], lin[0, q], d.mean[0, q] - d.nominal[0, q], d.min[0, q], d.max[0, q]))
     if corridor:
         corridor_report("open loop", d, res.params, t.tf[0], outdir, "corridor.png")
+    if quantiles:
+        quantile_report("open loop", d)
     return d
 
 
@@ -211,7 +244,7 @@ def lincov_report(name, lc, d, params, tf, outdir=None, figure=None):
 
 
 def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=False, corridor=False, outdir=None, lincov=False,
-          nav_tau=None, knowledge_tau=None):
+          nav_tau=None, knowledge_tau=None, quantiles=False):
     """The trimmed solution under the same dispersions, open loop and steering back to the nominal with a cutoff on the state.
     The cutoff channel stretches the last step only, T / K = 2.2 s here: 50 N of 15 kN over a 435 s burn is 1.4 s (1-sigma) of burn
     time, so the stretch is allowed +-2 steps; at stretch_max = 0.5 it sits on its bound for most samples.
@@ -219,7 +252,8 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
     lincov: the open and the closed loop flown once more with their history, beside linear_corridor's band (lincov_report).
     nav_tau, knowledge_tau (seconds; with feedforward, corridor and lincov): the navigation bias as a stationary first-order
     Gauss-Markov process of that correlation time and the thrust estimate converging from its 10 N with that time constant
-    (steady sigma 0): the sampled and the linear altitude band side by side, next to those of the frozen bias."""
+    (steady sigma 0): the sampled and the linear altitude band side by side, next to those of the frozen bias.
+    quantiles: every flight flown with its order statistics, and the lines of quantile_report for each."""
     from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, guidance_gains, linear_corridor, trim_batch
     res = m.result
     kw = dict(scheme=scheme, formulation=m._formulation)
@@ -228,6 +262,8 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
     thrust = np.zeros(16)
     thrust[3] = 50.0
     dkw = dict(param_sigma=thrust, control_sigma=1e-3, samples=samples, history=corridor, **kw)
+    if quantiles:
+        dkw.update(quantile_keywords())
     op = disperse_batch(res.params, t.blob, res.nt, **dkw)
     cl = disperse_batch(res.params, t.blob, res.nt, guidance=g, keep_samples=True, **dkw)
     print("guidance: status %d, %d of %d controls free, largest steering gain %.4g, largest cutoff gain %.4g (weights %g, 1, 1)"
@@ -242,6 +278,9 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
     if corridor:
         corridor_report("open loop", op, res.params, t.tf[0], outdir)
         corridor_report("closed loop", cl, res.params, t.tf[0], outdir, "corridor.png")
+    if quantiles:
+        quantile_report("open loop", op)
+        quantile_report("closed loop", cl)
     if feedforward:
         # the same draws with the feed-forward: the feedback gains are the same bits, the samples now plan with their own thrust
         gf = guidance_gains(res.params, t.blob, res.nt, cond_weights=(weight,) * 3, control_weight=1.0, cutoff_weight=1.0, stretch_max=stretch_max,
@@ -258,6 +297,9 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
         if corridor:
             corridor_report("thrust known", known, res.params, t.tf[0], outdir)
             corridor_report("known to 10 N", nav, res.params, t.tf[0], outdir)
+        if quantiles:
+            quantile_report("thrust known", known)
+            quantile_report("known to 10 N", nav)
         if corridor and lincov and (nav_tau is not None or knowledge_tau is not None):
             # the same errors, time-varying: the bias a stationary process, the thrust estimate converging to the truth
             nkw = dict(guidance=gf, knowledge_sigma=10.0, nav_sigma=NAV_BIAS, nav_tau=nav_tau, knowledge_tau=knowledge_tau,
@@ -276,7 +318,7 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
                 print("%s: closed-loop 1-sigma altitude at burnout: linear +-%.2f m; Monte Carlo +-%.2f m" % (name, lc_.std[0, -1, 7], d_.history.std[0, -1, 7]))
     if lincov:
         lkw = dict(param_sigma=thrust, control_sigma=1e-3, **kw)
-        hkw = dict(dkw, history=True)
+        hkw = dict({k: v for k, v in dkw.items() if k not in ("quantiles", "limits")}, history=True)
         lincov_report("open loop", linear_corridor(res.params, t.blob, res.nt, **lkw), op if corridor else disperse_batch(res.params, t.blob, res.nt, **hkw),
                       res.params, t.tf[0], outdir)
         lincov_report("closed loop", linear_corridor(res.params, t.blob, res.nt, guidance=g, **lkw),
@@ -323,12 +365,15 @@ if __name__ == "__main__":
     ap.add_argument("--guide", action="store_true", help="trim, compute LQ feedback gains and fly 1024 dispersed samples open loop and closed loop; prints both 1-sigmas of the flown apsides")
     ap.add_argument("--feedforward", action="store_true", help="with --guide: also fly the same draws with the thrust feed-forward, once with the thrust known exactly and once known to 10 N (1-sigma) under a navigation bias of 1-sigma %g (scaled; %.1f m) on both positions and %g (scaled; %.1f cm/s) on both velocities" % (NAV_BIAS[0], NAV_BIAS[0] * ORBIT["periapsis"], NAV_BIAS[2], NAV_BIAS[2] * ORBIT["periapsis"] * 100))
     ap.add_argument("--corridor", action="store_true", help="with --disperse or --guide: reduce the samples at every node as well (disperse_batch(history=True)); prints, per flight flown, the widest 1-sigma altitude band, the lowest altitude any sample reached, the largest excursion of the angle beyond its bounds and the step with the most clipped commands, and writes corridor.png (with --guide: of the closed loop; the other flights as corridor_<flight>.png)")
+    ap.add_argument("--quantiles", action="store_true", help="with --disperse or --guide: select order statistics of the samples on the device (disperse_batch(quantiles=..., limits=...)); prints, per flight flown, the 0.135 / 50 / 99.865 %%%% points of the flown periapsis and apoapsis and the fraction of samples whose flown periapsis is below %.0f km, and with --corridor the 0.135 %%%% .. 99.865 %%%% altitude band at the node where it is widest" % (PERIAPSIS_LIMIT / 1000))
     ap.add_argument("--nav-tau", type=float, default=None, metavar="SECONDS", help="with --guide --feedforward --corridor --lincov: the navigation bias as a stationary first-order Gauss-Markov process of this correlation time; prints the sampled and the linear altitude band beside those of the frozen bias")
     ap.add_argument("--knowledge-tau", type=float, default=None, metavar="SECONDS", help="with --guide --feedforward --corridor --lincov: the 10 N error of the thrust estimate decays with this time constant")
     ap.add_argument("--lincov", action="store_true", help="with --guide: the linear covariance corridor (linear_corridor) of the open and the closed loop beside their Monte Carlo history; prints both 1-sigma altitude bands at the node where the sampled one is widest, and writes lincov.png (closed loop) and lincov_open_loop.png")
     a = ap.parse_args()
     if a.corridor and not (a.disperse or a.guide):
         ap.error("--corridor needs --disperse or --guide")
+    if a.quantiles and not (a.disperse or a.guide):
+        ap.error("--quantiles needs --disperse or --guide")
     if a.lincov and not a.guide:
         ap.error("--lincov needs --guide")
     if (a.nav_tau is not None or a.knowledge_tau is not None) and not (a.guide and a.feedforward and a.corridor and a.lincov):
@@ -346,9 +391,9 @@ if __name__ == "__main__":
     if a.trim:
         trim(model, a.scheme)
     if a.disperse:
-        disperse(model, a.scheme, corridor=a.corridor, outdir=figdir)
+        disperse(model, a.scheme, corridor=a.corridor, outdir=figdir, quantiles=a.quantiles)
     if a.guide:
         guide(model, a.scheme, feedforward=a.feedforward, corridor=a.corridor, outdir=figdir, lincov=a.lincov, nav_tau=a.nav_tau,
-              knowledge_tau=a.knowledge_tau)
+              knowledge_tau=a.knowledge_tau, quantiles=a.quantiles)
     if not a.no_plots:
         plots(model, variables, a.outdir)

@@ -657,6 +657,65 @@ int ascent_covariance_drifting_batch(const ascent_params *p, int64_t batch, cons
                                      int32_t node_stride, double *nominal_out, double *cov_out, double *jac_hist_out_or_null,
                                      int device_id, void *hip_stream_or_null, int ptr_is_device);
 
+/* Order statistics of sample rows: quantiles and limit counts, exact (nothing is summed in floating point), on caller arrays.
+ * values [quantities Q][groups G][samples][batch], element (q, i, s, problem) at (((q*G + i)*samples + s)*batch + problem): with
+ *   G = 1 the layout of samples_out, with Q = ASCENT_HISTORY_QUANTITIES and G = NJ that of hist_samples_out.
+ * Sample s of (group i, problem) is valid if its rows q < valid_quantities (V, 0 .. Q; 0: every sample) are finite there: V = 9,
+ *   G = 1 is the rule of stats_out, V = 10 that of hist_out.  n: the valid samples.  count_out [G][batch]: n.
+ * Per (q, i, problem) the values of the valid samples in ascending order x_(0) <= .. <= x_(n-1), NaN (rows q >= V only) last, as
+ *   np.sort orders them; which of -0 and +0 comes first is unspecified.
+ * probs: n_probs (1 .. 16) probabilities in [0, 1], ALWAYS a host array, read during the call.  For probability pi:
+ *   h = pi (double)(n - 1), lo = floor(h), g = h - lo, hi = min(lo + 1, n - 1),
+ *   quant_out[((j*Q + q)*G + i)*batch + problem] = x_(lo) + g (x_(hi) - x_(lo)) -- one subtraction, one multiplication, one
+ *   addition, each rounded once, never fused: numpy's default "linear" quantile up to the rounding of its interpolation.
+ *   n = 0: NaN.  n = 1: the sample.  pi = 0 the minimum, pi = 1 the maximum (g = 0).
+ * limits_or_null [n_limits (1 .. 16)][Q][batch], the same limit at every group; below_out [n_limits][Q][G][batch]: the number
+ *   of valid samples with value <= limit.  A NaN limit counts 0, +inf every valid sample that is not NaN.  Both or neither.
+ * A result depends on the set of valid values only: not on the batch size, the problem's place in it, the kind of pointer or
+ *   timing.
+ * Refuses (ASCENT_E_ARG, before the device is looked at, no array touched): a null values, probs, count_out or quant_out; Q, G
+ *   or batch < 1; V outside 0 .. Q; samples outside 1 .. ASCENT_DISPERSE_MAX_SAMPLES; n_probs outside 1 .. 16; a probability
+ *   outside [0, 1] or not finite; limits without below_out or the reverse; n_limits outside 1 .. 16 where limits are given.
+ * Host or device pointers; with device pointers and a stream the call only enqueues (q_sort: the rows of a tile of problems
+ *   sorted in LDS, up to 16384 samples; q_select: radix select, one workgroup per row, above that).  No device workspace. */
+int ascent_sample_quantiles(const double *values, int32_t quantities, int32_t groups, int32_t valid_quantities, int32_t samples,
+                            int64_t batch, const double *probs, int32_t n_probs, const double *limits_or_null, int32_t n_limits,
+                            double *count_out, double *quant_out, double *below_out_or_null, int device_id,
+                            void *hip_stream_or_null, int ptr_is_device);
+
+/* Monte Carlo dispersion with quantiles and limit counts: the flight of the existing calls, then ascent_sample_quantiles over
+ * its sample rows, which never leave the device.  Arguments p .. xi_drift_or_null: those of ascent_disperse_drifting_batch, every
+ * _or_null optional -- nav_phi null: the flight of ascent_disperse_history_batch (node_stride > 0) or of ascent_disperse_batch /
+ * _guided_batch / _navigated_batch (node_stride = 0: open loop without gain_u, navigated with any of ff_u .. sigma_nav); the
+ * "both or neither" and "only with gain_u" rules are theirs.  nav_phi needs node_stride > 0, as in the drifting call.
+ * node_stride: 0 no history, else 1 .. K.  stats_out [ASCENT_DISPERSE_STAT_ROWS][batch] and hist_out_or_null
+ *   [ASCENT_HISTORY_ROWS][NJ][batch] (with node_stride > 0, where it is required as in the parent call, and only then): the bits
+ *   of that call.
+ * probs, n_probs, n_limits: as in ascent_sample_quantiles.  limits_or_null [n_limits][ASCENT_GUIDED_SAMPLE_ROWS][batch] with
+ *   below_out_or_null of the same shape, hist_limits_or_null [n_limits][ASCENT_HISTORY_QUANTITIES][batch] with
+ *   hist_below_out_or_null [n_limits][ASCENT_HISTORY_QUANTITIES][NJ][batch]; quant_out [n_probs][ASCENT_GUIDED_SAMPLE_ROWS][batch];
+ *   hist_quant_out_or_null [n_probs][ASCENT_HISTORY_QUANTITIES][NJ][batch] (node_stride > 0 only; hist_below_out needs it).
+ * The end rows use the validity rule of stats_out (their count is its row 0), the history rows that of hist_out (row 0 of it).
+ *   Rows 9 .. 11 of quant_out are exactly 0 in the open-loop flight (NaN where no sample is valid).
+ * Refuses what the parent calls and ascent_sample_quantiles refuse of these arguments.
+ * Host or device pointers; with device pointers and a stream the call only enqueues: the parent's kernels with the sample rows
+ *   directed to the workspace, then the selection.  Device workspace: ascent_disperse_quantiles_bytes, the parent call's and
+ *   (ASCENT_GUIDED_SAMPLE_ROWS + ASCENT_HISTORY_QUANTITIES NJ) samples batch doubles; a problem's results do not depend on
+ *   the batch, so a caller short of memory splits the batch. */
+int ascent_disperse_quantiles_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                                    int32_t substeps, int32_t samples, const double *xi, const double *sigma,
+                                    const double *sigma_u_or_null, const double *gain_u_or_null, const double *gain_t_or_null,
+                                    const double *stretch_max_or_null, const double *ff_u_or_null, const double *ff_t_or_null,
+                                    const double *ff_know_or_null, const double *xi_nav_or_null, const double *sigma_nav_or_null,
+                                    const double *nav_phi_or_null, const double *nav_q_or_null, const double *xi_drift_or_null,
+                                    int32_t node_stride, double *stats_out, double *hist_out_or_null, const double *probs,
+                                    int32_t n_probs, const double *limits_or_null, const double *hist_limits_or_null,
+                                    int32_t n_limits, double *quant_out, double *below_out_or_null, double *hist_quant_out_or_null,
+                                    double *hist_below_out_or_null, int device_id, void *hip_stream_or_null, int ptr_is_device);
+/* The device workspace of that call in bytes; no device work.  Negative (ASCENT_E_ARG) for batch < 1, n_nodes outside
+ * 3 .. 65536, samples outside 1 .. ASCENT_DISPERSE_MAX_SAMPLES or node_stride outside 0 .. n_nodes - 1. */
+int64_t ascent_disperse_quantiles_bytes(int64_t batch, int32_t n_nodes, int32_t samples, int32_t node_stride);
+
 /* Generic bordered block-tridiagonal solve (parity surface of the linear algebra):
  *     [ T   B ] [x]   [r]        T: n_nodes x n_nodes blocks of size bs (<= 16): diag[i] on the diagonal, lower[i] = block
  *     [ B'  d ] [y] = [s]           (i, i-1) (lower[0] ignored), upper[i] = block (i, i+1) (upper[n-1] ignored);

@@ -43,6 +43,7 @@
 #include "ascent_disperse.hpp"
 #include "ascent_guide.hpp"
 #include "ascent_lincov.hpp"
+#include "ascent_quantile.hpp"
 
 using namespace ascent;
 
@@ -876,11 +877,76 @@ int check_drift(const double *nav_phi, const double *nav_q, const double *xi_dri
   return 0;
 }
 
+// What ascent_sample_quantiles and ascent_disperse_quantiles_batch refuse of the arguments they share
+int check_probs(const double *probs, int32_t n_probs) {
+  if (!probs) { snprintf(g_err, sizeof g_err, "null probs"); return ASCENT_E_ARG; }
+  if (n_probs < 1 || n_probs > QUANTILE_MAX_PROBS) { snprintf(g_err, sizeof g_err, "n_probs out of range (1 .. %d)", QUANTILE_MAX_PROBS); return ASCENT_E_ARG; }
+  for (int j = 0; j < n_probs; j++)
+    if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) { snprintf(g_err, sizeof g_err, "probability %d outside [0, 1] or not finite", j); return ASCENT_E_ARG; }
+  return 0;
+}
+int check_limits(const double *limits, const double *below, int32_t n_limits, const char *lname, const char *bname) {
+  if ((limits != nullptr) != (below != nullptr)) { snprintf(g_err, sizeof g_err, "%s and %s come together", lname, bname); return ASCENT_E_ARG; }
+  if (limits && (n_limits < 1 || n_limits > QUANTILE_MAX_LIMITS)) { snprintf(g_err, sizeof g_err, "n_limits out of range (1 .. %d)", QUANTILE_MAX_LIMITS); return ASCENT_E_ARG; }
+  return 0;
+}
+
+// The sample rows of ascent_disperse_quantiles_batch in the analysis workspace, behind what the flight needs: the twelve end
+// rows, then the ten quantities at the NJ history nodes
+size_t quantile_scratch_bytes(int K, int64_t batch, int32_t samples, int32_t node_stride) {
+  const size_t nj = node_stride > 0 ? (size_t)history_nodes(K, node_stride) : 0;
+  return (ASCENT_GUIDED_SAMPLE_ROWS + ASCENT_HISTORY_QUANTITIES * nj) * (size_t)samples * (size_t)batch * sizeof(double);
+}
+
+// The selection of ascent_disperse_quantiles_batch: the caller's pointers, staged by quantiles_behind
+struct QuantileRequest {
+  const double *probs;
+  int n_probs;
+  const double *limits, *hist_limits;
+  int n_limits;
+  double *quant, *below, *hist_quant, *hist_below;
+};
+
+// disperse_call's last step with a QuantileRequest: the flight's kernels with the sample rows directed to the workspace, then the
+// selection over them (the counts are stats_out's and hist_out's rows 0 and are not written again; nothing is allocated, so with
+// device pointers the call only enqueues).  The open-loop flight without history writes nine rows; the other three are zeroed here.
+int quantiles_behind(BlobCall &b, DisperseKind kind, int substeps, int samples, DisperseIO io, bool history, size_t flight_bytes,
+                     const QuantileRequest &qr) {
+  Staging &st = b.st;
+  const size_t B = (size_t)b.c.batch, S = (size_t)samples, NJ = history ? (size_t)history_nodes(b.K, io.node_stride) : 0;
+  const size_t end = ASCENT_GUIDED_SAMPLE_ROWS * S * B;
+  double *rows = b.ws + flight_bytes / sizeof(double);
+  io.samples_out = rows;
+  io.hist_samples = history && qr.hist_quant ? rows + end : nullptr;
+  QuantileIO e{}, h{};
+  e.values = rows; e.Q = ASCENT_GUIDED_SAMPLE_ROWS; e.G = 1; e.V = ASCENT_DISPERSE_ROWS; e.samples = samples; e.batch = b.c.batch;
+  e.n_probs = qr.n_probs;
+  for (int j = 0; j < qr.n_probs; j++) e.probs[j] = qr.probs[j];
+  h = e;
+  e.limits = st.in(qr.limits, (size_t)qr.n_limits * e.Q * B); e.n_limits = qr.n_limits;
+  e.quant = st.out(qr.quant, (size_t)qr.n_probs * e.Q * B);
+  e.below = st.out(qr.below, (size_t)qr.n_limits * e.Q * B);
+  if (io.hist_samples) {
+    h.values = io.hist_samples; h.Q = ASCENT_HISTORY_QUANTITIES; h.G = (int)NJ; h.V = ASCENT_HISTORY_QUANTITIES;
+    h.limits = st.in(qr.hist_limits, (size_t)qr.n_limits * h.Q * B); h.n_limits = qr.n_limits;
+    h.quant = st.out(qr.hist_quant, (size_t)qr.n_probs * h.Q * NJ * B);
+    h.below = st.out(qr.hist_below, (size_t)qr.n_limits * h.Q * NJ * B);
+  }
+  int rc = st.failed();
+  if (rc) return rc;
+  if (kind == DISPERSE_OPEN && !history)
+    HIPCHK(hipMemsetAsync(rows + ASCENT_DISPERSE_ROWS * S * B, 0, (ASCENT_GUIDED_SAMPLE_ROWS - ASCENT_DISPERSE_ROWS) * S * B * sizeof(double), b.c.stream));
+  if ((rc = disperse_run(b.c, kind, substeps, samples, io, b.ws)) || (rc = quantile_run(e, b.c.stream, g_err, sizeof g_err))) return rc;
+  if (io.hist_samples && (rc = quantile_run(h, b.c.stream, g_err, sizeof g_err))) return rc;
+  return b.close();
+}
+
 // ascent_disperse_batch, ascent_disperse_guided_batch and ascent_disperse_navigated_batch: io holds the caller's pointers.
 // history: ascent_disperse_history_batch, the kind picked from gain_u by the entry point; its own refusals stand after the
 // refusals the three share, each of which keeps its place and its text.
 int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, int32_t samples, DisperseKind kind,
-                  DisperseIO io, int device_id, void *stream_, int ptr_is_device, bool history = false, bool drifting = false) {
+                  DisperseIO io, int device_id, void *stream_, int ptr_is_device, bool history = false, bool drifting = false,
+                  const QuantileRequest *qr = nullptr) {
   BlobCall b(p, batch, o, io.blob, stream_, ptr_is_device);
   int rc = b.options();
   if (rc) return rc;
@@ -896,7 +962,8 @@ int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, i
   }
   if ((rc = b.solvable())) return rc;
   if (drifting && (rc = check_drift(io.nav_phi, io.nav_q, io.xi_drift, true, io.gain_u, batch, ptr_is_device))) return rc;
-  if ((rc = b.open(device_id, disperse_ws_bytes(o->n_nodes - 1, (long)batch, samples, history ? io.node_stride : 0)))) return rc;
+  const size_t flight_bytes = disperse_ws_bytes(o->n_nodes - 1, (long)batch, samples, history ? io.node_stride : 0);
+  if ((rc = b.open(device_id, flight_bytes + (qr ? quantile_scratch_bytes(o->n_nodes - 1, batch, samples, history ? io.node_stride : 0) : 0)))) return rc;
   Staging &st = b.st;
   const size_t K = (size_t)b.K, B = (size_t)batch, S = (size_t)samples;
   io.blob = b.blob;
@@ -921,6 +988,7 @@ int disperse_call(const ascent_params *p, int64_t batch, const ascent_opts *o, i
     io.hist = st.out(io.hist, ASCENT_HISTORY_ROWS * NJ * B);
     io.hist_samples = st.out(io.hist_samples, ASCENT_HISTORY_QUANTITIES * NJ * S * B);
   }
+  if (qr) return quantiles_behind(b, kind, substeps, samples, io, history, flight_bytes, *qr);
   if ((rc = b.st.failed()) || (rc = disperse_run(b.c, kind, substeps, samples, io, b.ws))) return rc;
   return b.close();
 }
@@ -1154,6 +1222,79 @@ int ascent_covariance_drifting_batch(const ascent_params *p, int64_t batch, cons
   io.nav_phi = nav_phi; io.nav_q = nav_q;
   io.node_stride = node_stride; io.nominal = nominal_out; io.cov = cov_out; io.jac = jac_hist_out;
   return lincov_call(p, batch, o, substeps, io, device_id, stream_, ptr_is_device, true);
+}
+
+int ascent_sample_quantiles(const double *values, int32_t quantities, int32_t groups, int32_t valid_quantities, int32_t samples,
+                            int64_t batch, const double *probs, int32_t n_probs, const double *limits_or_null, int32_t n_limits,
+                            double *count_out, double *quant_out, double *below_out_or_null, int device_id, void *stream_,
+                            int ptr_is_device) {
+  if (!values || !count_out || !quant_out) { snprintf(g_err, sizeof g_err, "null values, count_out or quant_out"); return ASCENT_E_ARG; }
+  if (quantities < 1 || groups < 1 || batch < 1) { snprintf(g_err, sizeof g_err, "quantities, groups and batch must be at least 1"); return ASCENT_E_ARG; }
+  if (valid_quantities < 0 || valid_quantities > quantities) { snprintf(g_err, sizeof g_err, "valid_quantities out of range (0 .. quantities = %d)", quantities); return ASCENT_E_ARG; }
+  int rc = check_samples(samples);
+  if (rc || (rc = check_probs(probs, n_probs)) || (rc = check_limits(limits_or_null, below_out_or_null, n_limits, "limits", "below_out"))) return rc;
+  if ((rc = check_device(device_id))) return rc;
+  std::lock_guard<std::mutex> lock(g_mu[device_id]);
+  HIPCHK(hipSetDevice(device_id));
+  hipStream_t stream = (hipStream_t)stream_;
+  Staging st(stream, ptr_is_device);
+  const size_t Q = (size_t)quantities, G = (size_t)groups, B = (size_t)batch, NL = limits_or_null ? (size_t)n_limits : 0;
+  QuantileIO io{};
+  io.values = st.in(values, Q * G * (size_t)samples * B);
+  io.Q = quantities; io.G = groups; io.V = valid_quantities; io.samples = samples; io.batch = (long)batch;
+  io.n_probs = n_probs;
+  for (int j = 0; j < n_probs; j++) io.probs[j] = probs[j];
+  io.limits = st.in(limits_or_null, NL * Q * B); io.n_limits = (int)NL;
+  io.count = st.out(count_out, G * B);
+  io.quant = st.out(quant_out, (size_t)n_probs * Q * G * B);
+  io.below = st.out(below_out_or_null, NL * Q * G * B);
+  if ((rc = st.failed()) || (rc = quantile_run(io, stream, g_err, sizeof g_err))) return rc;
+  return st.finish();
+}
+
+int64_t ascent_disperse_quantiles_bytes(int64_t batch, int32_t n_nodes, int32_t samples, int32_t node_stride) {
+  if (batch < 1 || n_nodes < 3 || n_nodes > 65536 || samples < 1 || samples > ASCENT_DISPERSE_MAX_SAMPLES || node_stride < 0 ||
+      node_stride > n_nodes - 1)
+    return ASCENT_E_ARG;
+  return (int64_t)(disperse_ws_bytes(n_nodes - 1, (long)batch, samples, node_stride) + quantile_scratch_bytes(n_nodes - 1, batch, samples, node_stride));
+}
+
+int ascent_disperse_quantiles_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                                    int32_t samples, const double *xi, const double *sigma, const double *sigma_u, const double *gain_u,
+                                    const double *gain_t, const double *stretch_max, const double *ff_u, const double *ff_t,
+                                    const double *ff_know, const double *xi_nav, const double *sigma_nav, const double *nav_phi,
+                                    const double *nav_q, const double *xi_drift, int32_t node_stride, double *stats_out,
+                                    double *hist_out_or_null, const double *probs, int32_t n_probs, const double *limits_or_null,
+                                    const double *hist_limits_or_null, int32_t n_limits, double *quant_out, double *below_out_or_null,
+                                    double *hist_quant_out_or_null, double *hist_below_out_or_null, int device_id, void *stream_,
+                                    int ptr_is_device) {
+  int rc = check_probs(probs, n_probs);
+  if (rc) return rc;
+  if (!quant_out) { snprintf(g_err, sizeof g_err, "null quant_out"); return ASCENT_E_ARG; }
+  if ((rc = check_limits(limits_or_null, below_out_or_null, n_limits, "limits", "below_out")) ||
+      (rc = check_limits(hist_limits_or_null, hist_below_out_or_null, n_limits, "hist_limits", "hist_below_out")))
+    return rc;
+  if (node_stride == 0 && (hist_out_or_null || hist_limits_or_null || hist_quant_out_or_null || hist_below_out_or_null)) {
+    snprintf(g_err, sizeof g_err, "hist_out, hist_limits, hist_quant_out and hist_below_out need node_stride > 0");
+    return ASCENT_E_ARG;
+  }
+  if (hist_below_out_or_null && !hist_quant_out_or_null) { snprintf(g_err, sizeof g_err, "hist_below_out needs hist_quant_out"); return ASCENT_E_ARG; }
+  const bool drifting = nav_phi || nav_q || xi_drift, history = node_stride != 0 || drifting;      // (node_stride 0 with them: refused as the drifting call refuses it)
+  const bool nav = ff_u || ff_t || ff_know || xi_nav || sigma_nav;
+  DisperseIO io{};
+  io.blob = sol_blob; io.xi = xi; io.sigma = sigma; io.sigma_u = sigma_u;
+  io.gain_u = gain_u; io.gain_t = gain_t; io.stretch_max = stretch_max;
+  io.ff_u = ff_u; io.ff_t = ff_t; io.ff_know = ff_know; io.xi_nav = xi_nav; io.sigma_nav = sigma_nav;
+  io.nav_phi = nav_phi; io.nav_q = nav_q; io.xi_drift = xi_drift;
+  io.stats = stats_out;
+  io.node_stride = node_stride; io.hist = hist_out_or_null;
+  const QuantileRequest qr{probs, n_probs, limits_or_null, hist_limits_or_null, n_limits, quant_out, below_out_or_null, hist_quant_out_or_null,
+                           hist_below_out_or_null};
+  DisperseKind kind = DISPERSE_OPEN;
+  if (history) kind = gain_u ? DISPERSE_NAVIGATED : DISPERSE_OPEN;
+  else if (gain_u) kind = nav ? DISPERSE_NAVIGATED : DISPERSE_GUIDED;
+  else if (gain_t || stretch_max || nav) { snprintf(g_err, sizeof g_err, "gain_t, stretch_max, ff_u, ff_t, ff_know, xi_nav and sigma_nav need gain_u"); return ASCENT_E_ARG; }
+  return disperse_call(p, batch, o, substeps, samples, kind, io, device_id, stream_, ptr_is_device, history, drifting, &qr);
 }
 
 int ascent_kkt_step(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *iterate,

@@ -156,6 +156,11 @@ class DispersionResult:
     effort: np.ndarray | None = None    # (batch, samples, 3) guided flights with keep_samples: EFFORT_ROWS
     xi_nav: np.ndarray | None = None    # (8, samples) the navigation draws (ascent_disperse_navigated_batch), shared by every problem
     nav_sigma: np.ndarray | None = None     # (batch, 8): 7 state-knowledge biases (scaled units), the error of theta-hat
+    quantile_probs: np.ndarray | None = None    # (n_probs,) disperse_batch(quantiles=...): the probabilities of the quantile rows
+    quantiles: np.ndarray | None = None         # (batch, n_probs, 9) numpy's "linear" quantiles of the nine end quantities over the valid samples
+    effort_quantiles: np.ndarray | None = None  # (batch, n_probs, 3) those of EFFORT_ROWS, guided flights
+    below: np.ndarray | None = None             # (batch, n_limits, 9) disperse_batch(limits=...): valid samples at or below the limit; 0 where it is NaN
+    effort_below: np.ndarray | None = None      # (batch, n_limits, 3)
     xi_drift: np.ndarray | None = None      # (8, K, samples) the driving draws of the drifting knowledge errors (nav_tau, knowledge_tau)
     nav_phi: np.ndarray | None = None       # (batch, 8) their per-step decay exp(-dt / tau); 1 where frozen
     nav_q: np.ndarray | None = None         # (batch, 8) their per-step drive steady * sqrt(1 - phi^2); 0 where frozen
@@ -207,6 +212,8 @@ class DispersionHistory:
     max: np.ndarray                 # (batch, NJ, 10)
     clipped: np.ndarray             # (batch, NJ) valid samples whose command of the step was clipped; 0 in open loop
     samples: np.ndarray | None      # (batch, samples, NJ, 10) every sample's quantities (keep_history_samples=True)
+    quantiles: np.ndarray | None = None     # (batch, NJ, n_probs, 10) disperse_batch(quantiles=...), over the samples valid at the node
+    below: np.ndarray | None = None         # (batch, NJ, n_limits, 10) disperse_batch(history_limits=...): valid samples at or below the limit
 
     @property
     def std(self) -> np.ndarray:
@@ -526,6 +533,38 @@ def trim_batch(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, t
     return TrimResult(out, np.ascontiguousarray(summ.T), nt)
 
 
+def _history_stride(history, keep_history_samples, K):
+    """the node stride of disperse_batch's `history`: 0 for none, 1 for True, else the stride, checked"""
+    if history is False or history is None:
+        if keep_history_samples:
+            raise ValueError("keep_history_samples needs history")
+        return 0
+    stride = 1 if history is True else int(history)
+    if not 1 <= stride <= K:
+        raise ValueError(f"history: the node stride must be in 1 .. K = {K}")
+    return stride
+
+
+def _dispersion_draws(xi, seed, samples, K):
+    """xi (24 + K, samples) of disperse_batch, contiguous and checked; None draws it from the seed"""
+    if xi is None:
+        xi = np.random.default_rng(seed).standard_normal((24 + K, int(samples)))
+    xi = np.ascontiguousarray(xi, dtype=np.float64)
+    if xi.ndim != 2 or xi.shape[0] != 24 + K:
+        raise ValueError(f"xi must have shape (24 + K, samples) = ({24 + K}, samples)")
+    return xi
+
+
+def _drift_draws(xi_drift, drift_seed, K, S):
+    """xi_drift (8, K, samples) of the drifting flight, contiguous and checked; None draws it from the seed"""
+    if xi_drift is None:
+        xi_drift = np.random.default_rng(drift_seed).standard_normal((8, K, S))
+    xi_drift = np.ascontiguousarray(xi_drift, dtype=np.float64)
+    if xi_drift.shape != (8, K, S):
+        raise ValueError(f"xi_drift must have shape (8, K, samples) = {(8, K, S)}")
+    return xi_drift
+
+
 def _dispersion_sigmas(z0_sigma, param_sigma, tf_sigma, control_sigma, K, B):
     """The sigma arguments of disperse_batch and linear_corridor, broadcast: -> z0 (B, 7), params (B, 16), tf (B, 1), controls
     (B, K), and the arrays the C ABI takes: sigma [24][B], sigma_u [K][B] or None where control_sigma is None"""
@@ -635,7 +674,7 @@ def _dispersion_result(stats, smp, effort, xi, sigmas, xi_nav, nav_s, *drift, hi
                             _cov_from_upper(st[:, 19:64]), np.ascontiguousarray(st[:, 64:73]), np.ascontiguousarray(st[:, 73:82]),
                             None if smp is None else np.ascontiguousarray(smp[:9].transpose(2, 1, 0)), xi, zs, ps, ts[:, 0].copy(), us,
                             None if smp is None or not effort else np.ascontiguousarray(smp[9:].transpose(2, 1, 0)),
-                            xi_nav if nav_s is not None else None, nav_s, *drift, history=history)
+                            xi_nav if nav_s is not None else None, nav_s, **dict(zip(("xi_drift", "nav_phi", "nav_q"), drift)), history=history)
 
 
 LINCOV_COLS = tuple(f"z0_{n}" for n in HISTORY_ROWS[:7]) + PARAM_FIELDS + ("tf",) + tuple(f"nav_{n}" for n in HISTORY_ROWS[:7]) + (
@@ -710,7 +749,8 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
                    move_penalty: bool = False, substeps: int = 0, device: int = 0, guidance: GuidanceResult | None = None,
                    nav_sigma=None, knowledge_sigma=None, xi_nav=None, nav_seed: int = 1, history=False,
                    keep_history_samples: bool = False, nav_tau=None, knowledge_tau=None, nav_steady_sigma=None,
-                   knowledge_steady_sigma=None, xi_drift=None, drift_seed: int = 2) -> DispersionResult:
+                   knowledge_steady_sigma=None, xi_drift=None, drift_seed: int = 2, quantiles=None, limits=None, history_limits=None,
+                   max_workspace_bytes: int = 2**31) -> DispersionResult:
     """Monte Carlo dispersion (include/ascent.h: ascent_disperse_batch): every blob's control flown `samples` times on the
     device as fly_batch flies it, with the initial state, the 16 parameter fields, t_f and every control perturbed by
     sigma * xi, and the nine end quantities reduced on the device to count, mean, covariance and extrema.  The blob is shared
@@ -737,20 +777,32 @@ def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, c
     sqrt(1 - phi^2); None: the channel's initial sigma (a stationary process), 0: pure decay.  xi_drift (8, K, samples): the
     driving draws, None draws np.random.default_rng(drift_seed).standard_normal((8, K, samples)).  The result keeps xi_drift,
     nav_phi and nav_q.  Without `history` the call runs with stride K and the result's history is None.  Without these keywords
-    the calls are exactly those above."""
+    the calls are exactly those above.
+    quantiles: a sequence of 1 .. 16 probabilities in [0, 1]; limits (n_limits, 12) or (batch, n_limits, 12), n_limits 1 .. 16, in
+    the units of the nine end quantities and EFFORT_ROWS, NaN: no limit here; history_limits likewise with the 10 columns of
+    HISTORY_ROWS (needs history, and as many limits as `limits` where both are given).  The flight runs through
+    ascent_disperse_quantiles_batch, which selects behind it on the device: the result gains quantile_probs, quantiles,
+    effort_quantiles (guided flights), below and effort_below, its history quantiles and below -- order statistics over the valid
+    samples, exact (include/ascent.h: ascent_sample_quantiles); everything else has the bits of the call without the keywords.
+    Limits without quantiles report the median.  The call keeps (12 + 10 NJ) samples batch doubles on the device: where
+    ascent_disperse_quantiles_bytes exceeds max_workspace_bytes the batch is flown in runs of consecutive problems that fit
+    (quantile_chunks; a problem's rows do not depend on the batch), ValueError where one problem does not.  keep_samples and
+    keep_history_samples with these keywords fly the flight a second time through the calls above for the samples.
+    The analysis workspace of a device only grows: after such a call up to max_workspace_bytes stay claimed on the device for
+    the life of the process.  Without the three keywords the calls are exactly those above."""
     L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
-    stride = 0
-    if history is not False and history is not None:
-        stride = 1 if history is True else int(history)
-        if not 1 <= stride <= K:
-            raise ValueError(f"history: the node stride must be in 1 .. K = {K}")
-    elif keep_history_samples:
-        raise ValueError("keep_history_samples needs history")
-    if xi is None:
-        xi = np.random.default_rng(seed).standard_normal((24 + K, int(samples)))
-    xi = np.ascontiguousarray(xi, dtype=np.float64)
-    if xi.ndim != 2 or xi.shape[0] != 24 + K:
-        raise ValueError(f"xi must have shape (24 + K, samples) = ({24 + K}, samples)")
+    if quantiles is not None or limits is not None or history_limits is not None:
+        if history_limits is not None and (history is False or history is None):
+            raise ValueError("history_limits needs history")
+        kw = dict(param_sigma=param_sigma, control_sigma=control_sigma, tf_sigma=tf_sigma, z0_sigma=z0_sigma, samples=samples, seed=seed,
+                  xi=xi, scheme=scheme, formulation=formulation, terminal=terminal, move_penalty=move_penalty, substeps=substeps,
+                  device=device, guidance=guidance, nav_sigma=nav_sigma, knowledge_sigma=knowledge_sigma, xi_nav=xi_nav,
+                  nav_seed=nav_seed, history=history, nav_tau=nav_tau, knowledge_tau=knowledge_tau, nav_steady_sigma=nav_steady_sigma,
+                  knowledge_steady_sigma=knowledge_steady_sigma, xi_drift=xi_drift, drift_seed=drift_seed)
+        return _disperse_quantiles(params, sol_blob, nt, kw, keep_samples, keep_history_samples, quantiles, limits, history_limits,
+                                   int(max_workspace_bytes))
+    stride = _history_stride(history, keep_history_samples, K)
+    xi = _dispersion_draws(xi, seed, samples, K)
     S = xi.shape[1]
     zs, ps, ts, us, sig, sig_u = _dispersion_sigmas(z0_sigma, param_sigma, tf_sigma, control_sigma, K, B)
     ffu = getattr(guidance, "ff_u", None)
@@ -818,11 +870,7 @@ def _disperse_drifting(L, P, B, K, blob, o, substeps, device, xi, sigmas, guidan
                                                       (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma), S, xi_nav, nav_seed)
     if phi is None:
         raise ValueError("xi_drift needs nav_tau or knowledge_tau")
-    if xi_drift is None:
-        xi_drift = np.random.default_rng(drift_seed).standard_normal((8, K, S))
-    xi_drift = np.ascontiguousarray(xi_drift, dtype=np.float64)
-    if xi_drift.shape != (8, K, S):
-        raise ValueError(f"xi_drift must have shape (8, K, samples) = {(8, K, S)}")
+    xi_drift = _drift_draws(xi_drift, drift_seed, K, S)
     call_stride = stride if stride else K
     NJ = len(history_nodes(K, call_stride))
     stats = np.empty((82, B))
@@ -835,6 +883,167 @@ def _disperse_drifting(L, P, B, K, blob, o, substeps, device, xi, sigmas, guidan
                                                 call_stride, _ptr(stats), _ptr(smp), _ptr(hist), _ptr(hsmp), device, None, 0))
     return _dispersion_result(stats, smp, True, xi, sigmas, xi_nav, nav_s, xi_drift, phi, q,
                               history=_history_result(K, stride, hist, hsmp) if stride else None)
+
+
+def quantile_chunks(batch: int, bytes_of, max_bytes: int) -> list:
+    """Runs (start, stop) of consecutive problems that tile range(batch), each with bytes_of(stop - start) <= max_bytes; bytes_of
+    does not decrease with the number of problems.  The runs are as long as fits and equal but for the last.  ValueError where
+    one problem does not fit."""
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    one = int(bytes_of(1))
+    if one > max_bytes:
+        raise ValueError(f"one problem needs a device workspace of {one} bytes, more than max_workspace_bytes = {max_bytes}")
+    lo, hi = 1, batch      # bytes_of(lo) fits
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if int(bytes_of(mid)) <= max_bytes:
+            lo = mid
+        else:
+            hi = mid - 1
+    return [(a, min(a + lo, batch)) for a in range(0, batch, lo)]
+
+
+def _quantile_probs(quantiles):
+    probs = np.ascontiguousarray([0.5] if quantiles is None else quantiles, dtype=np.float64).reshape(-1)
+    if not 1 <= probs.size <= 16:
+        raise ValueError("quantiles: 1 .. 16 probabilities")
+    if not np.all((probs >= 0.0) & (probs <= 1.0)):
+        raise ValueError("quantiles: every probability must be in [0, 1]")
+    return probs
+
+
+def _limit_rows(limits, cols, B, what):
+    """limits (n_limits, cols) or (batch, n_limits, cols) -> [n_limits][cols][batch] as the C ABI takes them, or None"""
+    if limits is None:
+        return None
+    a = np.asarray(limits, dtype=np.float64)
+    if a.ndim == 2:
+        a = np.broadcast_to(a[None], (B,) + a.shape)
+    if a.ndim != 3 or a.shape[0] != B or a.shape[2] != cols or not 1 <= a.shape[1] <= 16:
+        raise ValueError(f"{what} must have shape (n_limits, {cols}) or (batch, n_limits, {cols}) with 1 .. 16 limits")
+    return np.ascontiguousarray(a.transpose(1, 2, 0))
+
+
+def _disperse_quantiles(params, sol_blob, nt, kw, keep_samples, keep_history_samples, quantiles, limits, history_limits, max_bytes):
+    """disperse_batch with quantiles / limits / history_limits: ascent_disperse_quantiles_batch on runs of problems that fit"""
+    L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, kw["scheme"], kw["formulation"], kw["terminal"], kw["move_penalty"])
+    guidance, device, substeps = kw["guidance"], kw["device"], int(kw["substeps"])
+    stride = _history_stride(kw["history"], keep_history_samples, K)
+    probs = _quantile_probs(quantiles)
+    lim, hlim = _limit_rows(limits, 12, B, "limits"), _limit_rows(history_limits, 10, B, "history_limits")
+    if lim is not None and hlim is not None and lim.shape[0] != hlim.shape[0]:
+        raise ValueError("limits and history_limits must hold the same number of limits")
+    NL = lim.shape[0] if lim is not None else hlim.shape[0] if hlim is not None else 0
+    xi = _dispersion_draws(kw["xi"], kw["seed"], kw["samples"], K)
+    S = xi.shape[1]
+    sigmas = _dispersion_sigmas(kw["z0_sigma"], kw["param_sigma"], kw["tf_sigma"], kw["control_sigma"], K, B)
+    sig, sig_u = sigmas[4:]
+    drift = (kw["nav_tau"], kw["knowledge_tau"], kw["nav_steady_sigma"], kw["knowledge_steady_sigma"])
+    xi_drift, xi_nav = kw["xi_drift"], kw["xi_nav"]
+    drifting = any(v is not None for v in drift + (xi_drift,))
+    navigated = getattr(guidance, "ff_u", None) is not None or kw["nav_sigma"] is not None or kw["knowledge_sigma"] is not None
+    if guidance is None and navigated:
+        raise ValueError("nav_sigma and knowledge_sigma need guidance")
+    if guidance is None and drifting:
+        raise ValueError("nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma and xi_drift need guidance")
+    law, sn, nav_s, phi, q = [None] * 6, None, None, None, None
+    if guidance is not None:
+        law, sn, nav_s, xi_nav, phi, q = _guidance_arrays(P, blob, K, B, guidance, kw["nav_sigma"], kw["knowledge_sigma"],
+                                                          drift if drifting else (None,) * 4, S, xi_nav, kw["nav_seed"])
+    else:
+        xi_nav = None
+    phi_c = q_c = None
+    if drifting:
+        if phi is None:
+            raise ValueError("xi_drift needs nav_tau or knowledge_tau")
+        xi_drift = _drift_draws(xi_drift, kw["drift_seed"], K, S)
+        phi_c, q_c = np.ascontiguousarray(phi.T), np.ascontiguousarray(q.T)
+    call_stride = stride if stride or not drifting else K      # (the drifting call has no form without history)
+    NJ = len(history_nodes(K, call_stride)) if call_stride else 0
+    NP = probs.size
+
+    def bytes_of(n):
+        return L.ascent_disperse_quantiles_bytes(n, nt, S, call_stride)
+    if bytes_of(1) < 0:
+        _lib.check(int(bytes_of(1)))
+    stats, hist = np.empty((82, B)), np.empty((52, NJ, B)) if call_stride else None
+    quant, below = np.empty((NP, 12, B)), np.empty((NL, 12, B)) if lim is not None else None
+    hquant = np.empty((NP, 10, NJ, B)) if stride else None
+    hbelow = np.empty((NL, 10, NJ, B)) if hlim is not None else None
+    per_problem = [blob, sig, sig_u, *law, sn, phi_c, q_c, lim, hlim]
+    outs = [stats, hist, quant, below, hquant, hbelow]
+    for a, b in quantile_chunks(B, bytes_of, max_bytes):
+        whole = a == 0 and b == B
+        cut = [x if x is None or whole else np.ascontiguousarray(x[..., a:b]) for x in per_problem]
+        part = [x if x is None or whole else np.empty(x.shape[:-1] + (b - a,)) for x in outs]
+        cb, cs, csu, *claw = cut[:9]
+        csn, cphi, cq, clim, chlim = cut[9:]
+        _lib.check(L.ascent_disperse_quantiles_batch(
+            _ptr(np.ascontiguousarray(P[a:b])), b - a, C.byref(o), _ptr(cb), substeps, S, _ptr(xi), _ptr(cs), _ptr(csu),
+            *[_ptr(x) for x in claw], _ptr(xi_nav), _ptr(csn), _ptr(cphi), _ptr(cq), _ptr(xi_drift if drifting else None), call_stride,
+            _ptr(part[0]), _ptr(part[1]), _ptr(probs), NP, _ptr(clim), _ptr(chlim), NL, _ptr(part[2]), _ptr(part[3]), _ptr(part[4]),
+            _ptr(part[5]), device, None, 0))
+        if not whole:
+            for x, y in zip(outs, part):
+                if x is not None:
+                    x[..., a:b] = y
+    if keep_samples or keep_history_samples:      # the samples themselves: the calls without the keywords
+        res = disperse_batch(params, sol_blob, nt, keep_samples=keep_samples, keep_history_samples=keep_history_samples,
+                             **{**kw, "xi": xi, "xi_nav": xi_nav, "xi_drift": xi_drift if drifting else None})
+    else:
+        tail = (xi_drift, phi, q) if drifting else ()
+        res = _dispersion_result(stats, None, guidance is not None, xi, sigmas, xi_nav, nav_s, *tail,
+                                 history=_history_result(K, stride, hist, None) if stride else None)
+    res.quantile_probs = probs
+    res.quantiles = np.ascontiguousarray(quant[:, :9].transpose(2, 0, 1))
+    if guidance is not None:
+        res.effort_quantiles = np.ascontiguousarray(quant[:, 9:].transpose(2, 0, 1))
+    if below is not None:
+        res.below = np.ascontiguousarray(below[:, :9].transpose(2, 0, 1)).astype(np.int64)
+        if guidance is not None:
+            res.effort_below = np.ascontiguousarray(below[:, 9:].transpose(2, 0, 1)).astype(np.int64)
+    if stride:
+        res.history.quantiles = np.ascontiguousarray(hquant.transpose(3, 2, 0, 1))
+        if hbelow is not None:
+            res.history.below = np.ascontiguousarray(hbelow.transpose(3, 2, 0, 1)).astype(np.int64)
+    return res
+
+
+def sample_quantiles(values, probs, valid_quantities: int, limits=None, device: int = 0):
+    """Order statistics of sample rows on the device (include/ascent.h: ascent_sample_quantiles).  values (Q, G, samples, batch) or
+    (Q, samples, batch), the layouts of the C ABI's hist_samples_out and samples_out; a sample is valid where its first
+    valid_quantities rows are finite.  probs: 1 .. 16 probabilities; limits (n_limits, Q) or (n_limits, Q, batch), None: no counts.
+    Returns (count, quantiles, below): count (G, batch) int64 the valid samples, quantiles (n_probs, Q, G, batch) numpy's "linear"
+    quantiles over them (NaN where there is none), below (n_limits, Q, G, batch) int64 the valid samples at or below each limit or
+    None; without the G axis where values came without it."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    flat = v.ndim == 3
+    if flat:
+        v = v[:, None]
+    if v.ndim != 4 or 0 in v.shape:
+        raise ValueError("values must have shape (Q, G, samples, batch) or (Q, samples, batch)")
+    Q, G, S, B = v.shape
+    probs = _quantile_probs(probs)
+    lim = None
+    if limits is not None:
+        lim = np.asarray(limits, dtype=np.float64)
+        if lim.ndim == 2:
+            lim = np.broadcast_to(lim[:, :, None], lim.shape + (B,))
+        if lim.ndim != 3 or lim.shape[1:] != (Q, B) or not 1 <= lim.shape[0] <= 16:
+            raise ValueError("limits must have shape (n_limits, Q) or (n_limits, Q, batch) with 1 .. 16 limits")
+        lim = np.ascontiguousarray(lim)
+    NL = 0 if lim is None else lim.shape[0]
+    count, quant = np.empty((G, B)), np.empty((probs.size, Q, G, B))
+    below = np.empty((NL, Q, G, B)) if lim is not None else None
+    _lib.check(_lib.load().ascent_sample_quantiles(_ptr(v), Q, G, int(valid_quantities), S, B, _ptr(probs), probs.size, _ptr(lim), NL,
+                                                   _ptr(count), _ptr(quant), _ptr(below), device, None, 0))
+    count = count.astype(np.int64)
+    if below is not None:
+        below = below.astype(np.int64)
+    if flat:
+        return count[0], quant[:, :, 0], None if below is None else below[:, :, 0]
+    return count, quant, below
 
 
 def guidance_gains(params, sol_blob: np.ndarray, nt: int, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,
