@@ -129,32 +129,39 @@ ASC_DEV void store_start(double *w, int Kp, int k, const double *z, const double
   for (int b = 0; b < 6; b++) w[(R_IT + O_ZB + b) * Kp + k] = zb[b];
   // (the second iterate buffer, the step and the gains are written before they are read)
 }
+// The zero halo of the node rows (ascent_persist_dev.hpp, load_node): column k >= K of both iterate buffers and of the step.  The
+// workspace comes from an earlier call with another geometry as it was left; p_solve never stores there.  Every thread of the NLP's blocks
+// takes a share of the 3 NIT (Kp - K) words (left to the threads of the pad columns alone they are 3 NIT stores in a row per thread).
+ASC_DEV void store_halo(double *w, int K, int Kp, int nit) {
+  const int npad = Kp - K, n = 3 * nit * npad;
+  for (int i = blockIdx.x * WAVE + threadIdx.x; i < n; i += gridDim.x * WAVE) w[(size_t)(i / npad) * Kp + K + i % npad] = 0.0;
+}
 
 __global__ __launch_bounds__(WAVE) void p_init(const ascent_params *params, long batch, PGeo g, double *ws, const double *guess,
                                                int warm, double mu_init, const double *probe_mu, const double *probe_dw, int probe_kind) {
   const long p = blockIdx.y;
   const int k = blockIdx.x * WAVE + threadIdx.x, K = g.K, Kp = g.Kp;
-  if (k >= Kp) return;
   double *w = ws + (size_t)p * g.nlp_doubles();
+  store_halo(w, K, Kp, g.nit());
+  if (k >= K) return;
   const Der d = derive_t(params[p], g.term);
   const int asked_warm = warm;
   if (warm && !(guess[(21L * K + S_TH) * batch + p] > 0.0)) warm = 0;
   const bool probe = probe_mu != nullptr;          // the iterate is taken as it is
   double z[7], l[7], zb[6], u = 0.0;
-  const int kk = k < K ? k : K - 1;                  // padding nodes replicate the last node (never read by anything that counts)
   if (warm) {
     ASC_UNROLL
-    for (int i = 0; i < 7; i++) { z[i] = guess[(7L * kk + i) * batch + p]; l[i] = guess[(8L * K + 7L * kk + i) * batch + p]; }
-    u = guess[(7L * K + kk) * batch + p];
+    for (int i = 0; i < 7; i++) { z[i] = guess[(7L * k + i) * batch + p]; l[i] = guess[(8L * K + 7L * k + i) * batch + p]; }
+    u = guess[(7L * K + k) * batch + p];
     ASC_UNROLL
-    for (int b = 0; b < 6; b++) zb[b] = guess[(15L * K + 6L * kk + b) * batch + p];
+    for (int b = 0; b < 6; b++) zb[b] = guess[(15L * K + 6L * k + b) * batch + p];
   }
-  start_node(d, K, kk, warm, probe, g.form, z, l, zb, u);
+  start_node(d, K, k, warm, probe, g.form, z, l, zb, u);
   store_start(w, Kp, k, z, l, zb, u);
   if (g.mp) {       // (v1: the MV is the angle = (aub/2)(u + 1), starts at 0 and carries DCOST itself)
-    const double ha = 0.5 * d.aub, f0 = (double)kk / K * 0.5;             // (cold start: the straight-line guess of node kk-1)
-    double up = kk == 0 ? (g.form == 1 ? -1.0 : 0.0) : warm ? guess[(7L * K + kk - 1) * batch + p] : (g.form == 1 ? f0 / ha - 1.0 : 0.0);
-    if (kk > 0 && !probe) up = push_in(up, -1.0, 1.0);
+    const double ha = 0.5 * d.aub, f0 = (double)k / K * 0.5;             // (cold start: the straight-line guess of node k-1)
+    double up = k == 0 ? (g.form == 1 ? -1.0 : 0.0) : warm ? guess[(7L * K + k - 1) * batch + p] : (g.form == 1 ? f0 / ha - 1.0 : 0.0);
+    if (k > 0 && !probe) up = push_in(up, -1.0, 1.0);
     start_move(w, Kp, k, u, up, warm != 0, bad_weight(params[p]) ? 1.0 : g.form == 1 ? params[p].dcost * ha : params[p].dcost);
   }
   if (k != K - 1) return;
@@ -184,17 +191,17 @@ __global__ __launch_bounds__(WAVE) void p_transfer(const ascent_params *params, 
                                                    double *wsf, double mu) {
   const long p = blockIdx.y;
   const int k = blockIdx.x * WAVE + threadIdx.x, Kc = gc.K, Kf = gf.K, Kpc = gc.Kp, Kpf = gf.Kp;
-  if (k >= Kpf) return;
   const double *wc = wsc + (size_t)p * gc.nlp_doubles(), *scc = wc + (size_t)gc.nrows() * Kpc;
   double *wf = wsf + (size_t)p * gf.nlp_doubles();
+  store_halo(wf, Kf, Kpf, gf.nit());
+  if (k >= Kf) return;
   const Der d = derive_t(params[p], gf.term);
   const int warm = (int)scc[X_STATUS] == ASCENT_CONVERGED ? 2 : 0;
   const bool invalid = (int)scc[X_STATUS] == ASCENT_INVALID_PROBLEM;      // refused by p_init: stays refused, at a cold start of this grid
   const double *ic = wc + (size_t)((int)scc[X_CUR] * gc.nit()) * Kpc;
   double z[7], l[7], zb[6], u = 0.0, up = 0.0;
-  const int kk = k < Kf ? k : Kf - 1;
-  if (warm && gf.mp && kk > 0) {      // the prolonged control of the node before (for the slack pair of this node's movement)
-    const double x = (double)kk / (double)Kf * (double)Kc;
+  if (warm && gf.mp && k > 0) {      // the prolonged control of the node before (for the slack pair of this node's movement)
+    const double x = (double)k / (double)Kf * (double)Kc;
     int j = (int)x;
     if (j > Kc - 1) j = Kc - 1;
     const double wt = x - (double)j;
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(WAVE) void p_transfer(const ascent_params *params, 
     up = push_in(fma(wt, b - a, a), -1.0, 1.0);
   }
   if (warm) {
-    const double x = (double)(kk + 1) / (double)Kf * (double)Kc;
+    const double x = (double)(k + 1) / (double)Kf * (double)Kc;
     int j = (int)x;
     if (j > Kc - 1) j = Kc - 1;
     const double wt = x - (double)j;
@@ -223,11 +230,11 @@ __global__ __launch_bounds__(WAVE) void p_transfer(const ascent_params *params, 
       zb[b6] = fma(wt, b - a, a) * zsc;
     }
   }
-  start_node(d, Kf, kk, warm, false, gf.form, z, l, zb, u);
+  start_node(d, Kf, k, warm, false, gf.form, z, l, zb, u);
   store_start(wf, Kpf, k, z, l, zb, u);
   if (gf.mp) {
-    if (kk == 0) up = gf.form == 1 ? -1.0 : 0.0;
-    else if (!warm && gf.form == 1) up = push_in((double)kk / Kf * 0.5 / (0.5 * d.aub) - 1.0, -1.0, 1.0);      // (cold: the guess of node kk-1)
+    if (k == 0) up = gf.form == 1 ? -1.0 : 0.0;
+    else if (!warm && gf.form == 1) up = push_in((double)k / Kf * 0.5 / (0.5 * d.aub) - 1.0, -1.0, 1.0);      // (cold: the guess of node k-1)
     start_move(wf, Kpf, k, u, up, warm != 0, invalid ? 1.0 : gf.form == 1 ? params[p].dcost * 0.5 * d.aub : params[p].dcost);
   }
   if (k != Kf - 1) return;
@@ -600,9 +607,9 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             const int k = c * CHN + nl;
             if (k < K) {
               NodeIn n, dn;
-              load_node<MP>(ic, Kp, K, k, n, UINIT);
+              load_node<MP, 0, FORM>(ic, Kp, k, n);
               if (first) dn = NodeIn{};             // (no step yet; the step rows are not initialised)
-              else load_node<MP>(stp, Kp, K, k, dn);
+              else load_node<MP, 1>(stp, Kp, k, dn);
               trial_node<SCHEME, FORM, MP, TERM>(d, K, Kp, k, n, dn, t, live, in, P);
             }
           }
@@ -758,7 +765,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
           const int k = c * CHN + nl;
           if (k < K && act) {
             NodeIn n;
-            load_node<MP>(it, Kp, K, k, n, UINIT);
+            load_node<MP, 0, FORM>(it, Kp, k, n);
             double G[8], E[4], H[10], F[7], fl[7], lt[7], ax, ay;
             ASC_UNROLL
             for (int i = 0; i < 7; i++) lt[i] = SCHEME == 1 ? n.l[i] + n.ln[i] : n.l[i];
@@ -1052,7 +1059,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
           if (on) {
             double z[7], zp[7], F[7], ax, ay;
             ASC_UNROLL
-            for (int i = 0; i < 7; i++) { z[i] = it[(O_Z + i) * Kp + kn]; zp[i] = kn > 0 ? it[(O_Z + i) * Kp + kn - 1] : 0.0; }
+            for (int i = 0; i < 7; i++) { z[i] = it[(O_Z + i) * Kp + kn]; zp[i] = (i > 0 || kn > 0) ? it[(O_Z + i) * Kp + kn - 1] : 0.0; }      // (zero halo columns: load_node)
             u_ = it[O_U * Kp + kn];
             a_ = z[IA]; m_ = z[IM];
             ASC_UNROLL
@@ -1061,7 +1068,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             for (int i = 0; i < NS; i++) ka[i] = w[(size_t)(R_KA + i) * Kp + kn];
             if constexpr (MP) {
               pp_ = it[O_PP * Kp + kn]; pn_ = it[O_PN * Kp + kn]; zpp_ = it[O_ZP * Kp + kn]; zpn_ = it[O_ZN * Kp + kn]; lu_ = it[O_LU * Kp + kn];
-              x0u = -(u_ - (kn > 0 ? it[O_U * Kp + kn - 1] : UINIT) - pp_ + pn_);
+              x0u = -(u_ - ((FORM != 1 || kn > 0) ? it[O_U * Kp + kn - 1] : UINIT) - pp_ + pn_);
             }
             du00 = w[(size_t)R_K0 * Kp + kn] + w[(size_t)(R_K0 + 1) * Kp + kn] * dth + w[(size_t)(R_K0 + 2) * Kp + kn] * dnu3;
             accel<1>(d, z[IX], z[IY], z[IA], z[IM], 0.0, 0.0, ax, ay, G, nullptr);
@@ -1294,16 +1301,16 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
           TrialKeep kp;                       // what the trial point's dual rows need of its primal part (evaluated before the sweep)
           if (kn < K && act) {
             NodeIn n, dn;
-            load_node<MP>(it, Kp, K, kn, n, UINIT);
+            load_node<MP, 0, FORM>(it, Kp, kn, n);
             ASC_UNROLL
-            for (int i = 0; i < 7; i++) { dn.z[i] = stp[(O_Z + i) * Kp + kn]; dn.zp[i] = kn > 0 ? stp[(O_Z + i) * Kp + kn - 1] : 0.0; }
+            for (int i = 0; i < 7; i++) { dn.z[i] = stp[(O_Z + i) * Kp + kn]; dn.zp[i] = stp[(O_Z + i) * Kp + kn - 1]; }
             dn.u = stp[O_U * Kp + kn];
             ASC_UNROLL
             for (int b = 0; b < 6; b++) dn.zb[b] = stp[(O_ZB + b) * Kp + kn];
             if constexpr (MP) {
-              dn.up = kn > 0 ? stp[O_U * Kp + kn - 1] : 0.0;
+              dn.up = stp[O_U * Kp + kn - 1];
               dn.lu = stp[O_LU * Kp + kn];
-              dn.lun = kn + 1 < K ? stp[O_LU * Kp + kn + 1] : 0.0;
+              dn.lun = stp[O_LU * Kp + kn + 1];
               dn.pp = stp[O_PP * Kp + kn]; dn.pn = stp[O_PN * Kp + kn]; dn.zpp = stp[O_ZP * Kp + kn]; dn.zpn = stp[O_ZN * Kp + kn];
             }
             const double *dz = dn.z;
@@ -1430,11 +1437,11 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             ASC_UNROLL
             for (int i = 0; i < 7; i++) {
               l[i] = it[(O_L + i) * Kp + kn] + tc.alpha * dl[i];
-              ln[i] = (kn + 1 < K ? it[(O_L + i) * Kp + kn + 1] : 0.0) + tc.alpha * dln[i];
+              ln[i] = it[(O_L + i) * Kp + kn + 1] + tc.alpha * dln[i];
             }
             if constexpr (MP) {
               lu = it[O_LU * Kp + kn] + tc.alpha * stp[O_LU * Kp + kn];
-              lun = (kn + 1 < K ? it[O_LU * Kp + kn + 1] : 0.0) + tc.alpha * (kn + 1 < K ? stp[O_LU * Kp + kn + 1] : 0.0);
+              lun = it[O_LU * Kp + kn + 1] + tc.alpha * stp[O_LU * Kp + kn + 1];
             }
             trial_dual<SCHEME, FORM, MP, TERM>(d, K, Kp, kn, kp, l, ln, lu, lun, tc, live, in, P);
           }
@@ -1490,7 +1497,8 @@ namespace ascent {
 static PGeo geo_of(int K, int form = 0, int mp = 0, int term = 0, int wide = 0, int scheme = 0) {
   PGeo g;
   const int ch = scheme == 2 ? hs_chunk_nodes(wide) : wide ? 64 : CH;
-  g.K = K; g.nch = (K + ch - 1) / ch; g.Kp = (g.nch * ch + 15) / 16 * 16;      // (rows of an NLP start on 128-byte lines: see PGeo::nlp_doubles)
+  // (rows of an NLP start on 128-byte lines: see PGeo::nlp_doubles; at least one column behind the last node: the zero halo of load_node)
+  g.K = K; g.nch = (K + ch - 1) / ch; g.Kp = ((g.nch * ch > K ? g.nch * ch : K + 1) + 15) / 16 * 16;
   g.form = form; g.mp = mp ? 1 : 0; g.term = term == 2 ? 2 : 0; g.wide = wide ? 1 : 0;
   return g;
 }

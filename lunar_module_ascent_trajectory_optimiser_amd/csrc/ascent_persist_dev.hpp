@@ -18,6 +18,8 @@ constexpr int O_LU = 21, O_PP = 22, O_PN = 23, O_ZP = 24, O_ZN = 25;      // mov
 // Rows of an NLP's node arrays: two iterate buffers, the step, the feedback gains of the factorisation.  MP = 1: with the l1 move
 // penalty (ascent_opts.move_penalty, the reference's angledoubledot.DCOST, Launch_Optimiser.py:99) the control is the eighth
 // state of a stage and an iterate carries five more rows per node.
+// A row has Kp >= K + 1 columns; the columns k >= K of the iterate and step rows are zero halos: p_init / p_transfer write +0.0 there
+// and every store of p_solve into a node row stands under k < K, so they stay +0.0 for the life of a level (see load_node below).
 template <int MP>
 struct Lay {
   static constexpr int NS = 7 + MP, NIT = 21 + 5 * MP;
@@ -172,24 +174,32 @@ struct NodeIn {      // what a node evaluation reads: node k of the iterate, the
   double z[7], zp[7], l[7], ln[7], zb[6], u;
   double up, lu, lun, pp, pn, zpp, zpn;      // move penalty only: u_{k-1}, lambda_u of nodes k and k+1, the slack pair and its multipliers
 };
-// (uinit: the control "before node 0" of the movement equations -- the MV's initial value: 0, or -1 where the v1 formulation's
-//  angle starts at 0; loads of a STEP pass 0)
-template <int MP = 0>
-ASC_DEV void load_node(const double *it, int Kp, int K, int k, NodeIn &n, double uinit = 0.0) {
+// Zero halo columns.  Kp >= K + 1 (geo_of), and in every node row of the two iterate buffers and of the step (rows R_IT .. R_KA - 1)
+// the columns k >= K hold +0.0 for the whole life of a level: p_init and p_transfer write them, and every store of p_solve into
+// these rows stands under k < K (trial_primal, trial_dual, the step stores of the forward and adjoint phases, the probe rows).
+// The neighbour of the first node is then the last pad column of the row in front, the neighbour of the last node the row's own
+// column K: node k-1 / k+1 of a row is loaded without a test and the grid ends read the +0.0 a select would produce.  Two loads
+// keep their select: row O_Z + 0 of an iterate at k = 0 (in front of buffer 0 lies the scalar record of the NLP before, or nothing),
+// and the control "before node 0" of the v1 formulation's movement equations, which is -1 (the angle starts at 0), not 0.
+// STEP: the rows are the step's -- the row in front of its O_Z + 0 is the second iterate buffer's last, the control before node 0 is 0.
+// (Kp is taken as a 64-bit stride here: a row address is then one v_lshl_add_u64 instead of add, sign extension and shift-add.  Here
+//  only -- in trial_* or all of p_solve it costs scratch or time)
+template <int MP = 0, int STEP = 0, int FORM = 0>
+ASC_DEV void load_node(const double *it, long Kp, int k, NodeIn &n) {
   ASC_UNROLL
   for (int i = 0; i < 7; i++) {
     n.z[i] = it[(O_Z + i) * Kp + k];
     n.l[i] = it[(O_L + i) * Kp + k];
-    n.zp[i] = k > 0 ? it[(O_Z + i) * Kp + k - 1] : 0.0;
-    n.ln[i] = k + 1 < K ? it[(O_L + i) * Kp + k + 1] : 0.0;
+    n.zp[i] = (STEP || i > 0 || k > 0) ? it[(O_Z + i) * Kp + k - 1] : 0.0;
+    n.ln[i] = it[(O_L + i) * Kp + k + 1];
   }
   n.u = it[O_U * Kp + k];
   ASC_UNROLL
   for (int b = 0; b < 6; b++) n.zb[b] = it[(O_ZB + b) * Kp + k];
   if constexpr (MP) {
-    n.up = k > 0 ? it[O_U * Kp + k - 1] : uinit;
+    n.up = (STEP || FORM != 1 || k > 0) ? it[O_U * Kp + k - 1] : -1.0;
     n.lu = it[O_LU * Kp + k];
-    n.lun = k + 1 < K ? it[O_LU * Kp + k + 1] : 0.0;
+    n.lun = it[O_LU * Kp + k + 1];
     n.pp = it[O_PP * Kp + k]; n.pn = it[O_PN * Kp + k]; n.zpp = it[O_ZP * Kp + k]; n.zpn = it[O_ZN * Kp + k];
   }
 }
