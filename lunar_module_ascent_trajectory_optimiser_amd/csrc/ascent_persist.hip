@@ -78,6 +78,50 @@ ASC_DEV MovePivot move_pivot(double pp, double pn, double zp, double zn, double 
   m.gdl = m.Rd * (m.rp * isp - m.rn * isn);
   return m;
 }
+// The node-local rows of a Newton step: everything the step of node k holds besides dz, du, dl and d lambda_u is a closed form of
+// the node's iterate, of dz_angle, dz_mass, du of the node, du of node k-1 and of the NLP's mu and delta_w.  The forward phase
+// computes the rows for the fraction to the boundary and does not store them; the adjoint phase, a line-search retry and
+// p_probe_out compute them again from what they load anyway (one function: the same bits everywhere, as with move_pivot).
+//   bounds: dz_b = (mu -+ z_b dx) / dist - z_b,  id[b] = rcp(dist[b]), dist = angle, aub - angle, mass, 1 - mass, u + 1, 1 - u
+//   MP: the movement multiplier from the stage control's own stationarity row, d lambda_u = Rd ddelta + gdl, then the slack pair:
+//   the slack with the larger curvature from its own row (well conditioned), the other one from ddelta = dp - dn (its own row
+//   divides a difference of two nearly equal numbers by a curvature that vanishes for an inactive slack)
+// x0u = move_x0(...): minus the movement equation's residual; du_p: the control step of node k-1 (0 before node 0).
+struct StepLocals { double zb[6], lu, pp, pn, zpp, zpn; MovePivot mv; };
+ASC_DEV double move_x0(double u, double up, double pp, double pn) { return -(u - up - pp + pn); }
+template <int MP>
+ASC_DEV void step_locals(const double *id, const double *zb, double dza, double dzm, double du, double mu, double du_p, double x0u,
+                         double pp, double pn, double zpp, double zpn, double lu, double dcw, double dw, StepLocals &o) {
+  const double dx3[3] = {dza, dzm, du};
+  ASC_UNROLL
+  for (int b = 0; b < 3; b++) {
+    const double zl = zb[2 * b], zu = zb[2 * b + 1];
+    o.zb[2 * b] = id[2 * b] * (mu - zl * dx3[b]) - zl;
+    o.zb[2 * b + 1] = id[2 * b + 1] * (mu + zu * dx3[b]) - zu;
+  }
+  if constexpr (MP) {
+    const double ddel = (du - du_p) - x0u;
+    o.mv = move_pivot(pp, pn, zpp, zpn, lu, dcw, mu, dw);
+    const MovePivot &mvp = o.mv;
+    const double dlu = mvp.Rd * ddel + mvp.gdl;
+    double dpp, dpn;
+    if (mvp.sgp >= mvp.sgn) { dpp = (dlu - mvp.rp) * rcp(mvp.sgp); dpn = dpp - ddel; }
+    else { dpn = (-dlu - mvp.rn) * rcp(mvp.sgn); dpp = ddel + dpn; }
+    o.lu = dlu; o.pp = dpp; o.pn = dpn;
+    o.zpp = mvp.ip * (mu - zpp * dpp) - zpp; o.zpn = mvp.in_ * (mu - zpn * dpn) - zpn;
+  }
+}
+// ... for a node whose iterate n (load_node) and stored step rows dz, du, du_{k-1} (dn.z, dn.u, dn.up) are loaded: the step rows
+// that are not stored, into dn.  id: the reciprocal bound distances of the iterate; mu, dw: X_MU, X_DWL as the forward phase used them.
+template <int MP>
+ASC_DEV void node_step_locals(const NodeIn &n, NodeIn &dn, const double *id, double mu, double dw, double dcw) {
+  StepLocals sl;
+  if constexpr (MP) step_locals<1>(id, n.zb, dn.z[IA], dn.z[IM], dn.u, mu, dn.up, move_x0(n.u, n.up, n.pp, n.pn), n.pp, n.pn, n.zpp, n.zpn, n.lu, dcw, dw, sl);
+  else step_locals<0>(id, n.zb, dn.z[IA], dn.z[IM], dn.u, mu, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, sl);
+  ASC_UNROLL
+  for (int b = 0; b < 6; b++) dn.zb[b] = sl.zb[b];
+  if constexpr (MP) { dn.pp = sl.pp; dn.pn = sl.pn; dn.zpp = sl.zpp; dn.zpn = sl.zpn; }
+}
 
 // The starting point at node kk: the built-in straight-line guess (warm == 0) or the caller's / the coarser grid's values in
 // z, l, u, zb, pushed into the interior (warm 1: primal only, warm 2: primal-dual; a probe takes them as they are)
@@ -325,13 +369,33 @@ __global__ __launch_bounds__(WAVE) void p_reduce_probe(const double *in, long n,
 }
 
 // p_probe_out: the Newton step one probe round left behind, in the external blob layout; inertia[p] = 1: refused
-__global__ __launch_bounds__(WAVE) void p_probe_out(long batch, PGeo g, const double *ws, double *step, int *inertia) {
+// (stored_zb: h_solve stores the bound-multiplier steps; p_solve does not -- they are formed here from the probe's iterate, which the
+//  round left in buffer X_CUR, its mu and the stored primal step, with the function the kernel's forward phase used: step_locals)
+__global__ __launch_bounds__(WAVE) void p_probe_out(const ascent_params *params, long batch, PGeo g, const double *ws, int stored_zb, double *step,
+                                                    int *inertia) {
   const long p = blockIdx.y;
   const int k = blockIdx.x * WAVE + threadIdx.x, K = g.K, Kp = g.Kp;
   if (k >= K) return;
   const double *w = ws + (size_t)p * g.nlp_doubles();
   const double *sc = w + (size_t)g.nrows() * Kp, *stp = w + (size_t)g.r_st() * Kp;
   const bool ok = (int)sc[X_STATE] == ST_TRIAL;
+  double dzb[6];
+  if (stored_zb) {
+    ASC_UNROLL
+    for (int b = 0; b < 6; b++) dzb[b] = stp[(O_ZB + b) * Kp + k];
+  } else {
+    const double *it = w + (size_t)((int)sc[X_CUR] * g.nit()) * Kp;
+    const Der d = derive_t(params[p], g.term);
+    const double a_ = it[(O_Z + IA) * Kp + k], m_ = it[(O_Z + IM) * Kp + k], u_ = it[O_U * Kp + k];
+    const double id[6] = {rcp(a_), rcp(d.aub - a_), rcp(m_), rcp(1.0 - m_), rcp(u_ + 1.0), rcp(1.0 - u_)};
+    double zb[6];
+    ASC_UNROLL
+    for (int b = 0; b < 6; b++) zb[b] = it[(O_ZB + b) * Kp + k];
+    StepLocals sl;
+    step_locals<0>(id, zb, stp[(O_Z + IA) * Kp + k], stp[(O_Z + IM) * Kp + k], stp[O_U * Kp + k], sc[X_MU], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, sl);
+    ASC_UNROLL
+    for (int b = 0; b < 6; b++) dzb[b] = sl.zb[b];
+  }
   if (k == 0) {
     inertia[p] = ok ? 0 : 1;
     for (int r = 0; r < 10; r++) step[(21L * K + r) * batch + p] = ok ? sc[X_D + r] : 0.0;
@@ -343,7 +407,7 @@ __global__ __launch_bounds__(WAVE) void p_probe_out(long batch, PGeo g, const do
   }
   step[(7L * K + k) * batch + p] = ok ? stp[O_U * Kp + k] : 0.0;
   ASC_UNROLL
-  for (int b = 0; b < 6; b++) step[(15L * K + 6L * k + b) * batch + p] = ok ? stp[(O_ZB + b) * Kp + k] : 0.0;
+  for (int b = 0; b < 6; b++) step[(15L * K + 6L * k + b) * batch + p] = ok ? dzb[b] : 0.0;
 }
 
 // p_probe_rows_out: the node rows one probe round (kind 2) dumped from LDS, in the layout of ascent_eval_nodes: defects
@@ -600,6 +664,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
           P.rd = sc[X_P + 0]; P.cinf = sc[X_P + 1]; P.pmin = sc[X_P + 2]; P.pmax = sc[X_P + 3]; P.l1 = sc[X_P + 4];
           P.zsum = sc[X_P + 5]; P.rth = sc[X_P + 6]; P.c1 = sc[X_P + 7]; P.sl = sc[X_P + 8]; P.mv = sc[X_P + 9];
         } else {
+          const double dwl = sc[X_DWL];      // (retries: mu and delta_w are still those of the step's forward phase -- X_MU moves on acceptance only)
           TrialCtx t;
           t.alpha = alpha; t.adu = adu; t.mlo = mlo; t.mhi = mhi; t.dt = dt; t.be = be; t.hT = hT; t.first = first; t.stt = stt; t.dcw = dcw;
           P.clear();
@@ -607,9 +672,13 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             const int k = c * CHN + nl;
             if (k < K) {
               NodeIn n, dn;
-              load_node<MP, 0, FORM>(ic, Kp, k, n);
+              load_node<MP, FORM>(ic, Kp, k, n);
               if (first) dn = NodeIn{};             // (no step yet; the step rows are not initialised)
-              else load_node<MP, 1>(stp, Kp, k, dn);
+              else {                                // a retry: the stored step rows, the others from the iterate as the forward phase formed them
+                load_step<MP>(stp, Kp, k, dn);
+                const double id[6] = {rcp(n.z[IA]), rcp(d.aub - n.z[IA]), rcp(n.z[IM]), rcp(1.0 - n.z[IM]), rcp(n.u + 1.0), rcp(1.0 - n.u)};
+                node_step_locals<MP>(n, dn, id, mu, dwl, dcw);
+              }
               trial_node<SCHEME, FORM, MP, TERM>(d, K, Kp, k, n, dn, t, live, in, P);
             }
           }
@@ -765,7 +834,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
           const int k = c * CHN + nl;
           if (k < K && act) {
             NodeIn n;
-            load_node<MP, 0, FORM>(it, Kp, k, n);
+            load_node<MP, FORM>(it, Kp, k, n);
             double G[8], E[4], H[10], F[7], fl[7], lt[7], ax, ay;
             ASC_UNROLL
             for (int i = 0; i < 7; i++) lt[i] = SCHEME == 1 ? n.l[i] + n.ln[i] : n.l[i];
@@ -1068,7 +1137,7 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             for (int i = 0; i < NS; i++) ka[i] = w[(size_t)(R_KA + i) * Kp + kn];
             if constexpr (MP) {
               pp_ = it[O_PP * Kp + kn]; pn_ = it[O_PN * Kp + kn]; zpp_ = it[O_ZP * Kp + kn]; zpn_ = it[O_ZN * Kp + kn]; lu_ = it[O_LU * Kp + kn];
-              x0u = -(u_ - ((FORM != 1 || kn > 0) ? it[O_U * Kp + kn - 1] : UINIT) - pp_ + pn_);
+              x0u = move_x0(u_, (FORM != 1 || kn > 0) ? it[O_U * Kp + kn - 1] : UINIT, pp_, pn_);
             }
             du00 = w[(size_t)R_K0 * Kp + kn] + w[(size_t)(R_K0 + 1) * Kp + kn] * dth + w[(size_t)(R_K0 + 2) * Kp + kn] * dnu3;
             accel<1>(d, z[IX], z[IY], z[IA], z[IM], 0.0, 0.0, ax, ay, G, nullptr);
@@ -1205,43 +1274,26 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             ASC_FTBR(rmax, id[2], dzm); ASC_FTBR(rmax, id[3], -dzm);
             ASC_FTBR(rmax, id[4], du); ASC_FTBR(rmax, id[5], -du);
             gsum += dza * (id[1] - id[0]) + dzm * (id[3] - id[2]) + du * (id[5] - id[4]);
-            const double dx3[3] = {dza, dzm, du};
-            double dzb[6];
+            // (the bound-multiplier steps and the slack pair's are used here and not stored: whoever needs them again -- the adjoint
+            //  phase's trial point, a line-search retry, p_probe_out -- computes them again with step_locals; d lambda_u is stored,
+            //  the trial point's stationarity row needs it of node k+1)
+            StepLocals sl;
+            step_locals<MP>(id, zb, dza, dzm, du, mu, MP ? (nl > 0 ? outb[7 * LDW + col - 1] : carry_u) : 0.0, x0u, pp_, pn_, zpp_, zpn_, lu_, dcw, dw, sl);
             ASC_UNROLL
-            for (int b = 0; b < 3; b++) {
-              const double zl = zb[2 * b], zu = zb[2 * b + 1];
-              dzb[2 * b] = id[2 * b] * (mu - zl * dx3[b]) - zl;
-              dzb[2 * b + 1] = id[2 * b + 1] * (mu + zu * dx3[b]) - zu;
-              ASC_FTB(adu, zl, dzb[2 * b]);
-              ASC_FTB(adu, zu, dzb[2 * b + 1]);
-            }
+            for (int b = 0; b < 6; b++) ASC_FTB(adu, zb[b], sl.zb[b]);
             if (live) {
               ASC_UNROLL
               for (int i = 0; i < 7; i++) stp[(O_Z + i) * Kp + kn] = dzn[i];
               stp[O_U * Kp + kn] = du;
-              ASC_UNROLL
-              for (int b = 0; b < 6; b++) stp[(O_ZB + b) * Kp + kn] = dzb[b];
             }
             if constexpr (MP) {
-              // The movement multiplier from the stage control's own stationarity row, d lambda_u = Rd ddelta + gdl, then the slack pair:
-              // the slack with the larger curvature from its own row (well conditioned), the other one from ddelta = dp - dn (its own row
-              // divides a difference of two nearly equal numbers by a curvature that vanishes for an inactive slack)
-              const double du_p = nl > 0 ? outb[7 * LDW + col - 1] : carry_u;
-              const double ddel = (du - du_p) - x0u;
-              const MovePivot mvp = move_pivot(pp_, pn_, zpp_, zpn_, lu_, dcw, mu, dw);
-              const double dlu = mvp.Rd * ddel + mvp.gdl;
-              double dpp, dpn;
-              if (mvp.sgp >= mvp.sgn) { dpp = (dlu - mvp.rp) * rcp(mvp.sgp); dpn = dpp - ddel; }
-              else { dpn = (-dlu - mvp.rn) * rcp(mvp.sgn); dpp = ddel + dpn; }
-              const double dzp = mvp.ip * (mu - zpp_ * dpp) - zpp_, dzn_ = mvp.in_ * (mu - zpn_ * dpn) - zpn_;
-              ASC_FTBR(rmax, mvp.ip, dpp); ASC_FTBR(rmax, mvp.in_, dpn);
-              ASC_FTB(adu, zpp_, dzp); ASC_FTB(adu, zpn_, dzn_);
-              gsum -= dpp * mvp.ip + dpn * mvp.in_;
-              gmove += dpp + dpn;
-              clu -= x0u * (lu_ + dlu);           // c_u (lambda_u + d lambda_u) of the merit function's curvature estimate
-              if (live) {
-                stp[O_LU * Kp + kn] = dlu; stp[O_PP * Kp + kn] = dpp; stp[O_PN * Kp + kn] = dpn; stp[O_ZP * Kp + kn] = dzp; stp[O_ZN * Kp + kn] = dzn_;
-              }
+              const MovePivot &mvp = sl.mv;
+              ASC_FTBR(rmax, mvp.ip, sl.pp); ASC_FTBR(rmax, mvp.in_, sl.pn);
+              ASC_FTB(adu, zpp_, sl.zpp); ASC_FTB(adu, zpn_, sl.zpn);
+              gsum -= sl.pp * mvp.ip + sl.pn * mvp.in_;
+              gmove += sl.pp + sl.pn;
+              clu -= x0u * (lu_ + sl.lu);         // c_u (lambda_u + d lambda_u) of the merit function's curvature estimate
+              if (live) stp[O_LU * Kp + kn] = sl.lu;
             }
           }
           if constexpr (MP) carry_u = outb[7 * LDW + cbase + CHN - 1];       // the control step of the chunk's last node
@@ -1301,18 +1353,11 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
           TrialKeep kp;                       // what the trial point's dual rows need of its primal part (evaluated before the sweep)
           if (kn < K && act) {
             NodeIn n, dn;
-            load_node<MP, 0, FORM>(it, Kp, kn, n);
+            load_node<MP, FORM>(it, Kp, kn, n);
             ASC_UNROLL
             for (int i = 0; i < 7; i++) { dn.z[i] = stp[(O_Z + i) * Kp + kn]; dn.zp[i] = stp[(O_Z + i) * Kp + kn - 1]; }
             dn.u = stp[O_U * Kp + kn];
-            ASC_UNROLL
-            for (int b = 0; b < 6; b++) dn.zb[b] = stp[(O_ZB + b) * Kp + kn];
-            if constexpr (MP) {
-              dn.up = stp[O_U * Kp + kn - 1];
-              dn.lu = stp[O_LU * Kp + kn];
-              dn.lun = stp[O_LU * Kp + kn + 1];
-              dn.pp = stp[O_PP * Kp + kn]; dn.pn = stp[O_PN * Kp + kn]; dn.zpp = stp[O_ZP * Kp + kn]; dn.zpn = stp[O_ZN * Kp + kn];
-            }
+            if constexpr (MP) dn.up = stp[O_U * Kp + kn - 1];
             const double *dz = dn.z;
             double G[8], E[4], H[10], F[7], fl[7], lt[7], ax, ay;
             ASC_UNROLL
@@ -1394,6 +1439,11 @@ __global__ __launch_bounds__(WAVE) void p_solve(const ascent_params *params, lon
             ASC_UNROLL
             for (int i = 0; i < 7; i++) stage[(6 * i + 5) * LDW + col] = wv[i];
             // the primal step of the chunk is known: the primal part of its trial point at the first step length, before the sweep
+            // (the step rows the forward phase did not store: formed here, next to their one use, not at the loads)
+            {
+              const double id[6] = {id0, id1, id2, id3, rcp(n.u + 1.0), rcp(1.0 - n.u)};
+              node_step_locals<MP>(n, dn, id, mu, dw, dcw);
+            }
             trial_primal<SCHEME, FORM, MP, TERM>(d, K, Kp, kn, n, dn, tc, live, in, P, kp);
           }
           wsync();
@@ -1592,7 +1642,7 @@ int persist_probe(const Call &c, bool wide, double *ws, const ProbeIO &io) {
   const dim3 ng((unsigned)((g.Kp + WAVE - 1) / WAVE), (unsigned)c.batch);
   hipLaunchKernelGGL(p_init, ng, dim3(WAVE), 0, c.stream, c.dp, c.batch, g, ws, io.iterate, 2, 0.1, io.mu, io.dw, 1);
   launch_solve(c.scheme, c.form, c.mp, c.batch, c.stream, c.dp, g, ws, 1000, -1.0);
-  hipLaunchKernelGGL(p_probe_out, ng, dim3(WAVE), 0, c.stream, c.batch, g, (const double *)ws, io.step, io.inertia);
+  hipLaunchKernelGGL(p_probe_out, ng, dim3(WAVE), 0, c.stream, c.dp, c.batch, g, (const double *)ws, c.scheme == 2 ? 1 : 0, io.step, io.inertia);
   ASC_CHK(c.err, c.errlen, hipGetLastError());
   return ASCENT_OK;
 }

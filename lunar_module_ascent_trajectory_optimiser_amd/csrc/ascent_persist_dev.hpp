@@ -181,26 +181,44 @@ struct NodeIn {      // what a node evaluation reads: node k of the iterate, the
 // column K: node k-1 / k+1 of a row is loaded without a test and the grid ends read the +0.0 a select would produce.  Two loads
 // keep their select: row O_Z + 0 of an iterate at k = 0 (in front of buffer 0 lies the scalar record of the NLP before, or nothing),
 // and the control "before node 0" of the v1 formulation's movement equations, which is -1 (the angle starts at 0), not 0.
-// STEP: the rows are the step's -- the row in front of its O_Z + 0 is the second iterate buffer's last, the control before node 0 is 0.
+// (load_step below: the rows are the step's -- the row in front of its O_Z + 0 is the second iterate buffer's last, the control before node 0 is 0.)
 // (Kp is taken as a 64-bit stride here: a row address is then one v_lshl_add_u64 instead of add, sign extension and shift-add.  Here
 //  only -- in trial_* or all of p_solve it costs scratch or time)
-template <int MP = 0, int STEP = 0, int FORM = 0>
+template <int MP = 0, int FORM = 0>
 ASC_DEV void load_node(const double *it, long Kp, int k, NodeIn &n) {
   ASC_UNROLL
   for (int i = 0; i < 7; i++) {
     n.z[i] = it[(O_Z + i) * Kp + k];
     n.l[i] = it[(O_L + i) * Kp + k];
-    n.zp[i] = (STEP || i > 0 || k > 0) ? it[(O_Z + i) * Kp + k - 1] : 0.0;
+    n.zp[i] = (i > 0 || k > 0) ? it[(O_Z + i) * Kp + k - 1] : 0.0;
     n.ln[i] = it[(O_L + i) * Kp + k + 1];
   }
   n.u = it[O_U * Kp + k];
   ASC_UNROLL
   for (int b = 0; b < 6; b++) n.zb[b] = it[(O_ZB + b) * Kp + k];
   if constexpr (MP) {
-    n.up = (STEP || FORM != 1 || k > 0) ? it[O_U * Kp + k - 1] : -1.0;
+    n.up = (FORM != 1 || k > 0) ? it[O_U * Kp + k - 1] : -1.0;
     n.lu = it[O_LU * Kp + k];
     n.lun = it[O_LU * Kp + k + 1];
     n.pp = it[O_PP * Kp + k]; n.pn = it[O_PN * Kp + k]; n.zpp = it[O_ZP * Kp + k]; n.zpn = it[O_ZN * Kp + k];
+  }
+}
+// The rows of the step that p_solve stores: dz, du, dl and (MP) d lambda_u with their neighbours (no select: see above).
+// The bound-multiplier rows and the slack pair's are not stored: the caller computes them from the iterate (step_locals, ascent_persist.hip).
+template <int MP = 0>
+ASC_DEV void load_step(const double *stp, long Kp, int k, NodeIn &n) {
+  ASC_UNROLL
+  for (int i = 0; i < 7; i++) {
+    n.z[i] = stp[(O_Z + i) * Kp + k];
+    n.l[i] = stp[(O_L + i) * Kp + k];
+    n.zp[i] = stp[(O_Z + i) * Kp + k - 1];
+    n.ln[i] = stp[(O_L + i) * Kp + k + 1];
+  }
+  n.u = stp[O_U * Kp + k];
+  if constexpr (MP) {
+    n.up = stp[O_U * Kp + k - 1];
+    n.lu = stp[O_LU * Kp + k];
+    n.lun = stp[O_LU * Kp + k + 1];
   }
 }
 
