@@ -4,7 +4,7 @@
 This is this repository's own counterpart of the reference script: the same problem, declared with
 the same modelling calls, solved by libascent on an MI355X instead of GEKKO/APMonitor/IPOPT.  It prints
 the quantities the reference prints (/root/reference/Launch_Optimiser.py:178-194) and writes the same
-three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim] [--disperse] [--guide [--feedforward]] [--corridor]
+three figures (:208-242).  Usage:  python examples/apollo11.py [--no-plots] [--outdir DIR] [--fly] [--trim] [--disperse] [--guide [--feedforward] [--lincov [--filter]]] [--corridor]
 --fly also integrates the ODEs under the control just found (RK4 on the device) and prints where that flight ends.
 --trim corrects (t_f, u) so that the flown control reaches the target orbit (trim_batch) and prints t_f and the flown apsides
 before and after.
@@ -34,6 +34,9 @@ NT = 200
 # --guide --feedforward: 1-sigma bias of each sample's state knowledge, scaled units (x, y, vx, vy, angle, angle rate, mass);
 # a position unit is the insertion altitude, 17703 m, a velocity unit 17703 m/s: 17.7 m and 1.8 cm/s
 NAV_BIAS = (1e-3, 1e-3, 1e-6, 1e-6, 0.0, 0.0, 0.0)
+# --guide --lincov --filter: 1-sigma of the position and velocity fixes, scaled units (5.3 m and 5.3 cm/s), taken at every FIX_STRIDE-th node
+FIX_SIGMA = (3e-4, 3e-4, 3e-6, 3e-6)
+FIX_STRIDE = 10
 
 
 def build(nt=NT, solver=None):
@@ -244,7 +247,7 @@ def lincov_report(name, lc, d, params, tf, outdir=None, figure=None):
 
 
 def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=False, corridor=False, outdir=None, lincov=False,
-          nav_tau=None, knowledge_tau=None, quantiles=False):
+          nav_tau=None, knowledge_tau=None, quantiles=False, navfilter=False):
     """The trimmed solution under the same dispersions, open loop and steering back to the nominal with a cutoff on the state.
     The cutoff channel stretches the last step only, T / K = 2.2 s here: 50 N of 15 kN over a 435 s burn is 1.4 s (1-sigma) of burn
     time, so the stretch is allowed +-2 steps; at stretch_max = 0.5 it sits on its bound for most samples.
@@ -253,8 +256,11 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
     nav_tau, knowledge_tau (seconds; with feedforward, corridor and lincov): the navigation bias as a stationary first-order
     Gauss-Markov process of that correlation time and the thrust estimate converging from its 10 N with that time constant
     (steady sigma 0): the sampled and the linear altitude band side by side, next to those of the frozen bias.
-    quantiles: every flight flown with its order statistics, and the lines of quantile_report for each."""
-    from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, guidance_gains, linear_corridor, trim_batch
+    quantiles: every flight flown with its order statistics, and the lines of quantile_report for each.
+    navfilter (with lincov): a Kalman filter on position and velocity fixes every tenth node (navigation_filter), and the closed
+    loop steering on its estimate (linear_corridor(filter=...)): what the filter believes of its error at burnout beside what the
+    error truly is under the thrust dispersion the filter does not model, and the burnout altitude with and without the filter."""
+    from lunar_module_ascent_trajectory_optimiser_amd import disperse_batch, guidance_gains, linear_corridor, navigation_filter, trim_batch
     res = m.result
     kw = dict(scheme=scheme, formulation=m._formulation)
     t = trim_batch(res.params, res.flight_blob(), res.nt, **kw)
@@ -323,6 +329,20 @@ def guide(m, scheme, samples=1024, weight=1e12, stretch_max=2.0, feedforward=Fal
                       res.params, t.tf[0], outdir)
         lincov_report("closed loop", linear_corridor(res.params, t.blob, res.nt, guidance=g, **lkw),
                       cl if corridor else disperse_batch(res.params, t.blob, res.nt, guidance=g, **hkw), res.params, t.tf[0], outdir, "lincov.png")
+    if lincov and navfilter:
+        S = ORBIT["periapsis"]
+        nf = navigation_filter(res.params, t.blob, res.nt, nav_sigma=NAV_BIAS, meas_rows=np.eye(7)[:4], meas_sigma=FIX_SIGMA, meas_stride=FIX_STRIDE,
+                               control_sigma=1e-3, **kw)
+        lkw = dict(param_sigma=thrust, control_sigma=1e-3, history=res.nt - 1, **kw)
+        bias = linear_corridor(res.params, t.blob, res.nt, guidance=g, nav_sigma=NAV_BIAS, **lkw)
+        filt = linear_corridor(res.params, t.blob, res.nt, guidance=g, filter=nf, **lkw)
+        print("navigation filter: status %d, fixes of %.1f m and %.1f cm/s (1-sigma) at every %dth node, %d of them"
+              % (nf.status[0], FIX_SIGMA[0] * S, FIX_SIGMA[2] * S * 100, FIX_STRIDE, nf.meas_nodes[0]))
+        print("knowledge error at burnout (1-sigma)   true   the filter's own")
+        for name, q, unit, f in (("x (m)", 0, S, 1.0), ("y (m)", 1, S, 1.0), ("xdot (cm/s)", 2, S, 100.0), ("ydot (cm/s)", 3, S, 100.0)):
+            print("%-30s %12.3f %14.3f" % (name, filt.nav_std[0, -1, q] * unit * f, nf.std[0, -1, q] * unit * f))
+        print("closed-loop 1-sigma altitude at burnout: with the filter +-%.2f m; with the frozen navigation bias +-%.2f m"
+              % (filt.std[0, -1, 7], bias.std[0, -1, 7]))
     return op, cl, g
 
 
@@ -368,6 +388,7 @@ if __name__ == "__main__":
     ap.add_argument("--quantiles", action="store_true", help="with --disperse or --guide: select order statistics of the samples on the device (disperse_batch(quantiles=..., limits=...)); prints, per flight flown, the 0.135 / 50 / 99.865 %%%% points of the flown periapsis and apoapsis and the fraction of samples whose flown periapsis is below %.0f km, and with --corridor the 0.135 %%%% .. 99.865 %%%% altitude band at the node where it is widest" % (PERIAPSIS_LIMIT / 1000))
     ap.add_argument("--nav-tau", type=float, default=None, metavar="SECONDS", help="with --guide --feedforward --corridor --lincov: the navigation bias as a stationary first-order Gauss-Markov process of this correlation time; prints the sampled and the linear altitude band beside those of the frozen bias")
     ap.add_argument("--knowledge-tau", type=float, default=None, metavar="SECONDS", help="with --guide --feedforward --corridor --lincov: the 10 N error of the thrust estimate decays with this time constant")
+    ap.add_argument("--filter", action="store_true", help="with --guide --lincov: a Kalman filter on position and velocity fixes (navigation_filter) and the closed loop steering on its estimate (linear_corridor(filter=...)); prints the true and the filter's own 1-sigma of the position and velocity knowledge at burnout, and the burnout altitude 1-sigma with the filter and with the frozen navigation bias")
     ap.add_argument("--lincov", action="store_true", help="with --guide: the linear covariance corridor (linear_corridor) of the open and the closed loop beside their Monte Carlo history; prints both 1-sigma altitude bands at the node where the sampled one is widest, and writes lincov.png (closed loop) and lincov_open_loop.png")
     a = ap.parse_args()
     if a.corridor and not (a.disperse or a.guide):
@@ -376,6 +397,8 @@ if __name__ == "__main__":
         ap.error("--quantiles needs --disperse or --guide")
     if a.lincov and not a.guide:
         ap.error("--lincov needs --guide")
+    if a.filter and not (a.guide and a.lincov):
+        ap.error("--filter needs --guide --lincov")
     if (a.nav_tau is not None or a.knowledge_tau is not None) and not (a.guide and a.feedforward and a.corridor and a.lincov):
         ap.error("--nav-tau and --knowledge-tau need --guide --feedforward --corridor --lincov")
     figdir = None if a.no_plots else a.outdir
@@ -394,6 +417,6 @@ if __name__ == "__main__":
         disperse(model, a.scheme, corridor=a.corridor, outdir=figdir, quantiles=a.quantiles)
     if a.guide:
         guide(model, a.scheme, feedforward=a.feedforward, corridor=a.corridor, outdir=figdir, lincov=a.lincov, nav_tau=a.nav_tau,
-              knowledge_tau=a.knowledge_tau, quantiles=a.quantiles)
+              knowledge_tau=a.knowledge_tau, quantiles=a.quantiles, navfilter=a.filter)
     if not a.no_plots:
         plots(model, variables, a.outdir)

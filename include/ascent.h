@@ -657,6 +657,72 @@ int ascent_covariance_drifting_batch(const ascent_params *p, int64_t batch, cons
                                      int32_t node_stride, double *nominal_out, double *cov_out, double *jac_hist_out_or_null,
                                      int device_id, void *hip_stream_or_null, int ptr_is_device);
 
+/* Navigation filter: the knowledge error estimated instead of driven.  A linear Kalman filter is designed along the flight
+ * (ascent_navigation_filter), and the linear covariance corridor is swept with the estimation error e = z-hat - z of any filter
+ * gains as the error the guidance law steers on (ascent_covariance_filtered_batch).  The model is that of
+ * ascent_covariance_history_batch: linearised about the flight of ascent_fly_batch at the blob, clips ignored, the substeps m held,
+ * the blob fixed in scaled units; Phi_k, g_k, Gamma_k, dz_k/dt_f and gamma_K the step records of ascent_guidance_gains.
+ * Measurements: n_meas (1 .. ASCENT_NAVFILTER_MAX_MEAS) scalar measurements h_i . z + sigma_i v, linear in the scaled state, constant
+ *   along the flight: meas_h [n_meas][7][batch], element (i, r, problem) at ((i*7 + r)*batch + problem), meas_sigma [n_meas][batch],
+ *   every sigma_i > 0.  They are taken at every node j, 1 <= j <= K, with j % meas_stride == 0 and processed one after the other,
+ *   i = 0 .. n_meas-1; no matrix is inverted.  A meas_stride above K is legal: no measurement is taken.
+ *
+ * ascent_navigation_filter (kernels f_fly, n_filter): the forward Riccati sweep.
+ *   P-hat_0 = diag(sigma_nav^2), sigma_nav [7][batch];
+ *   P-hat_k^- = Phi_k P-hat_{k-1} Phi_k' + sigma_u,k^2 g_k g_k' + diag(filter_q^2), sigma_u_or_null [K][batch] and filter_q_or_null
+ *   [7][batch] (null: zero);
+ *   at a measurement node, for i in order: s = h_i' P h_i + sigma_i^2, l_{k,i} = P h_i / s,
+ *   P <- (I - l h_i') P (I - l h_i')' + sigma_i^2 l l' (Joseph form; P is kept exactly symmetric by averaging the two halves of an entry).
+ *   gain_l_out [n_meas][7][K][batch], element (i, r, k-1, problem) at (((i*7 + r)*K + k-1)*batch + problem): l_{k,i}; exactly 0 at the
+ *   nodes without a measurement.  pfilt_out_or_null [ASCENT_NAV_COV_ROWS][K][batch]: the upper triangle, row by row, of P-hat_k
+ *   after the update.  summary_out [ASCENT_NAVFILTER_ROWS][batch]: 0 the status (0 ok, 2 frozen), 1 the first node whose innovation
+ *   variance s was <= 0 or not finite, or whose sigma_i was not > 0 (0: none; 1 where t_f, sigma_nav or filter_q is not finite), 2 the number of
+ *   measurement nodes, 3 the substeps m used.  From the failing node on the problem's rows of gain_l_out (those of the nodes
+ *   without a measurement included) and pfilt_out are NaN; the work stays bounded and the other problems are not affected.
+ *
+ * ascent_covariance_filtered_batch (kernels f_fly, l_lincov_filtered): the truth under filter gains gain_l [n_meas][7][K][batch],
+ *   the design's or any others; the gains of a node without a measurement are never read.  With e_0 = c[24..30]:
+ *   corr_k = K_k . (dz_{k-1} + e_{k-1}), du_k = -corr_k + eps_k,
+ *   dz_k = Phi_k dz_{k-1} + g_k du_k + Gamma_k dp + (dz_k/dt_f) dt_f, on step K with gain_t and stretch_max > 0 + gamma_K tau,
+ *   tau = -k_t . (dz_{K-1} + e_{K-1});
+ *   e_k^- = Phi_k e_{k-1} - g_k eps_k - Gamma_k dp - (dz_k/dt_f) dt_f (the filter knows the command and tau, not eps, dp or dt_f);
+ *   at a measurement node, for i in order: e <- e + l_{k,i} (-h_i . e + sigma_i v_{k,i}), v unit white noise.
+ *   The constants keep the ASCENT_LINCOV_COLS columns: 24..30 are e_0, with sigma_nav [7][batch] its standard deviations, and
+ *   column 31 is exactly 0 in every row.  History nodes and nominal_out (the same bits), jac_hist_out_or_null and cov_out as
+ *   ascent_covariance_history_batch defines them, the noise part of cov_out now from the 14 x 14 covariance of [dz; e] under eps and
+ *   v.  nav_cov_out [ASCENT_NAV_COV_ROWS][NJ][batch]: the upper triangle, row by row, of the covariance of e_j after the update
+ *   at node j.  nav_jac_out_or_null [7][ASCENT_LINCOV_COLS][NJ][batch], element (r, c, i, problem) at (((r*32 + c)*NJ + i)*batch +
+ *   problem): d e_j / d c.  Fed the design's own gains with sigma 0 on the fields and t_f, filter_q null and the same sigma_u and
+ *   sigma_nav, nav_cov_out is the design's pfilt_out up to rounding: the filter is consistent.
+ *   The order of every addition is fixed: a node's rows do not depend on node_stride, the batch, host or device pointers, or on
+ *   which optional outputs were asked for.  Without gain_u the ten quantities do not depend on the filter.
+ * Both refuse (ASCENT_E_ARG, before the device is looked at, no array touched) what ascent_covariance_history_batch refuses of the
+ *   arguments they share, n_meas outside 1 .. ASCENT_NAVFILTER_MAX_MEAS, meas_stride < 1, a null required pointer, gain_t or
+ *   stretch_max without gain_u and, with host pointers, a meas_sigma that is not > 0 and finite or a non-finite entry of meas_h,
+ *   sigma_nav or filter_q.  With device pointers the host does not read these arrays: such a problem has NaN rows at every node
+ *   of the covariance call; the filter call gives status 2 and NaN rows from node 1 for a non-finite sigma_nav or filter_q, which
+ *   enter P-hat before the first node, and from its first measurement node for meas_h and meas_sigma, which are not read before it
+ *   (never, with a meas_stride above K: status 0).  terminal = 2 is accepted.  Garbage blobs: the work is bounded
+ *   as in ascent_flight_jacobian; a non-finite t_f gives NaN rows at every node, a gain K_k or l_{k,i} that is not finite NaN rows
+ *   from the node where it enters.
+ * Host or device pointers; with device pointers and a stream each call only enqueues its two kernels.  Device workspace: that of
+ *   ascent_flight_jacobian. */
+#define ASCENT_NAVFILTER_MAX_MEAS 4
+#define ASCENT_NAVFILTER_ROWS 4
+#define ASCENT_NAV_COV_ROWS 28
+int ascent_navigation_filter(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                             const double *sigma_nav, const double *sigma_u_or_null, const double *filter_q_or_null,
+                             const double *meas_h, const double *meas_sigma, int32_t n_meas, int32_t meas_stride, double *gain_l_out,
+                             double *pfilt_out_or_null, double *summary_out, int device_id, void *hip_stream_or_null,
+                             int ptr_is_device);
+int ascent_covariance_filtered_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob,
+                                     int32_t substeps, const double *sigma, const double *sigma_u_or_null,
+                                     const double *gain_u_or_null, const double *gain_t_or_null, const double *stretch_max_or_null,
+                                     const double *sigma_nav, const double *gain_l, const double *meas_h, const double *meas_sigma,
+                                     int32_t n_meas, int32_t meas_stride, int32_t node_stride, double *nominal_out, double *cov_out,
+                                     double *nav_cov_out, double *jac_hist_out_or_null, double *nav_jac_out_or_null, int device_id,
+                                     void *hip_stream_or_null, int ptr_is_device);
+
 /* Order statistics of sample rows: quantiles and limit counts, exact (nothing is summed in floating point), on caller arrays.
  * values [quantities Q][groups G][samples][batch], element (q, i, s, problem) at (((q*G + i)*samples + s)*batch + problem): with
  *   G = 1 the layout of samples_out, with Q = ASCENT_HISTORY_QUANTITIES and G = NJ that of hist_samples_out.

@@ -10,7 +10,7 @@ from .solver import (solve_batch, solve_batch_torch, last_kernel_ms, eval_nodes,
                      param_sensitivity, final_time, fly_batch, FlightResult, FLIGHT_ROWS,
                      flight_jacobian, FlightJacobian, JACOBIAN_ROWS, trim_batch, TrimResult, TRIM_ROWS,
                      disperse_batch, DispersionResult, guidance_gains, GuidanceResult, GUIDE_ROWS, GUIDE_FF_ROWS,
-                     DispersionHistory, HISTORY_ROWS, linear_corridor, LinearCorridor, LINCOV_COLS,
+                     DispersionHistory, HISTORY_ROWS, linear_corridor, LinearCorridor, LINCOV_COLS, navigation_filter, NavigationFilter, NAVFILTER_ROWS,
                      sample_quantiles, quantile_chunks)
 
 __all__ = ["AscentParams", "sweep_isp_drymass", "sweep_config4", "solve_batch", "eval_nodes", "kkt_step",
@@ -18,5 +18,5 @@ __all__ = ["AscentParams", "sweep_isp_drymass", "sweep_config4", "solve_batch", 
            "isp_drymass_gradient", "fly_batch", "FlightResult", "FLIGHT_ROWS",
            "flight_jacobian", "FlightJacobian", "JACOBIAN_ROWS", "trim_batch", "TrimResult", "TRIM_ROWS",
            "disperse_batch", "DispersionResult", "guidance_gains", "GuidanceResult", "GUIDE_ROWS", "GUIDE_FF_ROWS",
-           "DispersionHistory", "HISTORY_ROWS", "linear_corridor", "LinearCorridor", "LINCOV_COLS",
+           "DispersionHistory", "HISTORY_ROWS", "linear_corridor", "LinearCorridor", "LINCOV_COLS", "navigation_filter", "NavigationFilter", "NAVFILTER_ROWS",
            "sample_quantiles", "quantile_chunks"]

@@ -37,7 +37,8 @@ SYMBOLS = ("ascent_version", "ascent_device_count", "ascent_strerror", "ascent_s
            "ascent_trim_batch", "ascent_disperse_batch", "ascent_guidance_gains", "ascent_disperse_guided_batch",
            "ascent_guidance_feedforward", "ascent_disperse_navigated_batch", "ascent_disperse_history_batch",
            "ascent_covariance_history_batch", "ascent_disperse_drifting_batch", "ascent_covariance_drifting_batch",
-           "ascent_reduce_probe", "ascent_sample_quantiles", "ascent_disperse_quantiles_batch", "ascent_disperse_quantiles_bytes")
+           "ascent_reduce_probe", "ascent_sample_quantiles", "ascent_disperse_quantiles_batch", "ascent_disperse_quantiles_bytes",
+           "ascent_navigation_filter", "ascent_covariance_filtered_batch")
 REDUCE_PROBE_ROWS = 14     # ASCENT_REDUCE_PROBE_ROWS
 PATHS = {"auto": 0, "fused": 1, "split_lane": 2, "split_wide": 3, "dense": 4, "persist": 5}     # enum ascent_path
 
@@ -183,6 +184,12 @@ def load():
     L.ascent_covariance_drifting_batch.restype = C.c_int
     L.ascent_covariance_drifting_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(AscentOptsC), C.c_void_p, C.c_int32] + [
         C.c_void_p] * 11 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int]
+    L.ascent_navigation_filter.restype = C.c_int
+    L.ascent_navigation_filter.argtypes = [C.c_void_p, C.c_int64, C.POINTER(AscentOptsC), C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [
+        C.c_int32] * 2 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int]
+    L.ascent_covariance_filtered_batch.restype = C.c_int
+    L.ascent_covariance_filtered_batch.argtypes = [C.c_void_p, C.c_int64, C.POINTER(AscentOptsC), C.c_void_p, C.c_int32] + [
+        C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int]
     L.ascent_sample_quantiles.restype = C.c_int
     L.ascent_sample_quantiles.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]

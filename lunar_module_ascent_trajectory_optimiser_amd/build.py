@@ -12,9 +12,9 @@ LIB = os.path.join(CSRC, "libascent.so")
 OBJ = os.path.join(CSRC, "_obj")
 SOURCES = ["ascent_solver.hip", "ascent_fused.hip", "ascent_pipeline.hip", "ascent_dense.hip", "ascent_blocktri.hip", "ascent_persist.hip",
            "ascent_hs.hip", "ascent_sens.hip", "ascent_flight.hip", "ascent_trim.hip", "ascent_disperse.hip", "ascent_guide.hip",
-           "ascent_lincov.hip", "ascent_quantile.hip"]
+           "ascent_lincov.hip", "ascent_navfilter.hip", "ascent_quantile.hip"]
 HEADERS = ["ascent_host.hpp", "ascent_device.hpp", "ascent_tile.hpp", "ascent_fused.hpp", "ascent_pipeline.hpp", "ascent_dense.hpp", "ascent_blocktri.hpp",
-           "ascent_persist.hpp", "ascent_persist_dev.hpp", "ascent_sens.hpp", "ascent_flight.hpp", "ascent_flight_dev.hpp", "ascent_tangent_dev.hpp", "ascent_trim.hpp", "ascent_disperse.hpp", "ascent_guide.hpp", "ascent_lincov.hpp", "ascent_quantile.hpp", os.path.join(ROOT, "include", "ascent.h")]
+           "ascent_persist.hpp", "ascent_persist_dev.hpp", "ascent_sens.hpp", "ascent_flight.hpp", "ascent_flight_dev.hpp", "ascent_tangent_dev.hpp", "ascent_trim.hpp", "ascent_disperse.hpp", "ascent_guide.hpp", "ascent_lincov.hpp", "ascent_lincov_dev.hpp", "ascent_navfilter.hpp", "ascent_quantile.hpp", os.path.join(ROOT, "include", "ascent.h")]
 
 
 def needs_build() -> bool:

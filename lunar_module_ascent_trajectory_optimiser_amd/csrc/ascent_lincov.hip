@@ -61,6 +61,7 @@
 #include "ascent_flight.hpp"
 #include "ascent_flight_dev.hpp"
 #include "ascent_lincov.hpp"
+#include "ascent_lincov_dev.hpp"
 #include "ascent_tangent_dev.hpp"
 
 namespace ascent {
@@ -161,17 +162,6 @@ ASC_DEV void stage_step(const Sweep<XCOLS> &L, const LincovArgs &A, const Flight
   fly_step_tangent<FORM>(F.d, z, dz, u, F.hs, F.m, col);
   ASC_UNROLL
   for (int i = 0; i < 7; i++) L.rec[g * REC + i * NCOL + col] = dz[i];
-}
-
-// the nominal node in metres about the centre and its radius rr: the operations of f_history_stats' altitude (ascent_disperse.hip:
-// altitude_of), none contracted, so that rr - R0 in nominal_out has the bits of hist_out.  The altitude's gradient is formed from
-// the same three values
-struct Radius { double X, Y, rr; };
-
-ASC_DEV Radius nominal_radius(double x, double y, double r_peri, double R0) {
-#pragma clang fp contract(off)
-  const double X = x * r_peri, Y = y * r_peri + R0;
-  return {X, Y, sqrt(X * X + Y * Y)};
 }
 
 // entry (xi, xc) of X_k from copy Xo of X_{k-1}; corr is the lane's own copy of corr_c.  pw is phi^k of the column's channel,

@@ -19,6 +19,7 @@
 //   guidance gains g_gains / g_gains_ff                   ascent_guide.hpp (ascent_guide.hip), one GainsIO for both calls
 //   dispersion f_disperse / _guided / _navigated          ascent_disperse.hpp (ascent_disperse.hip), one DisperseIO for all three
 //   linear covariance corridor l_lincov                   ascent_lincov.hpp (ascent_lincov.hip)
+//   navigation filter n_filter / l_lincov_filtered        ascent_navfilter.hpp (ascent_navfilter.hip)
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -43,6 +44,7 @@
 #include "ascent_disperse.hpp"
 #include "ascent_guide.hpp"
 #include "ascent_lincov.hpp"
+#include "ascent_navfilter.hpp"
 #include "ascent_quantile.hpp"
 
 using namespace ascent;
@@ -1026,6 +1028,86 @@ int lincov_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int
   return b.close();
 }
 
+// What ascent_navigation_filter and ascent_covariance_filtered_batch refuse of the measurements and the initial knowledge: the
+// counts, the null pointers and, with host pointers, the values
+int check_measurements(const double *sigma_nav, const double *filter_q, const double *meas_h, const double *meas_sigma, int32_t n_meas,
+                       int32_t meas_stride, int64_t batch, int ptr_is_device) {
+  if (n_meas < 1 || n_meas > ASCENT_NAVFILTER_MAX_MEAS) { snprintf(g_err, sizeof g_err, "n_meas out of range (1 .. %d)", ASCENT_NAVFILTER_MAX_MEAS); return ASCENT_E_ARG; }
+  if (meas_stride < 1) { snprintf(g_err, sizeof g_err, "meas_stride must be at least 1"); return ASCENT_E_ARG; }
+  if (!sigma_nav || !meas_h || !meas_sigma) { snprintf(g_err, sizeof g_err, "null sigma_nav, meas_h or meas_sigma"); return ASCENT_E_ARG; }
+  if (ptr_is_device) return 0;
+  for (int64_t i = 0; i < n_meas * batch; i++)
+    if (!(meas_sigma[i] > 0.0 && std::isfinite(meas_sigma[i]))) { snprintf(g_err, sizeof g_err, "meas_sigma not positive or not finite (measurement %d, problem %lld)", (int)(i / batch), (long long)(i % batch)); return ASCENT_E_ARG; }
+  for (int64_t i = 0; i < 7 * n_meas * batch; i++)
+    if (!std::isfinite(meas_h[i])) { snprintf(g_err, sizeof g_err, "meas_h not finite (measurement %d, problem %lld)", (int)(i / (7 * batch)), (long long)(i % batch)); return ASCENT_E_ARG; }
+  for (int64_t i = 0; i < 7 * batch; i++) {
+    if (!std::isfinite(sigma_nav[i])) { snprintf(g_err, sizeof g_err, "sigma_nav not finite (row %d, problem %lld)", (int)(i / batch), (long long)(i % batch)); return ASCENT_E_ARG; }
+    if (filter_q && !std::isfinite(filter_q[i])) { snprintf(g_err, sizeof g_err, "filter_q not finite (row %d, problem %lld)", (int)(i / batch), (long long)(i % batch)); return ASCENT_E_ARG; }
+  }
+  return 0;
+}
+
+// ascent_navigation_filter: io holds the caller's pointers
+int navfilter_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, NavFilterIO io, int device_id,
+                   void *stream_, int ptr_is_device) {
+  BlobCall b(p, batch, o, io.blob, stream_, ptr_is_device);
+  int rc = b.options();
+  if (rc) return rc;
+  if (!io.blob || !io.gain_l || !io.summary) { snprintf(g_err, sizeof g_err, "null solution blob, gain_l_out or summary_out"); return ASCENT_E_ARG; }
+  if ((rc = check_substeps(substeps))) return rc;
+  if ((rc = check_measurements(io.sigma_nav, io.filter_q, io.meas_h, io.meas_sigma, io.n_meas, io.meas_stride, batch, ptr_is_device))) return rc;
+  if ((rc = b.solvable())) return rc;
+  if ((rc = b.open(device_id, lincov_ws_bytes(o->n_nodes - 1, (long)batch)))) return rc;
+  Staging &st = b.st;
+  const size_t K = (size_t)b.K, B = (size_t)batch, M = (size_t)io.n_meas;
+  io.blob = b.blob;
+  io.sigma_nav = st.in(io.sigma_nav, 7 * B);
+  io.sigma_u = st.in(io.sigma_u, K * B);
+  io.filter_q = st.in(io.filter_q, 7 * B);
+  io.meas_h = st.in(io.meas_h, M * 7 * B);
+  io.meas_sigma = st.in(io.meas_sigma, M * B);
+  io.gain_l = st.out(io.gain_l, M * 7 * K * B);
+  io.pfilt = st.out(io.pfilt, ASCENT_NAV_COV_ROWS * K * B);
+  io.summary = st.out(io.summary, ASCENT_NAVFILTER_ROWS * B);
+  if ((rc = b.st.failed()) || (rc = navfilter_run(b.c, substeps, io, b.ws))) return rc;
+  return b.close();
+}
+
+// ascent_covariance_filtered_batch: io holds the caller's pointers.  The order of the shared refusals is lincov_call's.
+int filtered_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, FilteredIO io, int device_id,
+                  void *stream_, int ptr_is_device) {
+  BlobCall b(p, batch, o, io.blob, stream_, ptr_is_device);
+  int rc = b.options();
+  if (rc) return rc;
+  if (!io.blob || !io.sigma || !io.nominal || !io.cov) { snprintf(g_err, sizeof g_err, "null solution blob, sigma, nominal_out or cov_out"); return ASCENT_E_ARG; }
+  if (!io.nav_cov || !io.gain_l) { snprintf(g_err, sizeof g_err, "null nav_cov_out or gain_l"); return ASCENT_E_ARG; }
+  if ((rc = check_substeps(substeps))) return rc;
+  if (io.node_stride < 1 || io.node_stride > o->n_nodes - 1) { snprintf(g_err, sizeof g_err, "node_stride out of range (1 .. K = %d)", o->n_nodes - 1); return ASCENT_E_ARG; }
+  if (!io.gain_u && (io.gain_t || io.stretch_max)) { snprintf(g_err, sizeof g_err, "gain_t and stretch_max need gain_u"); return ASCENT_E_ARG; }
+  if ((rc = check_measurements(io.sigma_nav, nullptr, io.meas_h, io.meas_sigma, io.n_meas, io.meas_stride, batch, ptr_is_device))) return rc;
+  if ((rc = b.solvable())) return rc;
+  if ((rc = b.open(device_id, lincov_ws_bytes(o->n_nodes - 1, (long)batch)))) return rc;
+  Staging &st = b.st;
+  const size_t K = (size_t)b.K, B = (size_t)batch, M = (size_t)io.n_meas, NJ = (size_t)history_nodes(b.K, io.node_stride);
+  io.blob = b.blob;
+  io.sigma = st.in(io.sigma, ASCENT_DISPERSE_COLS * B);
+  io.sigma_u = st.in(io.sigma_u, K * B);
+  io.gain_u = st.in(io.gain_u, 7 * K * B);
+  io.gain_t = st.in(io.gain_t, 7 * B);
+  io.stretch_max = st.in(io.stretch_max, B);
+  io.sigma_nav = st.in(io.sigma_nav, 7 * B);
+  io.gain_l = st.in(io.gain_l, M * 7 * K * B);
+  io.meas_h = st.in(io.meas_h, M * 7 * B);
+  io.meas_sigma = st.in(io.meas_sigma, M * B);
+  io.nominal = st.out(io.nominal, ASCENT_HISTORY_QUANTITIES * NJ * B);
+  io.cov = st.out(io.cov, ASCENT_LINCOV_COV_ROWS * NJ * B);
+  io.nav_cov = st.out(io.nav_cov, ASCENT_NAV_COV_ROWS * NJ * B);
+  io.jac = st.out(io.jac, (size_t)ASCENT_HISTORY_QUANTITIES * ASCENT_LINCOV_COLS * NJ * B);
+  io.nav_jac = st.out(io.nav_jac, (size_t)7 * ASCENT_LINCOV_COLS * NJ * B);
+  if ((rc = b.st.failed()) || (rc = lincov_filtered_run(b.c, substeps, io, b.ws))) return rc;
+  return b.close();
+}
+
 // ascent_guidance_gains and ascent_guidance_feedforward (ff): io holds the caller's pointers
 int gains_call(const ascent_params *p, int64_t batch, const ascent_opts *o, int32_t substeps, bool ff, GainsIO io, int device_id,
                void *stream_, int ptr_is_device) {
@@ -1222,6 +1304,32 @@ int ascent_covariance_drifting_batch(const ascent_params *p, int64_t batch, cons
   io.nav_phi = nav_phi; io.nav_q = nav_q;
   io.node_stride = node_stride; io.nominal = nominal_out; io.cov = cov_out; io.jac = jac_hist_out;
   return lincov_call(p, batch, o, substeps, io, device_id, stream_, ptr_is_device, true);
+}
+
+int ascent_navigation_filter(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                             const double *sigma_nav, const double *sigma_u, const double *filter_q, const double *meas_h,
+                             const double *meas_sigma, int32_t n_meas, int32_t meas_stride, double *gain_l_out, double *pfilt_out,
+                             double *summary_out, int device_id, void *stream_, int ptr_is_device) {
+  NavFilterIO io{};
+  io.blob = sol_blob; io.sigma_nav = sigma_nav; io.sigma_u = sigma_u; io.filter_q = filter_q;
+  io.meas_h = meas_h; io.meas_sigma = meas_sigma; io.n_meas = n_meas; io.meas_stride = meas_stride;
+  io.gain_l = gain_l_out; io.pfilt = pfilt_out; io.summary = summary_out;
+  return navfilter_call(p, batch, o, substeps, io, device_id, stream_, ptr_is_device);
+}
+
+int ascent_covariance_filtered_batch(const ascent_params *p, int64_t batch, const ascent_opts *o, const double *sol_blob, int32_t substeps,
+                                     const double *sigma, const double *sigma_u, const double *gain_u, const double *gain_t,
+                                     const double *stretch_max, const double *sigma_nav, const double *gain_l, const double *meas_h,
+                                     const double *meas_sigma, int32_t n_meas, int32_t meas_stride, int32_t node_stride,
+                                     double *nominal_out, double *cov_out, double *nav_cov_out, double *jac_hist_out,
+                                     double *nav_jac_out, int device_id, void *stream_, int ptr_is_device) {
+  FilteredIO io{};
+  io.blob = sol_blob; io.sigma = sigma; io.sigma_u = sigma_u;
+  io.gain_u = gain_u; io.gain_t = gain_t; io.stretch_max = stretch_max;
+  io.sigma_nav = sigma_nav; io.gain_l = gain_l; io.meas_h = meas_h; io.meas_sigma = meas_sigma;
+  io.n_meas = n_meas; io.meas_stride = meas_stride; io.node_stride = node_stride;
+  io.nominal = nominal_out; io.cov = cov_out; io.nav_cov = nav_cov_out; io.jac = jac_hist_out; io.nav_jac = nav_jac_out;
+  return filtered_call(p, batch, o, substeps, io, device_id, stream_, ptr_is_device);
 }
 
 int ascent_sample_quantiles(const double *values, int32_t quantities, int32_t groups, int32_t valid_quantities, int32_t samples,

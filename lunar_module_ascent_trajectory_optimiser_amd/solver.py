@@ -690,18 +690,118 @@ class LinearCorridor:
     nominal: np.ndarray             # (batch, NJ, 10) the bits of DispersionHistory.nominal
     cov: np.ndarray                 # (batch, NJ, 10, 10) symmetric
     jacobian: np.ndarray | None     # (batch, NJ, 10, 32) d HISTORY_ROWS / d LINCOV_COLS (want_jacobian=True)
+    # with a navigation filter (linear_corridor(filter=...); include/ascent.h: ascent_covariance_filtered_batch): the estimation
+    # error e = z-hat - z after the update at the node, scaled units; columns 24..30 of both jacobians are then e_0
+    # (plain attributes, set by linear_corridor: the dataclass keeps its four fields, so dataclasses.replace, asdict and == do not
+    # see them -- copy them by hand)
+    nav_cov = None                  # (batch, NJ, 7, 7) its true covariance, symmetric; None without a filter
+    nav_jacobian = None             # (batch, NJ, 7, 32) d e / d LINCOV_COLS (want_jacobian=True); None without a filter
 
     @property
     def std(self) -> np.ndarray:
         """(batch, NJ, 10)"""
         return np.sqrt(np.diagonal(self.cov, axis1=2, axis2=3))
 
+    @property
+    def nav_std(self) -> np.ndarray | None:
+        """(batch, NJ, 7); None without a filter"""
+        return None if self.nav_cov is None else np.sqrt(np.diagonal(self.nav_cov, axis1=2, axis2=3))
+
+
+NAVFILTER_ROWS = ("status", "first_bad", "meas_nodes", "substeps")
+NAVFILTER_MAX_MEAS = 4
+
+
+def _sym7(rows):
+    """(..., 7, 7) symmetric from (..., 28), the upper triangle row by row"""
+    iu = np.triu_indices(7)
+    full = np.empty(rows.shape[:-1] + (7, 7))
+    full[..., iu[0], iu[1]] = rows
+    full[..., iu[1], iu[0]] = rows
+    return full
+
+
+@dataclasses.dataclass
+class NavigationFilter:
+    """A linear Kalman filter designed along a flown solution (navigation_filter; include/ascent.h: ascent_navigation_filter).
+    At node k, measurement i corrects the estimate by gain_l[:, k-1, i] times its innovation.  Problem index first."""
+    gain_l: np.ndarray              # (batch, K, M, 7); exactly zero at the nodes without a measurement
+    cov: np.ndarray                 # (batch, K, 7, 7) the filter's own covariance P-hat after the update at node k = 1 .. K
+    status: np.ndarray              # (batch,) 0 ok, 2 frozen: an innovation variance was <= 0 or not finite
+    first_bad: np.ndarray           # (batch,) the first such node, 0: none; gain_l and cov are NaN from it on
+    meas_nodes: np.ndarray          # (batch,) the number of measurement nodes
+    substeps: np.ndarray            # (batch,)
+    # the inputs it was designed with
+    nav_sigma: np.ndarray           # (batch, 7)
+    meas_rows: np.ndarray           # (batch, M, 7)
+    meas_sigma: np.ndarray          # (batch, M)
+    meas_stride: int
+    control_sigma: np.ndarray | None    # (batch, K)
+    process_sigma: np.ndarray | None    # (batch, 7)
+
+    @property
+    def std(self) -> np.ndarray:
+        """(batch, K, 7)"""
+        return np.sqrt(np.diagonal(self.cov, axis1=2, axis2=3))
+
+
+def _measurement_arrays(meas_rows, meas_sigma, B):
+    """meas_rows (M, 7) or (batch, M, 7) and meas_sigma (M,) or (batch, M), M in 1 .. 4 -> (rows (B, M, 7), sigma (B, M))"""
+    h = np.asarray(meas_rows, dtype=np.float64)
+    if h.ndim == 1:
+        h = h[None]
+    if h.ndim not in (2, 3) or h.shape[-1] != 7 or not 1 <= h.shape[-2] <= NAVFILTER_MAX_MEAS:
+        raise ValueError(f"meas_rows must have shape (M, 7) or (batch, M, 7), M in 1 .. {NAVFILTER_MAX_MEAS}")
+    M = h.shape[-2]
+    try:
+        h = np.ascontiguousarray(np.broadcast_to(h, (B, M, 7)))
+    except ValueError:
+        raise ValueError(f"meas_rows must broadcast to {(B, M, 7)}") from None
+    sg = _sigma_rows(meas_sigma, M, B, "meas_sigma")
+    if meas_sigma is None or not np.all((sg > 0) & np.isfinite(sg)):
+        raise ValueError("meas_sigma must be positive and finite")
+    if not np.isfinite(h).all():
+        raise ValueError("meas_rows must be finite")
+    return h, sg
+
+
+def navigation_filter(params, sol_blob: np.ndarray, nt: int, *, nav_sigma, meas_rows, meas_sigma, meas_stride: int = 1,
+                      control_sigma=None, process_sigma=None, scheme=0, formulation=0, terminal=0, move_penalty: bool = False,
+                      substeps: int = 0, device: int = 0) -> NavigationFilter:
+    """Designs a linear Kalman filter along the flight of fly_batch (include/ascent.h: ascent_navigation_filter): the forward Riccati
+    sweep P-hat_k^- = Phi_k P-hat_{k-1} Phi_k' + control_sigma_k^2 g_k g_k' + diag(process_sigma^2) from P-hat_0 = diag(nav_sigma^2),
+    with M scalar measurements meas_rows . z of standard deviation meas_sigma, scaled units, processed one after the other at every
+    meas_stride-th node (a stride above K: none).  nav_sigma (7,) or (batch, 7); meas_rows (M, 7) or (batch, M, 7), M in 1 .. 4;
+    meas_sigma (M,) or (batch, M), positive; control_sigma a scalar, (K,) or (batch, K) or None; process_sigma (7,) or (batch, 7) or
+    None.  Returns a NavigationFilter, which linear_corridor(filter=...) takes."""
+    L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
+    stride = int(meas_stride)
+    if stride < 1:
+        raise ValueError("meas_stride must be at least 1")
+    if nav_sigma is None:
+        raise ValueError("nav_sigma is required")
+    ns = _sigma_rows(nav_sigma, 7, B, "nav_sigma")
+    h, sg = _measurement_arrays(meas_rows, meas_sigma, B)
+    M = h.shape[1]
+    us = None if control_sigma is None else _sigma_rows(control_sigma, K, B, "control_sigma")
+    qs = None if process_sigma is None else _sigma_rows(process_sigma, 7, B, "process_sigma")
+    if not np.isfinite(ns).all() or (qs is not None and not np.isfinite(qs).all()):
+        raise ValueError("nav_sigma and process_sigma must be finite")
+    t = lambda a: None if a is None else np.ascontiguousarray(np.moveaxis(a, 0, -1))
+    ns_c, us_c, qs_c, h_c, sg_c = t(ns), t(us), t(qs), t(h), t(sg)
+    gl, pf, summ = np.empty((M, 7, K, B)), np.empty((28, K, B)), np.empty((len(NAVFILTER_ROWS), B))
+    _lib.check(L.ascent_navigation_filter(_ptr(P), B, C.byref(o), _ptr(blob), int(substeps), _ptr(ns_c), _ptr(us_c), _ptr(qs_c),
+                                          _ptr(h_c), _ptr(sg_c), M, stride, _ptr(gl), _ptr(pf), _ptr(summ), device, None, 0))
+    col = lambda r: summ[r].astype(np.int64)
+    return NavigationFilter(np.ascontiguousarray(gl.transpose(3, 2, 0, 1)), _sym7(pf.transpose(2, 1, 0)), col(0), col(1), col(2), col(3),
+                            ns, h, sg, stride, us, qs)
+
 
 def linear_corridor(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, control_sigma=None, tf_sigma=None, z0_sigma=None,
                     guidance: GuidanceResult | None = None, nav_sigma=None, knowledge_sigma=None, history=True,
                     want_jacobian: bool = True, scheme=0, formulation=0, terminal=0, move_penalty: bool = False, substeps: int = 0,
                     device: int = 0, nav_tau=None, knowledge_tau=None, nav_steady_sigma=None,
-                    knowledge_steady_sigma=None) -> LinearCorridor:
+                    knowledge_steady_sigma=None, filter: NavigationFilter | None = None) -> LinearCorridor:
     """Linear covariance analysis (include/ascent.h: ascent_covariance_history_batch): the flight disperse_batch(history=...)
     samples, linearised about the nominal flight and swept forward once per problem -- clips ignored, the execution errors of
     control_sigma independent white noise.  The sigmas broadcast as disperse_batch's and `guidance` is taken as there: None the
@@ -710,12 +810,20 @@ def linear_corridor(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, 
     terminal 2 is accepted.
     nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma: the time-varying navigation error of disperse_batch, taken
     as there (include/ascent.h: ascent_covariance_drifting_batch); the nav columns of the jacobian stay the derivative with
-    respect to the initial errors.  Without them the call is ascent_covariance_history_batch, exactly as before."""
+    respect to the initial errors.  Without them the call is ascent_covariance_history_batch, exactly as before.
+    filter: a NavigationFilter (or anything with gain_l (batch, K, M, 7), meas_rows, meas_sigma, meas_stride and nav_sigma): the
+    knowledge error the law steers on is that filter's estimation error (include/ascent.h: ascent_covariance_filtered_batch), and
+    the result gains nav_cov, nav_std and nav_jacobian.  nav_sigma, the 1-sigma of the initial error, is the filter's unless
+    given; guidance None is the open loop, which the filter does not touch.  Not with knowledge_sigma, a feed-forward guidance or
+    the nav_tau keywords."""
     L, P, B, K, blob, o = _blob_call(params, sol_blob, nt, scheme, formulation, terminal, move_penalty)
     stride = 1 if history is True else int(history) if history is not False and history is not None else 0
     if not 1 <= stride <= K:
         raise ValueError(f"history: the node stride must be in 1 .. K = {K}")
     _, _, _, _, sig, sig_u = _dispersion_sigmas(z0_sigma, param_sigma, tf_sigma, control_sigma, K, B)
+    if filter is not None:
+        return _filtered_corridor(L, P, B, K, blob, o, int(substeps), device, stride, sig, sig_u, guidance, filter, nav_sigma, want_jacobian,
+                                  knowledge_sigma, (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma))
     if guidance is None and (nav_sigma is not None or knowledge_sigma is not None):
         raise ValueError("nav_sigma and knowledge_sigma need guidance")
     drifting = any(v is not None for v in (nav_tau, knowledge_tau, nav_steady_sigma, knowledge_steady_sigma))
@@ -742,6 +850,50 @@ def linear_corridor(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, 
     full[:, :, iu[1], iu[0]] = cov.transpose(2, 1, 0)
     return LinearCorridor(nodes, np.ascontiguousarray(nom.transpose(2, 1, 0)), full,
                           None if jac is None else np.ascontiguousarray(jac.transpose(3, 2, 0, 1)))
+
+
+def _filtered_corridor(L, P, B, K, blob, o, substeps, device, stride, sig, sig_u, guidance, nf, nav_sigma, want_jacobian, knowledge_sigma,
+                       drift):
+    """linear_corridor(filter=nf): ascent_covariance_filtered_batch"""
+    if knowledge_sigma is not None:
+        raise ValueError("knowledge_sigma cannot be combined with filter (the filter does not estimate theta)")
+    if any(v is not None for v in drift):
+        raise ValueError("nav_tau, knowledge_tau, nav_steady_sigma and knowledge_steady_sigma cannot be combined with filter")
+    if guidance is not None and getattr(guidance, "ff_u", None) is not None:
+        raise ValueError("a feed-forward guidance cannot be combined with filter")
+    gl = np.asarray(nf.gain_l, dtype=np.float64)
+    if gl.ndim != 4 or gl.shape[0] != B or gl.shape[1] != K or gl.shape[3] != 7 or not 1 <= gl.shape[2] <= NAVFILTER_MAX_MEAS:
+        raise ValueError(f"filter.gain_l must have shape (batch, K, M, 7) = {(B, K, 'M', 7)}, M in 1 .. {NAVFILTER_MAX_MEAS}")
+    M = gl.shape[2]
+    h, sg = _measurement_arrays(nf.meas_rows, nf.meas_sigma, B)
+    if h.shape[1] != M:
+        raise ValueError("filter.meas_rows and filter.gain_l disagree on the number of measurements")
+    ms = int(nf.meas_stride)
+    if ms < 1:
+        raise ValueError("filter.meas_stride must be at least 1")
+    ns = _sigma_rows(nf.nav_sigma if nav_sigma is None else nav_sigma, 7, B, "nav_sigma")
+    if not np.isfinite(ns).all():
+        raise ValueError("nav_sigma must be finite")
+    law = [None] * 3 if guidance is None else list(_feedback_arrays(guidance, K, B))
+    t = lambda a: np.ascontiguousarray(np.moveaxis(a, 0, -1))
+    ns_c, h_c, sg_c, gl_c = t(ns), t(h), t(sg), np.ascontiguousarray(gl.transpose(2, 3, 1, 0))
+    nodes = history_nodes(K, stride)
+    NJ = len(nodes)
+    nom, cov, ncov = np.empty((10, NJ, B)), np.empty((55, NJ, B)), np.empty((28, NJ, B))
+    jac = np.empty((10, len(LINCOV_COLS), NJ, B)) if want_jacobian else None
+    njac = np.empty((7, len(LINCOV_COLS), NJ, B)) if want_jacobian else None
+    _lib.check(L.ascent_covariance_filtered_batch(_ptr(P), B, C.byref(o), _ptr(blob), substeps, _ptr(sig), _ptr(sig_u), *[_ptr(x) for x in law],
+                                                  _ptr(ns_c), _ptr(gl_c), _ptr(h_c), _ptr(sg_c), M, ms, stride, _ptr(nom), _ptr(cov),
+                                                  _ptr(ncov), _ptr(jac), _ptr(njac), device, None, 0))
+    full = np.empty((B, NJ, 10, 10))
+    iu = np.triu_indices(10)
+    full[:, :, iu[0], iu[1]] = cov.transpose(2, 1, 0)
+    full[:, :, iu[1], iu[0]] = cov.transpose(2, 1, 0)
+    lc = LinearCorridor(nodes, np.ascontiguousarray(nom.transpose(2, 1, 0)), full,
+                        None if jac is None else np.ascontiguousarray(jac.transpose(3, 2, 0, 1)))
+    lc.nav_cov = _sym7(ncov.transpose(2, 1, 0))
+    lc.nav_jacobian = None if njac is None else np.ascontiguousarray(njac.transpose(3, 2, 0, 1))
+    return lc
 
 
 def disperse_batch(params, sol_blob: np.ndarray, nt: int, *, param_sigma=None, control_sigma=None, tf_sigma=None, z0_sigma=None,
